@@ -4,7 +4,13 @@ raleigh/core/solver.py:854-861,968-974,1321-1339,1360,1376-1381,1444-1447) on a
 synthetic n x m block, n = 215^3 = 9 938 375 (the "n = 10^7" roofline point of
 BASELINE.json), m = 32, fp64, A = 7-point 3-D Laplacian.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--full` adds
+everything else the benchmark measures and checks: the batched iteration, the whole op mix, the
+Gram roofline, the end-to-end solves, the other BASELINE configurations and the CPU baseline
+(N = 1), the other scaling mode and the collectives (N > 1).  `--dump-outputs DIR` writes what
+the last timed step computed as DIR/<name>.npy (see dump_outputs).
 
 N > 1 runs one rank per GPU under torch.distributed.run (RCCL) -- started by the driver, or, when WORLD_SIZE is not
 set, by this script itself as a child process (`python bench.py --gpus 8` works as typed): the rows
@@ -14,7 +20,7 @@ ranks -- the north-star's ">= 6x at 8 GPUs at n = 10M" question; `value` is the 
 job's rate, so value(N) / value(1) is the speed-up.  `--scaling weak`: every GPU holds a
 215^3-row shard (the grid grows along z: 215 x 215 x 215 N), per-GPU work is fixed and
 `value` is the aggregate over the N GPUs.  At N = 1 the two are the same workload; with
-N > 1 the run also reports the other mode under "also", the strong figure of the batched
+N > 1 and --full the run also reports the other mode under "also", the strong figure of the batched
 (5 round trips) iteration under "fused", the measured latency of one reduction round trip
 under "collectives", and BASELINE config 4 (pca of a row-sharded 62 500 N x 40 000 matrix)
 under "config4".
@@ -47,6 +53,10 @@ HBM_PEAK_GBS = 8000.0        # MI355X HBM3E datasheet peak (MI355X_MICROARCH.md)
 class InnerIteration:
     """The Gram / dots / SpMM sequence of one steady-state iteration (standard problem,
     identity preconditioner, no deflation) on blocks X, AX, Y, AY, Z, AZ, W."""
+
+    # names of what headline() returns, in its order
+    HEADLINE_OUTPUTS = ('xax', 'xbx', 'w_dots', 'zay', 'zby', 'y_dots', 'z_dots', 'q', 'y_dots_norm', 'xby', 'yby',
+                        'xay', 'yay')
 
     def __init__(self, blocks, op):
         self.b, self.op = blocks, op
@@ -670,6 +680,26 @@ def config4_sharded(L, comm, rows_per_gpu=62500, Nn=40000, r=1280, npc=1000, m=1
             'max_sigma_error_over_sigma_max': float(np.max(np.abs(sv - exact)) / exact[0])}
 
 
+def dump_outputs(path, results, ay, write, rows=65536, seed=0):
+    """What one headline step hands its caller, as path/<name>.npy: the Gram matrices and dots of
+    InnerIteration.HEADLINE_OUTPUTS, and `ay_rows`, a fixed sample of rows of the SpMM's output block AY
+    (`rows` of them drawn with `seed`, ascending; every row when there are no more), rows x m.  Every rank
+    takes part (a sharded block is assembled vector by vector); only `write` ranks write."""
+    n, m = ay.dimension(), ay.nvec()
+    idx = np.arange(n) if n <= rows else np.sort(np.random.default_rng(seed).choice(n, rows, replace=False))
+    sample = np.empty((len(idx), m), dtype=np.float64)
+    for j in range(m):
+        sample[:, j] = ay.data(j)[idx]
+    if not write:
+        return
+    os.makedirs(path, exist_ok=True)
+    arrays = dict(zip(InnerIteration.HEADLINE_OUTPUTS, results))
+    arrays['ay_rows'] = sample
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(os.path.join(path, name + '.npy'), a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+
+
 def launch_ranks(n):
     """Runs this script under torch.distributed.run with n ranks on this node (one per GPU, rendezvous on 127.0.0.1 at a
     free port) and prints the one JSON line its rank 0 wrote; returns the launcher's exit code."""
@@ -704,6 +734,11 @@ def main():
     ap.add_argument('--side', type=int, default=215, help='lap3d side (n = side^3)')
     ap.add_argument('--m', type=int, default=32)
     ap.add_argument('--scaling', choices=('weak', 'strong'), default='strong')
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beside the headline: batched iteration, op mix, roofline, solves, configs, '
+                         'CPU baseline, the other scaling mode and the collectives (the options below apply to it)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-configs', action='store_true', help='skip the config legs (2 / 3 / 5 / one config-4 shard at N = 1, the '
                                                             'row-sharded config 4 on the sharded path)')
@@ -781,8 +816,9 @@ def main():
         comm.dist.all_reduce(t, op=comm.dist.ReduceOp.MAX)
         return float(t.item())
 
-    def run_mode(mode, steps, warmup, extras):
-        """Times `steps` headline iterations on lap3d side x side x nzg (weak: nzg = side * world)."""
+    def run_mode(mode, steps, warmup, extras, dump=None):
+        """Times `steps` headline iterations on lap3d side x side x nzg (weak: nzg = side * world); with `dump`, writes
+        what the last of them computed there (before the extras touch the blocks)."""
         nzg = side * world if mode == 'weak' else side
         n = side * side * nzg
         nnz = 7 * n - 2 * (side * nzg * 2 + side * side)      # 7-point stencil minus the six faces
@@ -814,11 +850,13 @@ def main():
         t0 = time.perf_counter()
         for _ in range(steps):
             _lib.check(L.rlh_timer_start())
-            it.headline()
+            last = it.headline()
             _lib.check(L.rlh_timer_stop(ctypes.byref(ms)))
             per_step.append(ms.value)
         sync_all()
         elapsed = max_over_ranks(time.perf_counter() - t0)
+        if dump is not None:
+            dump_outputs(dump, last, blocks[3], rank == 0)
         ms_per_step = elapsed / steps * 1e3
         nbytes, parts = InnerIteration.headline_bytes(n, m, es, nnz)
         res = {'mode': mode, 'n': n, 'nnz': nnz, 'nzg': nzg, 'nloc': nloc, 'ms_per_step': ms_per_step,
@@ -878,7 +916,32 @@ def main():
             res['copy_gbs'] = 2 * nloc * m * es / (max(ms.value, 1e-9) / reps * 1e-3) / 1e9
         return res
 
-    main_res = run_mode(args.scaling, args.steps, args.warmup, True)
+    main_res = run_mode(args.scaling, args.steps, args.warmup, args.full, args.dump_outputs)
+    n, nnz, nzg = main_res['n'], main_res['nnz'], main_res['nzg']
+    out = {'metric': 'inner-iter GB/s vs HBM roofline (Gram+dots+SpMM of one block-JCG iteration)',
+           'value': round(main_res['value'], 1), 'unit': 'GB/s', 'n_gpus': world, 'steps': args.steps,
+           'warmup': args.warmup, 'ms_per_step': round(main_res['ms_per_step'], 4), 'higher_is_better': True,
+           'scaling': args.scaling, 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
+           'config': {'workload': 'block-JCG inner iteration: 9 Gram + 4 dots + 1 SpMM, n=%dx%dx%d=%d rows '
+                                  '(%d per GPU), m=%d, 7-pt Laplacian nnz=%d, rows sharded over %d GPU(s), %s scaling'
+                                  % (side, side, nzg, n, main_res['nloc'], m, nnz, world, args.scaling),
+                      'n': n, 'm': m, 'nnz': nnz, 'algorithmic_bytes_per_step': main_res['nbytes'],
+                      'bytes_breakdown': main_res['parts']},
+           'ms_per_step_median_hip_events': round(main_res['median_ms'], 4)}
+
+    def finish(ok):
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(out) + '\n').encode())
+        if comm is not None:
+            comm.dist.destroy_process_group()
+        if not ok:
+            sys.exit(3)
+
+    if not args.full:
+        finish(True)
+        return
+
     also = None
     if world > 1:
         other = 'strong' if args.scaling == 'weak' else 'weak'
@@ -903,18 +966,7 @@ def main():
                 'inner_iteration_frac': round(main_res['value'] / world / HBM_PEAK_GBS, 4),
                 'device_copy_ceiling_gbs': round(main_res.get('copy_gbs', 0.0), 1),
                 'frac_of_copy_ceiling': round(achieved / max(main_res.get('copy_gbs', 0.0), 1e-9), 4)}
-    n, nnz, nzg = main_res['n'], main_res['nnz'], main_res['nzg']
-    out = {'metric': 'inner-iter GB/s vs HBM roofline (Gram+dots+SpMM of one block-JCG iteration)',
-           'value': round(main_res['value'], 1), 'unit': 'GB/s', 'n_gpus': world, 'steps': args.steps,
-           'warmup': args.warmup, 'ms_per_step': round(main_res['ms_per_step'], 4), 'higher_is_better': True,
-           'scaling': args.scaling, 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
-           'config': {'workload': 'block-JCG inner iteration: 9 Gram + 4 dots + 1 SpMM, n=%dx%dx%d=%d rows '
-                                  '(%d per GPU), m=%d, 7-pt Laplacian nnz=%d, rows sharded over %d GPU(s), %s scaling'
-                                  % (side, side, nzg, n, main_res['nloc'], m, nnz, world, args.scaling),
-                      'n': n, 'm': m, 'nnz': nnz, 'algorithmic_bytes_per_step': main_res['nbytes'],
-                      'bytes_breakdown': main_res['parts']},
-           'ms_per_step_median_hip_events': round(main_res['median_ms'], 4),
-           'roofline': roofline, 'fused': main_res['fused'], 'all_ops': main_res['all_ops']}
+    out.update(roofline=roofline, fused=main_res['fused'], all_ops=main_res['all_ops'])
     if also is not None:
         out['also'] = also
     if comm is not None:
@@ -970,13 +1022,7 @@ def main():
             ok = guarded('configs', lambda: config_legs(L)) and ok
         if not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(side, m)
-    if rank == 0:
-        sys.stdout.flush()
-        os.write(json_fd, (json.dumps(out) + '\n').encode())
-    if comm is not None:
-        comm.dist.destroy_process_group()
-    if not ok:
-        sys.exit(3)
+    finish(ok)
 
 
 if __name__ == '__main__':

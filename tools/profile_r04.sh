@@ -9,7 +9,7 @@ TAG=${1:-r04}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O
 bash $R/tools/profile_round.sh $TAG > $O/round.txt 2>&1 || { tail -5 $O/round.txt; exit 1; }
 tail -42 $O/round.txt
-cd $R && timeout -k 10 400 python bench.py --gpus 1 --force-dist --no-cpu-baseline --ilu-side 0 --ilu-large-side 0 > $O/bench_forced.json 2> $O/bench_forced.err || echo "FAILED forced bench"
+cd $R && timeout -k 10 400 python bench.py --full --gpus 1 --force-dist --no-cpu-baseline --ilu-side 0 --ilu-large-side 0 > $O/bench_forced.json 2> $O/bench_forced.err || echo "FAILED forced bench"
 cd /tmp && export TMPDIR=/tmp
 run() {  # name, counters ('' = kernel trace + stats), command...
   local name=$1 pmc=$2; shift 2
