@@ -363,6 +363,33 @@ int rlh_dense_apply_r1(int dtype, int64_t M, int64_t N, const void *A, int64_t l
                        int transp, int64_t m, const void *X, int64_t ldx, void *Y, int64_t ldy,
                        const void *d_u, const void *d_c);
 
+/* ---- general (rectangular) sparse data matrix: the operator of truncated SVD and PCA on sparse data
+ *      (the reference's interfaces take dense arrays only; raleigh/examples/truncated_svd.py:63-72 compares
+ *      against scipy's svds on the host)
+ * A: M x N, 0-based CSR in HOST memory (indptr: M + 1 int64, indices: int32 column indices, values of the
+ * dtype), duplicates summed; the order of the entries within a row does not matter.  rlh_spd_create copies
+ * A to the device and builds a CSR copy of A^H once (values conjugated, each row in ascending order of A's
+ * row index; on the host threads, RLH_HOST_THREADS), so that both products run on one row-parallel kernel
+ * with the work split by nonzeros (long rows of A and of A^H are shared among several wave subgroups and
+ * their partial sums combined in a fixed order: results are bit-identical from call to call and between
+ * handles of the same matrix).  Needs rlh_init; M, N < 2^31.
+ * rlh_spd_apply:  Y[:, j] = Op(A) X[:, j] - c[j] u,  Op(A) = A (transp 0: X has N rows, Y M rows) or A^H
+ * (transp 1: X has M rows, Y N rows); X, Y column-major DEVICE blocks of m vectors; u, c DEVICE arrays with
+ * the meaning of rlh_dense_apply_r1 (u NULL: a vector of ones; u and c NULL: the plain product).  The
+ * handle owns a workspace (the block interleaved by rows, the result by rows, the partial sums) that grows
+ * when a wider block than before is applied (that call synchronises the stream once); otherwise the call is
+ * asynchronous on the library stream and allocates nothing.
+ * rlh_spd_info: sizes, stored entries, device bytes held (both CSR copies, the partition, the workspace).
+ * rlh_spd_stats: workspace bytes and the seconds taken by the transpose at creation. */
+typedef struct rlh_spd *rlh_spd_t;
+int rlh_spd_create(rlh_spd_t *h, int dtype, int64_t n_rows, int64_t n_cols, const int64_t *indptr,
+                   const int32_t *indices, const void *values);
+int rlh_spd_destroy(rlh_spd_t h);
+int rlh_spd_info(rlh_spd_t h, int64_t *n_rows, int64_t *n_cols, int64_t *nnz, int64_t *device_bytes);
+int rlh_spd_stats(rlh_spd_t h, int64_t *workspace_bytes, double *transpose_seconds);
+int rlh_spd_apply(rlh_spd_t h, int transp, int64_t m, const void *X, int64_t ldx, void *Y, int64_t ldy,
+                  const void *d_u, const void *d_c);
+
 /* ---- profiling aid: HIP-event time of the last `count` kernels ---- */
 int rlh_timer_start(void);
 int rlh_timer_stop(float *milliseconds);

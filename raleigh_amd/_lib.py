@@ -101,6 +101,11 @@ SIGNATURES = {
     'rlh_sptrsv_destroy': [_p],
     'rlh_dense_apply': [_int, _i64, _i64, _p, _i64, _int, _int, _i64, _p, _i64, _p, _i64],
     'rlh_dense_apply_r1': [_int, _i64, _i64, _p, _i64, _int, _int, _i64, _p, _i64, _p, _i64, _p, _p],
+    'rlh_spd_create': [ctypes.POINTER(_p), _int, _i64, _i64, _p, _p, _p],
+    'rlh_spd_destroy': [_p],
+    'rlh_spd_info': [_p, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
+    'rlh_spd_stats': [_p, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)],
+    'rlh_spd_apply': [_p, _int, _i64, _p, _i64, _p, _i64, _p, _p],
     'rlh_timer_start': [],
     'rlh_timer_stop': [ctypes.POINTER(ctypes.c_float)],
 }

@@ -28,8 +28,10 @@ import sys
 
 import numpy
 import scipy.linalg as sla
+import scipy.sparse
 
 from ..algebra.dense_matrix import AMatrix
+from ..algebra.sparse_matrix import SparseAMatrix
 from ..core.solver import Options
 from .pca import PartialSVD, _SingularValueCriteria, _FrobeniusStopping, _project_out
 
@@ -65,6 +67,8 @@ def _eigh(a, single=False):
 def _as_matrix(A, arch):
     if hasattr(A, 'as_operator'):
         return A
+    if scipy.sparse.issparse(A):
+        return SparseAMatrix(A, arch=arch)
     if not isinstance(A, numpy.ndarray) or not A.flags['C_CONTIGUOUS']:
         raise ValueError('matrix must be C_CONTIGUOUS')
     return AMatrix(A, arch=arch)
@@ -319,8 +323,12 @@ class LowerRankApproximation:
     # ------------------------------------------------------------------ incremental
     def icompute(self, matrix, batch_size, opt=None, rank=-1, tol=0, norm='f', max_rank=-1, svtol=1e-3,
                  shift=False, arch='hip', verb=0):
-        """compute() on the first `batch_size` rows of the host array `matrix`, update() with every further
-        batch (lra.py:381-425): one batch of the data in HBM at a time."""
+        """compute() on the first `batch_size` rows of the host array `matrix` (an ndarray or a scipy.sparse matrix,
+        cut into CSR row slices), update() with every further batch (lra.py:381-425): one batch of the data in
+        HBM at a time."""
+        if scipy.sparse.issparse(matrix):
+            from ..algebra.hip.sparse_data import canonical_csr
+            matrix = canonical_csr(matrix)
         rows = matrix.shape[0]
         batch_size = max(1, min(batch_size, rows))
         first, batch = 0, 0

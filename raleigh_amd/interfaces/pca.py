@@ -18,6 +18,7 @@ import time
 
 import numpy
 import numpy.linalg as nla
+import scipy.sparse
 
 from ..algebra.dense_matrix import AMatrix
 from ..core.solver import Problem, Solver, Options
@@ -280,7 +281,8 @@ class PartialSVD:
 
 
 def pca(A, npc=-1, tol=0, have=None, batch_size=None, verb=0, arch='hip', norm='f', mpc=-1, svtol=1e-3, opt=None):
-    '''PCA of the rows of A: returns (mean (1, n), trans (m, k), comps (k, n)) with
+    '''PCA of the rows of A (a C-contiguous ndarray or a scipy.sparse matrix / array: the mean shift is then
+    applied implicitly, A - e mean is never formed): returns (mean (1, n), trans (m, k), comps (k, n)) with
     trans @ comps ~ A - e mean, comps rows orthonormal, columns of trans in descending
     order of norm (raleigh/interfaces/pca.py:16-164).
 
@@ -307,7 +309,7 @@ def pca(A, npc=-1, tol=0, have=None, batch_size=None, verb=0, arch='hip', norm='
         else:
             lra.update(matrix, opt=opt, rank=npc, tol=tol, norm=norm, max_rank=mpc, svtol=svtol, verb=verb)
     else:
-        if not isinstance(A, numpy.ndarray) or not A.flags['C_CONTIGUOUS']:
+        if not scipy.sparse.issparse(A) and (not isinstance(A, numpy.ndarray) or not A.flags['C_CONTIGUOUS']):
             raise ValueError('matrix must be C_CONTIGUOUS')
         lra.icompute(A, batch_size, opt=opt, rank=npc, tol=tol, norm=norm, max_rank=mpc, svtol=svtol, shift=True,
                      verb=verb, arch=arch)

@@ -15,8 +15,10 @@ absolute (-tol) for tol < 0.  Interactive stopping (tol = 0) is not offered.
 import math
 
 import numpy
+import scipy.sparse
 
 from ..algebra.dense_matrix import AMatrix
+from ..algebra.sparse_matrix import SparseAMatrix
 from ..core.solver import Options
 from .pca import PartialSVD
 
@@ -134,6 +136,8 @@ def truncated_svd(A, opt=None, nsv=-1, tol=0, norm='s', msv=-1, vtol=0, arch='hi
     '''Returns u (m, k), sigma (k,) in descending order and vt (k, n) with A vt^H = u diag(sigma), u and
     vt^H orthonormal (raleigh/interfaces/truncated_svd.py:24-127).
 
+    A : a 2D ndarray, a scipy.sparse matrix or array (the device operator of SparseAMatrix: never
+        densified), or an AMatrix-like wrap;
     nsv : number of singular values, or negative to stop by `tol`;
     tol, norm : with nsv < 0, stop when the `norm` ('s', 'f' or 'm') of A - u diag(sigma) vt is at most
         tol times that of A (tol > 0) or -tol (tol < 0);
@@ -145,6 +149,8 @@ def truncated_svd(A, opt=None, nsv=-1, tol=0, norm='s', msv=-1, vtol=0, arch='hi
         opt = Options()
     if hasattr(A, 'as_operator'):
         matrix = A
+    elif scipy.sparse.issparse(A):
+        matrix = SparseAMatrix(A, arch=arch)
     else:
         if not isinstance(A, numpy.ndarray) or A.ndim != 2:
             raise ValueError('a 2D array is needed')

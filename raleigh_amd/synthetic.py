@@ -9,7 +9,10 @@ container generate bit-identical matrices and committed reference eigenvalues st
 * ``fe_surrogate``     the stand-in for SuiteSparse shipsec5 (config 3: n = 179 860, ~56 nnz/row;
                        the .mtx is not available offline, README.md:20 of the reference only names it);
 * ``read_matrix_market``  coordinate-format Matrix-Market reader, so that a supplied shipsec5.mtx
-                       drops into the same tests.
+                       drops into the same tests (SURVEY 8(f).4);
+* ``sparse_data``      rectangular sparse data matrices (uniform or power-law rows and columns) for the
+                       truncated SVD / PCA of sparse data (seeded numpy generator);
+* ``block_diagonal_data``  a permuted block-diagonal sparse matrix whose singular values are known exactly.
 """
 
 import gzip
@@ -211,3 +214,87 @@ def read_matrix_market(path):
     a = sp.csr_matrix((v, (i, j)), shape=(nr, nc))      # duplicate entries are summed, as the format specifies
     a.sort_indices()
     return a
+
+
+def _random_values(rng, count, dtype):
+    v = rng.standard_normal(count)
+    if np.dtype(dtype).kind == 'c':
+        v = v + 1j * rng.standard_normal(count)
+    return v.astype(dtype)
+
+
+def _zipf_weights(count, exponent):
+    return 1.0 / np.arange(1, count + 1, dtype=np.float64) ** exponent
+
+
+def sparse_data(m, n, nnz_per_row, kind='uniform', dtype=np.float32, seed=0):
+    """An m x n sparse data matrix (canonical CSR, standard normal values, complex parts for a complex dtype) with
+    about nnz_per_row stored entries per row, a pure function of the arguments (numpy's PCG64 from `seed`).
+
+    kind 'uniform': every row holds nnz_per_row distinct columns drawn uniformly.
+    kind 'powerlaw': the row lengths follow a Zipf law (the k-th longest row ~ 1/k, the longest capped at n,
+    rows in random order) and so does the popularity of the columns (the k-th most popular column drawn with a
+    weight ~ 1/k, columns in random order): A has rows of up to n entries and A^H -- whose rows are the popular
+    columns -- rows of up to m.  Repeated draws of a column within a row are kept once, so a power-law
+    matrix stores somewhat fewer than m * nnz_per_row entries."""
+    if kind not in ('uniform', 'powerlaw'):
+        raise ValueError('kind must be uniform or powerlaw')
+    rng = np.random.default_rng(seed)
+    k = min(int(nnz_per_row), n)
+    if kind == 'uniform':
+        lengths = np.full(m, k, dtype=np.int64)
+        cols = rng.integers(0, n, size=m * k, dtype=np.int64)
+    else:
+        w = _zipf_weights(m, 1.0)
+        scale = m * k / w.sum()
+        for _ in range(8):              # rescale so that the capped lengths keep the mean
+            lengths = np.minimum(np.maximum(np.rint(scale * w), 1), n).astype(np.int64)
+            scale *= m * k / max(lengths.sum(), 1)
+        lengths = lengths[rng.permutation(m)]
+        cdf = np.cumsum(_zipf_weights(n, 1.0))
+        cdf /= cdf[-1]
+        colperm = rng.permutation(n)
+        cols = colperm[np.minimum(np.searchsorted(cdf, rng.random(int(lengths.sum())), side='right'), n - 1)]
+    rows = np.repeat(np.arange(m, dtype=np.int64), lengths)
+    key = np.unique(rows * n + cols)                    # sorted by row, then column; repeats dropped
+    rows, cols = key // n, key % n
+    indptr = np.zeros(m + 1, dtype=np.int64)
+    np.cumsum(np.bincount(rows, minlength=m), out=indptr[1:])
+    vals = _random_values(rng, key.size, dtype)
+    return sp.csr_matrix((vals, cols.astype(np.int32), indptr), shape=(m, n))
+
+
+def block_diagonal_data(blocks, dtype=np.float64, seed=0, decay=0.5):
+    """A sparse matrix with a known spectrum at any size: a block-diagonal matrix of small dense random blocks
+    with rows and columns randomly permuted.  blocks: a list of (rows, cols, count) -- `count` standard normal
+    blocks of that shape; block number b (in the order of the list) is scaled by (1 + b)^-decay, so the
+    leading singular values are well apart.  Blocks of very unequal sides (2 x 20000, 20000 x 2) make long rows
+    and long columns.  Returns (csr, sigma): sigma = all singular values in descending order -- the union of
+    the blocks' own, from batched numpy.linalg.svd -- and the csr matrix in canonical form."""
+    rng = np.random.default_rng(seed)
+    M = sum(b[0] * b[2] for b in blocks)
+    N = sum(b[1] * b[2] for b in blocks)
+    rows_l, cols_l, vals_l, sig_l = [], [], [], []
+    r0 = c0 = 0
+    b0 = 0
+    for (r, c, count) in blocks:
+        a = rng.standard_normal((count, r, c))
+        if np.dtype(dtype).kind == 'c':
+            a = a + 1j * rng.standard_normal((count, r, c))
+        a *= ((1.0 + np.arange(b0, b0 + count)) ** -decay)[:, None, None]
+        a = a.astype(dtype)
+        sig_l.append(np.linalg.svd(a.astype(np.complex128 if a.dtype.kind == 'c' else np.float64),
+                                   compute_uv=False).ravel())
+        ri = r0 + np.arange(count)[:, None, None] * r + np.arange(r)[None, :, None]
+        ci = c0 + np.arange(count)[:, None, None] * c + np.arange(c)[None, None, :]
+        rows_l.append(np.broadcast_to(ri, a.shape).ravel())
+        cols_l.append(np.broadcast_to(ci, a.shape).ravel())
+        vals_l.append(a.ravel())
+        r0 += r * count
+        c0 += c * count
+        b0 += count
+    prow, pcol = rng.permutation(M), rng.permutation(N)
+    A = sp.csr_matrix((np.concatenate(vals_l), (prow[np.concatenate(rows_l)], pcol[np.concatenate(cols_l)])),
+                      shape=(M, N))
+    A.sum_duplicates()
+    return A, np.sort(np.concatenate(sig_l))[::-1]
