@@ -390,6 +390,40 @@ int rlh_spd_stats(rlh_spd_t h, int64_t *workspace_bytes, double *transpose_secon
 int rlh_spd_apply(rlh_spd_t h, int transp, int64_t m, const void *X, int64_t ldx, void *Y, int64_t ldy,
                   const void *d_u, const void *d_c);
 
+/* ---- dense 8-bit data matrix: the operator of PCA and truncated SVD on uint8 / int8 data (images)
+ *      (the reference's dense path takes the data as float32 and runs one gemm per application,
+ *      raleigh/algebra/dense_cublas.py:732-776; here the data stay bytes and the products run on the bfloat16
+ *      matrix cores with float32 vectors: every 8-bit integer is exactly a bfloat16, every float32 is exactly the
+ *      sum of three bfloat16 numbers and their products are exact in float32, so the only error is that of
+ *      the float32 accumulation)
+ * rlh_bytes_create: A is M x N, row-major in HOST memory, `kind` RLH_BYTES_U8 or RLH_BYTES_I8, `row_stride` bytes
+ * from one row to the next (>= N).  The handle holds ONE device copy of A as bytes (rows padded with zeros to a
+ * multiple of 16 bytes; nothing is widened on the host or the device) and the split-K workspace.  Needs rlh_init. */
+#define RLH_BYTES_U8 0
+#define RLH_BYTES_I8 1
+typedef struct rlh_bytes *rlh_bytes_t;
+/* stands for the upload of the data (Matrix.__init__, dense_cublas.py:635-700) */
+int rlh_bytes_create(rlh_bytes_t *h, int kind, int64_t n_rows, int64_t n_cols, const void *h_data,
+                     int64_t row_stride);
+int rlh_bytes_destroy(rlh_bytes_t h);
+/* sizes, device bytes held (data and workspace) and the workspace bytes alone (the split-K partial tiles; it
+ * grows when a product needs more than before: that call synchronises the stream once) */
+int rlh_bytes_info(rlh_bytes_t h, int64_t *n_rows, int64_t *n_cols, int64_t *device_bytes,
+                   int64_t *workspace_bytes);
+/* Matrix.apply (dense_cublas.py:732-776): Y[:, j] = Op(A) X[:, j] - c[j] u, Op(A) = A (transp 0: X has N rows,
+ * Y M rows) or A^T (transp 1: X has M rows, Y N rows); X, Y column-major float32 DEVICE blocks of m vectors with
+ * any leading dimensions >= their rows; u, c DEVICE arrays with the meaning of rlh_dense_apply_r1 (u NULL: a
+ * vector of ones; u and c NULL: the plain product).  Asynchronous on the library stream; no atomics: results
+ * are bit-identical from call to call and between handles of the same data. */
+int rlh_bytes_apply(rlh_bytes_t h, int transp, int64_t m, const void *X, int64_t ldx, void *Y, int64_t ldy,
+                    const void *d_u, const void *d_c);
+/* Matrix.dots (dense_cublas.py:715-718): the sums of squares of the M rows, accumulated in 64-bit integers
+ * (exact), as M HOST doubles; the call synchronises. */
+int rlh_bytes_row_sumsq(rlh_bytes_t h, double *h_out);
+/* AMatrix.scale() (raleigh/algebra/dense_matrix.py:44-49): the largest modulus of the entries (exact), a HOST
+ * double; the call synchronises. */
+int rlh_bytes_absmax(rlh_bytes_t h, double *h_out);
+
 /* ---- profiling aid: HIP-event time of the last `count` kernels ---- */
 int rlh_timer_start(void);
 int rlh_timer_stop(float *milliseconds);

@@ -106,6 +106,12 @@ SIGNATURES = {
     'rlh_spd_info': [_p, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
     'rlh_spd_stats': [_p, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)],
     'rlh_spd_apply': [_p, _int, _i64, _p, _i64, _p, _i64, _p, _p],
+    'rlh_bytes_create': [ctypes.POINTER(_p), _int, _i64, _i64, _p, _i64],
+    'rlh_bytes_destroy': [_p],
+    'rlh_bytes_info': [_p, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
+    'rlh_bytes_apply': [_p, _int, _i64, _p, _i64, _p, _i64, _p, _p],
+    'rlh_bytes_row_sumsq': [_p, _p],
+    'rlh_bytes_absmax': [_p, ctypes.POINTER(ctypes.c_double)],
     'rlh_timer_start': [],
     'rlh_timer_stop': [ctypes.POINTER(ctypes.c_float)],
 }

@@ -32,6 +32,7 @@ import scipy.sparse
 
 from ..algebra.dense_matrix import AMatrix
 from ..algebra.sparse_matrix import SparseAMatrix
+from ..algebra.byte_matrix import ByteAMatrix
 from ..core.solver import Options
 from .pca import PartialSVD, _SingularValueCriteria, _FrobeniusStopping, _project_out
 
@@ -71,6 +72,8 @@ def _as_matrix(A, arch):
         return SparseAMatrix(A, arch=arch)
     if not isinstance(A, numpy.ndarray) or not A.flags['C_CONTIGUOUS']:
         raise ValueError('matrix must be C_CONTIGUOUS')
+    if A.dtype.type in (numpy.uint8, numpy.int8):       # 8-bit data stay bytes; vectors and results are float32
+        return ByteAMatrix(A, arch=arch)
     return AMatrix(A, arch=arch)
 
 
@@ -323,8 +326,8 @@ class LowerRankApproximation:
     # ------------------------------------------------------------------ incremental
     def icompute(self, matrix, batch_size, opt=None, rank=-1, tol=0, norm='f', max_rank=-1, svtol=1e-3,
                  shift=False, arch='hip', verb=0):
-        """compute() on the first `batch_size` rows of the host array `matrix` (an ndarray or a scipy.sparse matrix,
-        cut into CSR row slices), update() with every further batch (lra.py:381-425): one batch of the data in
+        """compute() on the first `batch_size` rows of the host array `matrix` (an ndarray -- of uint8 / int8 too: row
+        slices of the host bytes -- or a scipy.sparse matrix, cut into CSR row slices), update() with every further batch (lra.py:381-425): one batch of the data in
         HBM at a time."""
         if scipy.sparse.issparse(matrix):
             from ..algebra.hip.sparse_data import canonical_csr

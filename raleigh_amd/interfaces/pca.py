@@ -282,7 +282,9 @@ class PartialSVD:
 
 def pca(A, npc=-1, tol=0, have=None, batch_size=None, verb=0, arch='hip', norm='f', mpc=-1, svtol=1e-3, opt=None):
     '''PCA of the rows of A (a C-contiguous ndarray or a scipy.sparse matrix / array: the mean shift is then
-    applied implicitly, A - e mean is never formed): returns (mean (1, n), trans (m, k), comps (k, n)) with
+    applied implicitly, A - e mean is never formed; an ndarray of uint8 / int8 stays bytes on the host and in
+    HBM and the results are float32 -- `have` from a float32 run may be continued with 8-bit rows and the other
+    way round; other integer types, bool, float16 and arrays that are not C-contiguous raise ValueError): returns (mean (1, n), trans (m, k), comps (k, n)) with
     trans @ comps ~ A - e mean, comps rows orthonormal, columns of trans in descending
     order of norm (raleigh/interfaces/pca.py:16-164).
 

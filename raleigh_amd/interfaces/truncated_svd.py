@@ -19,6 +19,7 @@ import scipy.sparse
 
 from ..algebra.dense_matrix import AMatrix
 from ..algebra.sparse_matrix import SparseAMatrix
+from ..algebra.byte_matrix import ByteAMatrix
 from ..core.solver import Options
 from .pca import PartialSVD
 
@@ -136,8 +137,10 @@ def truncated_svd(A, opt=None, nsv=-1, tol=0, norm='s', msv=-1, vtol=0, arch='hi
     '''Returns u (m, k), sigma (k,) in descending order and vt (k, n) with A vt^H = u diag(sigma), u and
     vt^H orthonormal (raleigh/interfaces/truncated_svd.py:24-127).
 
-    A : a 2D ndarray, a scipy.sparse matrix or array (the device operator of SparseAMatrix: never
-        densified), or an AMatrix-like wrap;
+    A : a 2D ndarray of float32 / float64 / complex64 / complex128, or of uint8 / int8 (kept as bytes in HBM,
+        the products on the bfloat16 matrix cores with float32 accumulation: u, sigma, vt come back as
+        float32; every other integer type, bool and float16 raise ValueError), a scipy.sparse matrix or array
+        (the device operator of SparseAMatrix: never densified), or an AMatrix-like wrap;
     nsv : number of singular values, or negative to stop by `tol`;
     tol, norm : with nsv < 0, stop when the `norm` ('s', 'f' or 'm') of A - u diag(sigma) vt is at most
         tol times that of A (tol > 0) or -tol (tol < 0);
@@ -154,7 +157,10 @@ def truncated_svd(A, opt=None, nsv=-1, tol=0, norm='s', msv=-1, vtol=0, arch='hi
     else:
         if not isinstance(A, numpy.ndarray) or A.ndim != 2:
             raise ValueError('a 2D array is needed')
-        matrix = AMatrix(numpy.ascontiguousarray(A), arch=arch)
+        if A.dtype.type in (numpy.uint8, numpy.int8):       # 8-bit data stay bytes; u, sigma, vt are float32
+            matrix = ByteAMatrix(numpy.ascontiguousarray(A), arch=arch)
+        else:
+            matrix = AMatrix(numpy.ascontiguousarray(A), arch=arch)
     psvd = PartialSVD(matrix)
     user_bs, user_cc, user_sc = opt.block_size, opt.convergence_criteria, opt.stopping_criteria
     if user_bs < 1 and (nsv < 0 or nsv > 100):

@@ -298,3 +298,62 @@ def block_diagonal_data(blocks, dtype=np.float64, seed=0, decay=0.5):
                       shape=(M, N))
     A.sum_duplicates()
     return A, np.sort(np.concatenate(sig_l))[::-1]
+
+
+def byte_images(m, n, rank, seed=0, signed=False):
+    """An m x n matrix of 8-bit "pictures", one per row (numpy.uint8, or numpy.int8 with signed=True): `rank`
+    random patterns mixed with standard normal coefficients of weights 1, 1/2, ..., 1/rank (every pixel
+    with 30 grey levels of standard deviation) around the middle of the range, plus noise of 4 grey levels, rounded and clipped
+    to the 8-bit range (4.2 standard deviations away: a few entries in 10^5 sit on the bounds).  A pure function
+    of the arguments (numpy's PCG64 from `seed`); generated in row chunks, so that a large matrix needs no
+    floating-point copy of the whole."""
+    rng = np.random.default_rng(seed)
+    dtype = np.int8 if signed else np.uint8
+    lo, hi, mid = (-128, 127, 0.0) if signed else (0, 255, 128.0)
+    w = 1.0 / np.arange(1, rank + 1, dtype=np.float64)
+    patterns = rng.standard_normal((rank, n))
+    patterns *= 30.0 / np.sqrt(np.sum((w * w)[:, None] * patterns * patterns, axis=0))      # every pixel: 30 levels
+    out = np.empty((m, n), dtype=dtype)
+    chunk = max(1, (1 << 22) // max(n, 1))
+    for r0 in range(0, m, chunk):
+        r1 = min(m, r0 + chunk)
+        c = rng.standard_normal((r1 - r0, rank)) * w
+        block = c @ patterns
+        block += 4.0 * rng.standard_normal((r1 - r0, n))
+        block += mid
+        np.rint(block, out=block)
+        np.clip(block, lo, hi, out=block)
+        out[r0:r1] = block.astype(dtype)
+    return out
+
+
+def byte_blocks(blocks, shape=None, seed=0, signed=False):
+    """A dense 8-bit matrix with a spectrum known exactly at any size, the counterpart of block_diagonal_data: a
+    block-diagonal matrix of CONSTANT integer blocks with rows and columns randomly permuted, zero elsewhere.
+    blocks: a list of (p, q, v) -- a block of p x q entries of value v (0 < v <= 255, or 0 < |v| <= 128 within
+    the int8 range with signed=True); shape: (M, N), at least the sums of the p and of the q (default: exactly
+    those).  A constant p x q block has the one nonzero singular value |v| sqrt(p q); the blocks must make
+    these distinct (ValueError otherwise).  Returns (array, sigma): a C-contiguous numpy.uint8 / int8 array
+    and its nonzero singular values in descending order (float64)."""
+    rng = np.random.default_rng(seed)
+    dtype = np.int8 if signed else np.uint8
+    lo, hi = (-128, 127) if signed else (1, 255)
+    P, Q = sum(b[0] for b in blocks), sum(b[1] for b in blocks)
+    M, N = (P, Q) if shape is None else shape
+    if M < P or N < Q:
+        raise ValueError('shape %s cannot hold blocks of %d rows and %d columns in all' % (repr(shape), P, Q))
+    sigma = np.array([abs(int(v)) * np.sqrt(float(p) * float(q)) for (p, q, v) in blocks])
+    if any(p < 1 or q < 1 or int(v) != v or v == 0 or v < lo or v > hi for (p, q, v) in blocks):
+        raise ValueError('blocks need positive sides and nonzero integer values of the 8-bit range')
+    sigma = np.sort(sigma)[::-1]
+    if sigma.size > 1 and np.min(-np.diff(sigma)) <= 1e-9 * sigma[0]:
+        raise ValueError('the blocks must have distinct singular values |v| sqrt(p q)')
+    A = np.zeros((M, N), dtype=dtype)
+    prow, pcol = rng.permutation(M), rng.permutation(N)
+    r0 = c0 = 0
+    for (p, q, v) in blocks:
+        rows = np.sort(prow[r0:r0 + p])
+        A[np.ix_(rows, pcol[c0:c0 + q])] = v
+        r0 += p
+        c0 += q
+    return A, sigma
