@@ -94,7 +94,13 @@ int rlh_gram_multi(int dtype, int64_t n, int nx, const void *const *X, const int
                    const int64_t *my, void *d_out, void *h_out);
 
 /* ---- K2: column-wise dots (dense_numpy.py:68-76; dense_cublas.py:233-243)
- * out[i] = sum_r conj(Y[r,i]) * X[r,i], i < m. */
+ * out[i] = sum_r conj(Y[r,i]) * X[r,i], i < m.  Any m >= 0 in one call: the library walks the
+ * block in column panels that one launch can index, so the rows of a tall data matrix viewed as
+ * vectors (AMatrix.dots / frobenius2: m = number of rows) need nothing from the caller.  The
+ * other column-wise entry points (rlh_axpy, rlh_axpy_cols, rlh_lincomb_cols, rlh_scale_cols,
+ * rlh_copy, rlh_copy_cols, rlh_conj, rlh_convert, rlh_fill_random, rlh_bf16_pack / unpack,
+ * rlh_gather_rows*) do the same; only rlh_gram / rlh_gram_multi, whose result is m x m, keep
+ * a limit of 32768 vectors per window. */
 int rlh_dots(int dtype, int64_t n, int64_t m, const void *X, int64_t ldx,
              const void *Y, int64_t ldy, void *d_out, void *h_out);
 
@@ -104,7 +110,7 @@ int rlh_dots_transp(int dtype, int64_t n, int64_t m, const void *X, int64_t ldx,
                     const void *Y, int64_t ldy, void *d_out);
 /* Largest modulus of the real / imaginary parts of the entries of a block (AMatrix.scale():
  * the reference scans the host array, raleigh/algebra/dense_matrix.py:44-49); *h_out is a host
- * double; the call synchronises. */
+ * double; the call synchronises.  Any m >= 0 in one call (column panels, as rlh_dots). */
 int rlh_absmax(int dtype, int64_t n, int64_t m, const void *X, int64_t ldx, double *h_out);
 
 /* ---- K3/K4: block update (dense_numpy.py:84-105; dense_cublas.py:271-342)

@@ -77,6 +77,18 @@ class Matrix:
         upload(self.data_ptr(), self._lda * self._es, np.ascontiguousarray(host, dtype=self._dtype))
 
     def dots(self):
+        """Squared norms of the rows."""
+        if self._order != 'C_CONTIGUOUS':
+            # the device holds the columns: row i collects element i of every stored column
+            rows, cols = self._shape
+            w = np.zeros((rows,), dtype=self._dtype)
+            if rows > 0:
+                L = _lib.lib()
+                tmp = DeviceBuffer(rows * self._es, zero=False)
+                _lib.check(L.rlh_dots_transp(self._code, rows, cols, self.data_ptr(), self._lda,
+                                             self.data_ptr(), self._lda, tmp.ptr))
+                _lib.check(L.rlh_d2h(_lib.host_ptr(w), tmp.ptr, rows * self._es))
+            return w
         v = Vectors(self, shallow=True)
         return v.dots(v)
 

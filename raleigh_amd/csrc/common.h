@@ -153,6 +153,22 @@ int ensure_result(size_t bytes);          // result_d / result_h >= bytes
 // copy device result to user host memory through the pinned buffer + sync
 int fetch_result(void *h_out, const void *d_src, size_t bytes);
 
+// The column-wise kernels carry the column in blockIdx.y, which a launch limits to 65535.  Their entry points walk a
+// block of any number of columns in panels of kColPanel: f(j0, mp) handles columns [j0, j0 + mp).  A panel of 32768
+// columns also keeps the per-column coefficients of one launch (two complex128 per column for rlh_lincomb_cols)
+// within one staging slot.
+constexpr int64_t kColPanel = 32768;
+template <typename F> static inline int for_col_panels(int64_t m, F f) {
+  for (int64_t j0 = 0; j0 < m; j0 += kColPanel) {
+    const int64_t mp = (m - j0) < kColPanel ? (m - j0) : kColPanel;
+    if (int rc = f(j0, mp)) return rc;
+  }
+  return 0;
+}
+// p advanced by `elems` elements of `es` bytes
+static inline const void *at(const void *p, int64_t elems, int64_t es) { return (const char *)p + elems * es; }
+static inline void *at(void *p, int64_t elems, int64_t es) { return (char *)p + elems * es; }
+
 static inline bool aligned16(const void *p, int64_t ld, int64_t es) {
   return ((reinterpret_cast<uintptr_t>(p) & 15u) == 0) && (((ld * es) & 15) == 0);
 }

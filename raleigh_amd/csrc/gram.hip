@@ -1368,9 +1368,14 @@ static int absmax_impl(int64_t n, int64_t m, const void *X, int64_t ldx, void *d
   if (nbx > cap) nbx = cap;
   if (nbx < 1) nbx = 1;
   RLH_REQUIRE((size_t)nbx * m * sizeof(double) <= kWorkspaceBytes, "rlh_absmax: too many columns");
-  hipLaunchKernelGGL((absmax_kernel<R>), dim3((unsigned)nbx, (unsigned)m), dim3(256), 0, c.stream, (const R *)X,
-                     ldx * NC, n * NC, (double *)c.work, (int)nbx);
-  RLH_HIP(hipGetLastError());
+  // the panels' partials side by side, one finalize over all of them
+  if (int rc = for_col_panels(m, [&](int64_t j0, int64_t mp) {
+        hipLaunchKernelGGL((absmax_kernel<R>), dim3((unsigned)nbx, (unsigned)mp), dim3(256), 0, c.stream,
+                           (const R *)X + j0 * ldx * NC, ldx * NC, n * NC, (double *)c.work + j0 * nbx, (int)nbx);
+        RLH_HIP(hipGetLastError());
+        return 0;
+      }))
+    return rc;
   hipLaunchKernelGGL(absmax_finalize, dim3(1), dim3(256), 0, c.stream, (const double *)c.work, nbx * m, (double *)d_out);
   RLH_HIP(hipGetLastError());
   return 0;
@@ -1480,7 +1485,6 @@ int rlh_dots(int dtype, int64_t n, int64_t m, const void *X, int64_t ldx, const 
   if (int rc = require_ready()) return rc;
   RLH_REQUIRE(dtype_valid(dtype), "rlh_dots: unknown dtype %d", dtype);
   RLH_REQUIRE(n >= 0 && m >= 0, "rlh_dots: negative size");
-  RLH_REQUIRE(m <= 32768, "rlh_dots: more than 32768 vectors in a window");
   if (m == 0) return 0;
   RLH_REQUIRE(X && Y, "rlh_dots: null block pointer");
   RLH_REQUIRE(ldx >= n && ldy >= n, "rlh_dots: leading dimension smaller than n");
@@ -1494,7 +1498,13 @@ int rlh_dots(int dtype, int64_t n, int64_t m, const void *X, int64_t ldx, const 
   if (n == 0) {
     RLH_HIP(hipMemsetAsync(d_out, 0, bytes, ctx().stream));
   } else {
-    RLH_DISPATCH(dtype, dots_impl, n, m, X, ldx, Y, ldy, d_out)
+    // (every panel reduces through the same partials workspace: the launches are ordered on the stream)
+    const int64_t es = dtype_size(dtype);
+    rc = for_col_panels(m, [&](int64_t j0, int64_t mp) {
+      int rc = 0;
+      RLH_DISPATCH(dtype, dots_impl, n, mp, at(X, j0 * ldx, es), ldx, at(Y, j0 * ldy, es), ldy, at(d_out, j0, es))
+      return rc;
+    });
   }
   if (rc) return rc;
   if (h_out) return fetch_result(h_out, d_out, bytes);
@@ -1504,7 +1514,7 @@ int rlh_dots(int dtype, int64_t n, int64_t m, const void *X, int64_t ldx, const 
 int rlh_absmax(int dtype, int64_t n, int64_t m, const void *X, int64_t ldx, double *h_out) {
   if (int rc = require_ready()) return rc;
   RLH_REQUIRE(dtype_valid(dtype), "rlh_absmax: unknown dtype %d", dtype);
-  RLH_REQUIRE(n >= 0 && m >= 0 && m <= 65535, "rlh_absmax: bad size");
+  RLH_REQUIRE(n >= 0 && m >= 0, "rlh_absmax: bad size");
   RLH_REQUIRE(h_out != nullptr, "rlh_absmax: null output");
   if (n == 0 || m == 0) { *h_out = 0.0; return 0; }
   RLH_REQUIRE(X && ldx >= n, "rlh_absmax: bad block");

@@ -1554,10 +1554,12 @@ static int gather_rows_impl(int64_t nidx, const int64_t *d_idx, int64_t m, const
   const int64_t cap = ((int64_t)c.num_cu * 8 + m - 1) / m;
   if (nb > cap) nb = cap;
   if (nb < 1) nb = 1;
-  hipLaunchKernelGGL((gather_rows_kernel<T>), dim3((unsigned)nb, (unsigned)m), dim3(256), 0, c.stream, d_idx, nidx,
-                     (const T *)X, ldx, (T *)Out, ldo);
-  RLH_HIP(hipGetLastError());
-  return 0;
+  return for_col_panels(m, [&](int64_t j0, int64_t mp) {
+    hipLaunchKernelGGL((gather_rows_kernel<T>), dim3((unsigned)nb, (unsigned)mp), dim3(256), 0, c.stream, d_idx, nidx,
+                       (const T *)X + j0 * ldx, ldx, (T *)Out + j0 * ldo, ldo);
+    RLH_HIP(hipGetLastError());
+    return 0;
+  });
 }
 
 template <int DT>
@@ -2594,10 +2596,12 @@ int rlh_gather_rows_bf16(int64_t nidx, const int64_t *d_idx, int64_t m, const vo
   const int64_t cap = ((int64_t)c.num_cu * 8 + m - 1) / m;
   if (nb > cap) nb = cap;
   if (nb < 1) nb = 1;
-  hipLaunchKernelGGL((gather_rows_kernel<unsigned short>), dim3((unsigned)nb, (unsigned)m), dim3(256), 0, c.stream,
-                     d_idx, nidx, (const unsigned short *)X16, ldx, (unsigned short *)Out16, ldo);
-  RLH_HIP(hipGetLastError());
-  return 0;
+  return for_col_panels(m, [&](int64_t j0, int64_t mp) {
+    hipLaunchKernelGGL((gather_rows_kernel<unsigned short>), dim3((unsigned)nb, (unsigned)mp), dim3(256), 0, c.stream,
+                       d_idx, nidx, (const unsigned short *)X16 + j0 * ldx, ldx, (unsigned short *)Out16 + j0 * ldo, ldo);
+    RLH_HIP(hipGetLastError());
+    return 0;
+  });
 }
 
 int rlh_gather_rows(int dtype, int64_t nidx, const int64_t *d_idx, int64_t m, const void *X, int64_t ldx, void *Out,

@@ -1171,9 +1171,13 @@ int rlh_lincomb_cols(int dtype, int64_t n, int64_t m, const void *a, const void 
   if (n == 0 || m == 0) return 0;
   RLH_REQUIRE(a && b && A && B && Out, "rlh_lincomb_cols: null pointer");
   RLH_REQUIRE(lda >= n && ldb >= n && ldo >= n, "rlh_lincomb_cols: leading dimension smaller than n");
-  int rc = 0;
-  RLH_DISPATCH(dtype, lincomb_cols_impl, n, m, a, A, lda, b, B, ldb, Out, ldo)
-  return rc;
+  const int64_t es = dtype_size(dtype);
+  return for_col_panels(m, [&](int64_t j0, int64_t mp) {
+    int rc = 0;
+    RLH_DISPATCH(dtype, lincomb_cols_impl, n, mp, at(a, j0, es), at(A, j0 * lda, es), lda, at(b, j0, es),
+                 at(B, j0 * ldb, es), ldb, at(Out, j0 * ldo, es), ldo)
+    return rc;
+  });
 }
 
 int rlh_axpy(int dtype, int64_t n, int64_t m, const double *alpha, const void *X, int64_t ldx, void *Y, int64_t ldy) {
@@ -1185,9 +1189,12 @@ int rlh_axpy(int dtype, int64_t n, int64_t m, const double *alpha, const void *X
   RLH_REQUIRE(ldx >= n && ldy >= n, "rlh_axpy: leading dimension smaller than n");
   float sf[2] = {(float)alpha[0], (float)alpha[1]};
   const void *s = (dtype == RLH_S || dtype == RLH_C) ? (const void *)sf : (const void *)alpha;
-  int rc = 0;
-  RLH_DISPATCH(dtype, axpy_cols_impl, n, m, s, true, X, ldx, Y, ldy)
-  return rc;
+  const int64_t es = dtype_size(dtype);
+  return for_col_panels(m, [&](int64_t j0, int64_t mp) {
+    int rc = 0;
+    RLH_DISPATCH(dtype, axpy_cols_impl, n, mp, s, true, at(X, j0 * ldx, es), ldx, at(Y, j0 * ldy, es), ldy)
+    return rc;
+  });
 }
 
 int rlh_axpy_cols(int dtype, int64_t n, int64_t m, const void *s, const void *X, int64_t ldx, void *Y, int64_t ldy) {
@@ -1197,9 +1204,12 @@ int rlh_axpy_cols(int dtype, int64_t n, int64_t m, const void *s, const void *X,
   if (n == 0 || m == 0) return 0;
   RLH_REQUIRE(s && X && Y, "rlh_axpy_cols: null pointer");
   RLH_REQUIRE(ldx >= n && ldy >= n, "rlh_axpy_cols: leading dimension smaller than n");
-  int rc = 0;
-  RLH_DISPATCH(dtype, axpy_cols_impl, n, m, s, false, X, ldx, Y, ldy)
-  return rc;
+  const int64_t es = dtype_size(dtype);
+  return for_col_panels(m, [&](int64_t j0, int64_t mp) {
+    int rc = 0;
+    RLH_DISPATCH(dtype, axpy_cols_impl, n, mp, at(s, j0, es), false, at(X, j0 * ldx, es), ldx, at(Y, j0 * ldy, es), ldy)
+    return rc;
+  });
 }
 
 int rlh_copy(int dtype, int64_t n, int64_t m, const void *X, int64_t ldx, void *Y, int64_t ldy) {
@@ -1209,7 +1219,10 @@ int rlh_copy(int dtype, int64_t n, int64_t m, const void *X, int64_t ldx, void *
   if (n == 0 || m == 0 || (X == Y && ldx == ldy)) return 0;
   RLH_REQUIRE(X && Y, "rlh_copy: null pointer");
   RLH_REQUIRE(ldx >= n && ldy >= n, "rlh_copy: leading dimension smaller than n");
-  return copy_cols_impl(dtype, n, m, nullptr, X, ldx, Y, ldy);
+  const int64_t es = dtype_size(dtype);
+  return for_col_panels(m, [&](int64_t j0, int64_t mp) {
+    return copy_cols_impl(dtype, n, mp, nullptr, at(X, j0 * ldx, es), ldx, at(Y, j0 * ldy, es), ldy);
+  });
 }
 
 int rlh_copy_cols(int dtype, int64_t n, int64_t m, const int64_t *ind, const void *Xall, int64_t ldx, void *Y,
@@ -1221,7 +1234,10 @@ int rlh_copy_cols(int dtype, int64_t n, int64_t m, const int64_t *ind, const voi
   RLH_REQUIRE(ind && Xall && Y, "rlh_copy_cols: null pointer");
   RLH_REQUIRE(ldx >= n && ldy >= n, "rlh_copy_cols: leading dimension smaller than n");
   for (int64_t i = 0; i < m; ++i) RLH_REQUIRE(ind[i] >= 0, "rlh_copy_cols: negative index");
-  return copy_cols_impl(dtype, n, m, ind, Xall, ldx, Y, ldy);
+  const int64_t es = dtype_size(dtype);
+  return for_col_panels(m, [&](int64_t j0, int64_t mp) {
+    return copy_cols_impl(dtype, n, mp, ind + j0, Xall, ldx, at(Y, j0 * ldy, es), ldy);
+  });
 }
 
 int rlh_scale_cols(int dtype, int64_t n, int64_t m, const double *s, int mode, void *X, int64_t ldx) {
@@ -1232,9 +1248,13 @@ int rlh_scale_cols(int dtype, int64_t n, int64_t m, const double *s, int mode, v
   if (n == 0 || m == 0) return 0;
   RLH_REQUIRE(s && X, "rlh_scale_cols: null pointer");
   RLH_REQUIRE(ldx >= n, "rlh_scale_cols: leading dimension smaller than n");
-  int rc = 0;
-  RLH_DISPATCH(dtype, scale_cols_impl, n, m, s, mode, X, ldx)
-  return rc;
+  const int64_t es = dtype_size(dtype);
+  const int64_t sc = (dtype == RLH_C || dtype == RLH_Z) ? 2 : 1;       // doubles per coefficient
+  return for_col_panels(m, [&](int64_t j0, int64_t mp) {
+    int rc = 0;
+    RLH_DISPATCH(dtype, scale_cols_impl, n, mp, s + j0 * sc, mode, at(X, j0 * ldx, es), ldx)
+    return rc;
+  });
 }
 
 int rlh_convert(int src_dtype, int dst_dtype, int64_t n, int64_t m, const void *X, int64_t ldx, void *Y, int64_t ldy) {
@@ -1249,15 +1269,17 @@ int rlh_convert(int src_dtype, int dst_dtype, int64_t n, int64_t m, const void *
   // complex blocks are converted as real blocks of twice the length
   const int64_t f = cs ? 2 : 1;
   const bool src_single = (src_dtype == RLH_S || src_dtype == RLH_C);
-  dim3 grid(row_blocks(n * f, m), (unsigned)m);
-  if (src_single)
-    hipLaunchKernelGGL((convert_kernel<float, double>), grid, dim3(256), 0, ctx().stream, (const float *)X, ldx * f,
-                       (double *)Y, ldy * f, n * f);
-  else
-    hipLaunchKernelGGL((convert_kernel<double, float>), grid, dim3(256), 0, ctx().stream, (const double *)X, ldx * f,
-                       (float *)Y, ldy * f, n * f);
-  RLH_HIP(hipGetLastError());
-  return 0;
+  return for_col_panels(m, [&](int64_t j0, int64_t mp) {
+    dim3 grid(row_blocks(n * f, mp), (unsigned)mp);
+    if (src_single)
+      hipLaunchKernelGGL((convert_kernel<float, double>), grid, dim3(256), 0, ctx().stream,
+                         (const float *)X + j0 * ldx * f, ldx * f, (double *)Y + j0 * ldy * f, ldy * f, n * f);
+    else
+      hipLaunchKernelGGL((convert_kernel<double, float>), grid, dim3(256), 0, ctx().stream,
+                         (const double *)X + j0 * ldx * f, ldx * f, (float *)Y + j0 * ldy * f, ldy * f, n * f);
+    RLH_HIP(hipGetLastError());
+    return 0;
+  });
 }
 
 int rlh_fill_random(int dtype, int64_t n, int64_t m, void *X, int64_t ldx, uint64_t seed, int64_t row0, int64_t col0) {
@@ -1266,16 +1288,19 @@ int rlh_fill_random(int dtype, int64_t n, int64_t m, void *X, int64_t ldx, uint6
   RLH_REQUIRE(n >= 0 && m >= 0 && row0 >= 0 && col0 >= 0, "rlh_fill_random: negative size or offset");
   if (n == 0 || m == 0) return 0;
   RLH_REQUIRE(X && ldx >= n, "rlh_fill_random: bad arguments");
-  dim3 grid(row_blocks(n, m), (unsigned)m);
   hipStream_t st = ctx().stream;
-  switch (dtype) {
-    case RLH_S: hipLaunchKernelGGL((fill_random_kernel<float, 1>), grid, dim3(256), 0, st, (float *)X, ldx, n, seed, row0, col0); break;
-    case RLH_D: hipLaunchKernelGGL((fill_random_kernel<double, 1>), grid, dim3(256), 0, st, (double *)X, ldx, n, seed, row0, col0); break;
-    case RLH_C: hipLaunchKernelGGL((fill_random_kernel<float, 2>), grid, dim3(256), 0, st, (float *)X, 2 * ldx, n, seed, row0, col0); break;
-    case RLH_Z: hipLaunchKernelGGL((fill_random_kernel<double, 2>), grid, dim3(256), 0, st, (double *)X, 2 * ldx, n, seed, row0, col0); break;
-  }
-  RLH_HIP(hipGetLastError());
-  return 0;
+  return for_col_panels(m, [&](int64_t j0, int64_t mp) {
+    dim3 grid(row_blocks(n, mp), (unsigned)mp);
+    const int64_t c0 = col0 + j0;
+    switch (dtype) {
+      case RLH_S: hipLaunchKernelGGL((fill_random_kernel<float, 1>), grid, dim3(256), 0, st, (float *)X + j0 * ldx, ldx, n, seed, row0, c0); break;
+      case RLH_D: hipLaunchKernelGGL((fill_random_kernel<double, 1>), grid, dim3(256), 0, st, (double *)X + j0 * ldx, ldx, n, seed, row0, c0); break;
+      case RLH_C: hipLaunchKernelGGL((fill_random_kernel<float, 2>), grid, dim3(256), 0, st, (float *)X + 2 * j0 * ldx, 2 * ldx, n, seed, row0, c0); break;
+      case RLH_Z: hipLaunchKernelGGL((fill_random_kernel<double, 2>), grid, dim3(256), 0, st, (double *)X + 2 * j0 * ldx, 2 * ldx, n, seed, row0, c0); break;
+    }
+    RLH_HIP(hipGetLastError());
+    return 0;
+  });
 }
 
 int rlh_bf16_pack(int src_dtype, int64_t n, int64_t m, const void *X, int64_t ldx, double scale, void *Y16, int64_t ldy) {
@@ -1284,15 +1309,18 @@ int rlh_bf16_pack(int src_dtype, int64_t n, int64_t m, const void *X, int64_t ld
   RLH_REQUIRE(n >= 0 && m >= 0, "rlh_bf16_pack: negative size");
   if (n == 0 || m == 0) return 0;
   RLH_REQUIRE(X && Y16 && ldx >= n && ldy >= n, "rlh_bf16_pack: bad arguments");
-  dim3 grid(row_blocks(n, m), (unsigned)m);
-  if (src_dtype == RLH_S)
-    hipLaunchKernelGGL((bf16_pack_kernel<float>), grid, dim3(256), 0, ctx().stream, (const float *)X, ldx, (float)scale,
-                       (unsigned short *)Y16, ldy, n);
-  else
-    hipLaunchKernelGGL((bf16_pack_kernel<double>), grid, dim3(256), 0, ctx().stream, (const double *)X, ldx, (float)scale,
-                       (unsigned short *)Y16, ldy, n);
-  RLH_HIP(hipGetLastError());
-  return 0;
+  return for_col_panels(m, [&](int64_t j0, int64_t mp) {
+    dim3 grid(row_blocks(n, mp), (unsigned)mp);
+    unsigned short *y = (unsigned short *)Y16 + j0 * ldy;
+    if (src_dtype == RLH_S)
+      hipLaunchKernelGGL((bf16_pack_kernel<float>), grid, dim3(256), 0, ctx().stream, (const float *)X + j0 * ldx, ldx,
+                         (float)scale, y, ldy, n);
+    else
+      hipLaunchKernelGGL((bf16_pack_kernel<double>), grid, dim3(256), 0, ctx().stream, (const double *)X + j0 * ldx, ldx,
+                         (float)scale, y, ldy, n);
+    RLH_HIP(hipGetLastError());
+    return 0;
+  });
 }
 
 int rlh_bf16_unpack(int dst_dtype, int64_t n, int64_t m, const void *X16, int64_t ldx, void *Y, int64_t ldy) {
@@ -1301,15 +1329,18 @@ int rlh_bf16_unpack(int dst_dtype, int64_t n, int64_t m, const void *X16, int64_
   RLH_REQUIRE(n >= 0 && m >= 0, "rlh_bf16_unpack: negative size");
   if (n == 0 || m == 0) return 0;
   RLH_REQUIRE(X16 && Y && ldx >= n && ldy >= n, "rlh_bf16_unpack: bad arguments");
-  dim3 grid(row_blocks(n, m), (unsigned)m);
-  if (dst_dtype == RLH_S)
-    hipLaunchKernelGGL((bf16_unpack_kernel<float>), grid, dim3(256), 0, ctx().stream, (const unsigned short *)X16, ldx,
-                       (float *)Y, ldy, n);
-  else
-    hipLaunchKernelGGL((bf16_unpack_kernel<double>), grid, dim3(256), 0, ctx().stream, (const unsigned short *)X16, ldx,
-                       (double *)Y, ldy, n);
-  RLH_HIP(hipGetLastError());
-  return 0;
+  return for_col_panels(m, [&](int64_t j0, int64_t mp) {
+    dim3 grid(row_blocks(n, mp), (unsigned)mp);
+    const unsigned short *x = (const unsigned short *)X16 + j0 * ldx;
+    if (dst_dtype == RLH_S)
+      hipLaunchKernelGGL((bf16_unpack_kernel<float>), grid, dim3(256), 0, ctx().stream, x, ldx, (float *)Y + j0 * ldy,
+                         ldy, n);
+    else
+      hipLaunchKernelGGL((bf16_unpack_kernel<double>), grid, dim3(256), 0, ctx().stream, x, ldx, (double *)Y + j0 * ldy,
+                         ldy, n);
+    RLH_HIP(hipGetLastError());
+    return 0;
+  });
 }
 
 int rlh_conj(int dtype, int64_t n, int64_t m, void *X, int64_t ldx) {
@@ -1317,13 +1348,15 @@ int rlh_conj(int dtype, int64_t n, int64_t m, void *X, int64_t ldx) {
   RLH_REQUIRE(dtype_valid(dtype), "rlh_conj: unknown dtype %d", dtype);
   if (dtype == RLH_S || dtype == RLH_D || n <= 0 || m <= 0) return 0;
   RLH_REQUIRE(X && ldx >= n, "rlh_conj: bad arguments");
-  dim3 grid(row_blocks(n, m), (unsigned)m);
-  if (dtype == RLH_C)
-    hipLaunchKernelGGL((conj_kernel<float>), grid, dim3(256), 0, ctx().stream, (float *)X, 2 * ldx, n);
-  else
-    hipLaunchKernelGGL((conj_kernel<double>), grid, dim3(256), 0, ctx().stream, (double *)X, 2 * ldx, n);
-  RLH_HIP(hipGetLastError());
-  return 0;
+  return for_col_panels(m, [&](int64_t j0, int64_t mp) {
+    dim3 grid(row_blocks(n, mp), (unsigned)mp);
+    if (dtype == RLH_C)
+      hipLaunchKernelGGL((conj_kernel<float>), grid, dim3(256), 0, ctx().stream, (float *)X + 2 * j0 * ldx, 2 * ldx, n);
+    else
+      hipLaunchKernelGGL((conj_kernel<double>), grid, dim3(256), 0, ctx().stream, (double *)X + 2 * j0 * ldx, 2 * ldx, n);
+    RLH_HIP(hipGetLastError());
+    return 0;
+  });
 }
 
 }  // extern "C"

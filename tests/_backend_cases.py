@@ -194,6 +194,10 @@ def matrix_case(golden_dir, key):
     assert np.array_equal(rows.data(), a)
     from oracle import ops
     assert rel(A.dots(), ops.dots(a, a)) < tol
+    # the same row norms from the stored columns of an F-ordered Matrix
+    d = Matrix(np.asfortranarray(a)).dots()
+    assert d.shape == (a.shape[0],) and d.dtype == DT[key]
+    assert rel(d, ops.dots(a, a)) < tol
 
 
 def sparse_case(golden_dir):

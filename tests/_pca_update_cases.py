@@ -189,3 +189,52 @@ def other_norms():
         assert np.linalg.norm((trans @ comps - As).astype(np.float64), 2) <= 0.05 * smax * 1.01
         mean, trans, comps = pca(A, tol=0.001, norm='m', mpc=10)
         assert comps.shape[0] == 10 and k_m > 10
+
+
+def tall_low_rank(rows=40000, more=36000, cols=32, rank=6, top=50.0, seed=7):
+    """(A, A1): `rows` x `cols` fp32 data of rank 6 with singular values top / 2^k plus noise at 1e-4 of the
+    smallest, and `more` further rows of the same row space (their singular values sqrt(more / rows) times
+    those of A) -- more rows than one launch of a column-wise kernel can index by column, which is what the
+    row view of a data matrix asks of rlh_dots / rlh_absmax when a tolerance stops the decomposition."""
+    rng = np.random.default_rng(seed)
+    sigma = top / 2.0 ** np.arange(rank)
+    v = np.linalg.qr(rng.standard_normal((cols, rank)))[0]
+    out = []
+    for r in (rows, more):
+        u = np.linalg.qr(rng.standard_normal((r, rank)))[0]
+        noise = rng.standard_normal((r, cols)) * (1e-4 * sigma[-1] / (np.sqrt(r) + np.sqrt(cols)))
+        out.append(np.ascontiguousarray(((u * (sigma * np.sqrt(r / rows))) @ v.T + noise).astype(np.float32)))
+    return out
+
+
+def frobenius_count(exact, tol):
+    """Number of leading singular values after which the Frobenius norm of the rest is at most tol times the whole."""
+    tail = np.sqrt(np.cumsum((exact ** 2)[::-1])[::-1])
+    return int(np.argmax(np.append(tail, 0.0) <= tol * tail[0]))
+
+
+def more_rows_than_a_launch_indexes():
+    """pca(tol=) of 40000 rows, then its update with 36000 more, against the exact spectrum of the centred data.  Its
+    gaps leave no doubt about what the stopping rule needs (the remainder after 4, 5 and 6 components is 0.061, 0.027
+    and 1e-5 of the whole).  The first call may return more: with 32 columns the solver's default block spans the
+    whole space, every triplet converges in the same iteration and none is cut off (measured on the CPU tier: 32),
+    so the rule's count is a lower bound there, as in tests/_truncated_svd_cases.py.  The update drops trailing
+    components itself and returns exactly what its rule gives."""
+    from raleigh_amd.interfaces import pca
+    A, A1 = tall_low_rank()
+    exact = np.linalg.svd((A - A.mean(axis=0)).astype(np.float64), compute_uv=False)
+    mean, trans, comps = pca(A, tol=0.05)
+    check_shape_of_result(A, mean, trans, comps)
+    k = frobenius_count(exact, 0.05)
+    assert k == 5 and k <= comps.shape[0] <= A.shape[1]
+    sv = np.linalg.norm(trans, axis=0)
+    assert np.max(np.abs(sv - exact[:len(sv)]) / exact[0]) < 2e-3
+    mean, trans, comps = pca(A1, have=(mean, trans, comps), tol=0.05)
+    B = np.concatenate((A, A1))
+    check_shape_of_result(B, mean, trans, comps)
+    exact = np.linalg.svd((B - B.mean(axis=0)).astype(np.float64), compute_uv=False)
+    # the update keeps what the new rows add and drops trailing components while they carry at most tol / 4
+    k = frobenius_count(exact, 0.05 / 4)
+    assert k == 6 and comps.shape[0] == k
+    sv = np.linalg.norm(trans, axis=0)
+    assert np.max(np.abs(sv - exact[:k]) / exact[0]) < 2e-3

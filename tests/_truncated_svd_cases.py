@@ -68,3 +68,30 @@ def refusals():
         truncated_svd(A)                       # neither nsv nor tol: the interactive mode is not offered
     with pytest.raises(ValueError):
         truncated_svd(A[0], nsv=1)
+
+
+def more_rows_than_a_launch_indexes(norm):
+    """truncated_svd(tol=0.05) of the 40000 x 32 fp32 matrix of _pca_update_cases.tall_low_rank under each norm: at
+    least the number of values that the stopping rule needs on the exact singular values 50 / 2^k, k < 6 (noise: 1e-4
+    of the last) -- with 32 columns the solver's default block spans the whole space and every triplet converges in
+    the same iteration, so it may return all of them (measured on the CPU tier: 32) -- and the values themselves."""
+    from raleigh_amd.interfaces import truncated_svd
+    from _pca_update_cases import tall_low_rank, frobenius_count
+    A = tall_low_rank()[0]
+    ue, exact, _ = np.linalg.svd(A.astype(np.float64), full_matrices=False)
+    if norm == 's':             # the first value at or below tol times the largest is the last one taken
+        need = int(np.argmax(exact <= 0.05 * exact[0])) + 1
+        assert need == 6
+    elif norm == 'f':
+        need = frobenius_count(exact, 0.05)
+        assert need == 5
+    else:                       # the largest row of A less its first k triplets
+        rows2 = np.maximum((A.astype(np.float64) ** 2).sum(1)[:, None] - np.cumsum((ue * exact) ** 2, axis=1), 0.0)
+        worst = np.sqrt(np.append((A.astype(np.float64) ** 2).sum(1).max(), rows2.max(axis=0)))
+        need = int(np.argmax(worst <= 0.05 * worst[0]))
+    u, sg, vt = truncated_svd(A, tol=0.05, norm=norm)
+    _check_factors(A, u, sg, vt, 5e-6)
+    assert 1 <= need <= len(sg) <= A.shape[1]
+    # (the values past the rank are noise of 3e-6 of the largest, which fp32 Gram products do not resolve)
+    k = min(len(sg), 6)
+    assert np.max(np.abs(sg[:k] - exact[:k])) <= 2e-6 * exact[0]

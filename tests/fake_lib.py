@@ -139,6 +139,8 @@ class FakeLib:
     # ---- reductions
     def rlh_gram(self, code, n, mx, X, ldx, my, Y, ldy, d_out, h_out):
         self._count('gram')
+        if mx > 32768 or my > 32768:
+            return self._fail('rlh_gram: more than 32768 vectors in a window')
         if mx == 0 or my == 0:
             return 0
         if ldx < n or ldy < n:

@@ -42,6 +42,10 @@ def test_update_with_other_norms(golden_dir):
     cases.update_with_other_norms(golden_dir)
 
 
+def test_more_rows_than_a_launch_indexes():
+    cases.more_rows_than_a_launch_indexes()
+
+
 @pytest.mark.parametrize('mode', ['1', '0'])
 def test_update_eigensolver_on_the_device_and_on_the_host(monkeypatch, mode):
     """The k x k eigenproblems of an update at k ~ 900 through the vendor's eigensolver on the GPU (RLH_DEVICE_EIGH=1,

@@ -13,5 +13,10 @@ def test_truncated_svd(golden_dir, m, n, dt):
     cases.run(golden_dir, m, n, dt)
 
 
+@pytest.mark.parametrize('norm', ['f', 's', 'm'])
+def test_more_rows_than_a_launch_indexes(norm):
+    cases.more_rows_than_a_launch_indexes(norm)
+
+
 def test_refusals():
     cases.refusals()
