@@ -415,8 +415,12 @@ class FakeLib:
 
     def rlh_bdiag_solve(self, code, n, coef, shift, m, X, ldx):
         self._count('rlh_bdiag_solve')
+        if n < 0 or not 0 <= m <= 65535:
+            return self._fail('rlh_bdiag_solve: bad sizes')
         if n == 0 or m == 0:
             return 0
+        if not (_addr(coef) and _addr(shift) and _addr(X) and ldx >= n):
+            return self._fail('rlh_bdiag_solve: bad arguments')
         c = _flat(coef, _DT[code], 2 * n).reshape(n, 2)
         s = _flat(shift, np.int32, n)
         x = _block(X, code, n, m, ldx)
@@ -425,8 +429,11 @@ class FakeLib:
         return 0
 
     def rlh_sptrsv_create(self, ph, code, n, indptr, indices, values, lower, unit):
+        """Rows in any order, the diagonal anywhere in its row, duplicate off-diagonal entries summed."""
         ip = _flat(indptr, np.int64, n + 1).copy()
         nnz = int(ip[-1])
+        if nnz and not (_addr(indices) and _addr(values)):
+            return self._fail('rlh_sptrsv_create: null indices/values')
         ix = _flat(indices, np.int32, nnz).copy()
         va = _flat(values, _DT[code], nnz).copy()
         mat = sp.csr_matrix((va, ix, ip), shape=(n, n))
@@ -435,33 +442,52 @@ class FakeLib:
             return self._fail('rlh_sptrsv_create: a unit-diagonal factor must not store its diagonal')
         if np.any((ix > rows) if lower else (ix < rows)):
             return self._fail('rlh_sptrsv_create: entry lies in the wrong triangle')
+        mat.sum_duplicates()
         if unit:
             mat = mat + sp.identity(n, dtype=_DT[code], format='csr')
         elif np.any(mat.diagonal() == 0):
             return self._fail('rlh_sptrsv_create: zero diagonal')
+        mat = sp.csr_matrix(mat)
+        mat.sort_indices()
+        # rows on the longest dependency path: the levels of the factor as given (the stand-in has no block transform)
+        level = np.zeros(max(n, 1), dtype=np.int64)
+        for i in (range(n) if lower else range(n - 1, -1, -1)):
+            c = mat.indices[mat.indptr[i]:mat.indptr[i + 1]]
+            c = c[c != i]
+            level[i] = level[c].max() + 1 if c.size else 0
         h = self._next_handle
         self._next_handle += 1
-        self._csr[h] = (sp.csr_matrix(mat), bool(lower), code, nnz - (0 if unit else n))
+        self._csr[h] = (mat, bool(lower), code, nnz - (0 if unit else n), int(level[:n].max()) + 1 if n else 0)
         ph._obj.value = h
         return 0
 
     def rlh_sptrsv_info(self, h, nnz, levels, nbytes):
         ctypes.cast(nnz, ctypes.POINTER(ctypes.c_int64))[0] = self._csr[_addr(h)][3]
-        ctypes.cast(levels, ctypes.POINTER(ctypes.c_int64))[0] = 1
+        ctypes.cast(levels, ctypes.POINTER(ctypes.c_int64))[0] = self._csr[_addr(h)][4]
         ctypes.cast(nbytes, ctypes.POINTER(ctypes.c_int64))[0] = 0
         return 0
 
     def rlh_sptrsv_solve_chain(self, nops, ops, perm_in, perm_out, m, B, ldb, X, ldx):
         import scipy.sparse.linalg as sla
         self._count('rlh_sptrsv_solve_chain')
+        if not 1 <= nops <= 8:
+            return self._fail('rlh_sptrsv_solve_chain: 1 to 8 operators')
         handles = [int(ops[i]) for i in range(nops)]
-        mat0, _, code, _ = self._csr[handles[0]]
+        mat0, _, code, _, _ = self._csr[handles[0]]
         n = mat0.shape[0]
+        if any(self._csr[hh][2] != code or self._csr[hh][0].shape[0] != n for hh in handles):
+            return self._fail('rlh_sptrsv_solve_chain: the operators must have one type and one size')
+        if not 0 <= m <= 65536:
+            return self._fail('rlh_sptrsv_solve_chain: bad block size')
+        if m == 0 or n == 0:
+            return 0
+        if not (_addr(B) and _addr(X) and ldb >= n and ldx >= n):
+            return self._fail('rlh_sptrsv_solve_chain: bad block arguments')
         w = _block(B, code, n, m, ldb).T.copy()
         if _addr(perm_in):
             w = w[_flat(perm_in, np.int64, n)]
         for hh in handles:
-            mat, lower, _, _ = self._csr[hh]
+            mat, lower = self._csr[hh][:2]
             w = sla.spsolve_triangular(mat, w, lower=lower)
         out = _block(X, code, n, m, ldx)
         if _addr(perm_out):
