@@ -390,6 +390,22 @@ int rlh_dense_apply_r1(int dtype, int64_t M, int64_t N, const void *A, int64_t l
 typedef struct rlh_spd *rlh_spd_t;
 int rlh_spd_create(rlh_spd_t *h, int dtype, int64_t n_rows, int64_t n_cols, const int64_t *indptr,
                    const int32_t *indices, const void *values);
+/* The same operator from CSR arrays that already lie in DEVICE memory (`index_bits` 32 or 64: the type of both
+ * index arrays).  The input must be canonical -- indptr[0] == 0, indptr non-decreasing, its last entry the
+ * number of stored entries, columns inside [0, N) and strictly ascending within each row -- and is checked on
+ * the device before anything is built: a violation returns non-zero, a message that names it and a null handle
+ * (the last entry is held against what the allocations of the index and value arrays can hold, where the
+ * runtime knows them).  The handle's arrays are exactly those rlh_spd_create makes for the same matrix, built
+ * by kernels on the library stream (no floating-point atomics; integer atomics only for counts); the caller's
+ * arrays are copied, never written and not needed after the call.  One 16-byte status record is all that goes
+ * to the host.  rlh_spd_stats then reports the device time of the transpose.  RLH_SPD_TABLE_BYTES (read at
+ * creation, default 512 MB) caps the table of places of the transpose. */
+int rlh_spd_create_device(rlh_spd_t *h, int dtype, int64_t n_rows, int64_t n_cols, int index_bits,
+                          const void *d_indptr, const void *d_indices, const void *d_values);
+/* the sums of the squared moduli of the M rows as M HOST doubles (float64 accumulation in entry order) and
+ * the largest |re| / |im| of the entries as a HOST double, from the device copy; both calls synchronise */
+int rlh_spd_row_sumsq(rlh_spd_t h, double *h_out);
+int rlh_spd_absmax(rlh_spd_t h, double *h_out);
 int rlh_spd_destroy(rlh_spd_t h);
 int rlh_spd_info(rlh_spd_t h, int64_t *n_rows, int64_t *n_cols, int64_t *nnz, int64_t *device_bytes);
 int rlh_spd_stats(rlh_spd_t h, int64_t *workspace_bytes, double *transpose_seconds);
@@ -411,6 +427,13 @@ typedef struct rlh_bytes *rlh_bytes_t;
 /* stands for the upload of the data (Matrix.__init__, dense_cublas.py:635-700) */
 int rlh_bytes_create(rlh_bytes_t *h, int kind, int64_t n_rows, int64_t n_cols, const void *h_data,
                      int64_t row_stride);
+/* The same from row-major bytes that already lie in DEVICE memory.  The handle BORROWS the caller's buffer (which
+ * must then outlive it and is never written) when N, row_stride and the address are all multiples of 16: every
+ * 16-byte piece the kernels read then lies within the N columns of a row.  Otherwise it makes the padded copy with
+ * a kernel on the library stream.  rlh_bytes_info counts only what the handle owns: the workspace alone for a
+ * borrowed matrix. */
+int rlh_bytes_create_device(rlh_bytes_t *h, int kind, int64_t n_rows, int64_t n_cols, const void *d_data,
+                            int64_t row_stride);
 int rlh_bytes_destroy(rlh_bytes_t h);
 /* sizes, device bytes held (data and workspace) and the workspace bytes alone (the split-K partial tiles; it
  * grows when a product needs more than before: that call synchronises the stream once) */

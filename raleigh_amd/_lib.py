@@ -102,11 +102,15 @@ SIGNATURES = {
     'rlh_dense_apply': [_int, _i64, _i64, _p, _i64, _int, _int, _i64, _p, _i64, _p, _i64],
     'rlh_dense_apply_r1': [_int, _i64, _i64, _p, _i64, _int, _int, _i64, _p, _i64, _p, _i64, _p, _p],
     'rlh_spd_create': [ctypes.POINTER(_p), _int, _i64, _i64, _p, _p, _p],
+    'rlh_spd_create_device': [ctypes.POINTER(_p), _int, _i64, _i64, _int, _p, _p, _p],
+    'rlh_spd_row_sumsq': [_p, _p],
+    'rlh_spd_absmax': [_p, ctypes.POINTER(ctypes.c_double)],
     'rlh_spd_destroy': [_p],
     'rlh_spd_info': [_p, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
     'rlh_spd_stats': [_p, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)],
     'rlh_spd_apply': [_p, _int, _i64, _p, _i64, _p, _i64, _p, _p],
     'rlh_bytes_create': [ctypes.POINTER(_p), _int, _i64, _i64, _p, _i64],
+    'rlh_bytes_create_device': [ctypes.POINTER(_p), _int, _i64, _i64, _p, _i64],
     'rlh_bytes_destroy': [_p],
     'rlh_bytes_info': [_p, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
     'rlh_bytes_apply': [_p, _int, _i64, _p, _i64, _p, _i64, _p, _p],
@@ -184,6 +188,11 @@ def lib(device=None):
 
 def device():
     return _initialised_device
+
+
+def local_device():
+    """The GPU this process is bound to: the one initialised, or the one `lib()` will initialise."""
+    return default_device() if _initialised_device is None else _initialised_device
 
 
 def synchronize():

@@ -23,8 +23,9 @@ class _DeviceHandle:
 
 
 class AMatrix:
-    """A host ndarray uploaded once; ``as_operator()`` is the device Matrix, ``as_vectors()`` a
-    shallow Vectors view of its rows."""
+    """A host ndarray uploaded once, or a torch tensor already in device memory (borrowed where its layout
+    allows, else copied once on the device: hip.Matrix); ``as_operator()`` is the device Matrix,
+    ``as_vectors()`` a shallow Vectors view of its rows."""
 
     def __init__(self, a, arch='hip', copy_data=False):
         if str(arch)[:3] not in _ACCEPTED:

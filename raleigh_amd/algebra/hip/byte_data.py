@@ -12,6 +12,7 @@ import ctypes
 import numpy as np
 
 from ... import _lib
+from . import device_data
 from .vectors import Vectors
 
 _KINDS = {np.uint8: 0, np.int8: 1}
@@ -20,6 +21,10 @@ _KINDS = {np.uint8: 0, np.int8: 1}
 class ByteMatrix:
 
     def __init__(self, a):
+        self._tensor = None
+        if device_data.is_device_tensor(a):
+            self._from_device_tensor(a)
+            return
         if not isinstance(a, np.ndarray):
             raise ValueError('wrong argument %s in ByteMatrix constructor' % repr(type(a)))
         if a.ndim != 2:
@@ -34,6 +39,30 @@ class ByteMatrix:
         _lib.check(_lib.lib().rlh_bytes_create(ctypes.byref(h), _KINDS[self._storage], a.shape[0], a.shape[1],
                                                _lib.host_ptr(a), a.shape[1]))
         self._h = h
+        self._dots = None
+        self._absmax = None
+
+    def _from_device_tensor(self, t):
+        """Row-major bytes in device memory (rlh_bytes_create_device): borrowed when the number of columns, the row
+        stride and the address are multiples of 16, else copied into the padded layout by a kernel.  The tensor is
+        kept alive with the operator and never written."""
+        if t.dim() != 2:
+            raise ValueError('Matrix data must be a 2D tensor')
+        dt = device_data.numpy_type(t)
+        if dt not in _KINDS:
+            raise ValueError('data type %s not supported' % repr(dt))
+        if t.shape[0] > 1 and t.shape[1] > 0 and (t.stride(1) != 1 or t.stride(0) < t.shape[1]) \
+                or t.shape[1] > 1 and t.stride(1) != 1:
+            raise ValueError('8-bit matrix data must be row-major with unit stride along the rows: make the tensor '
+                             'contiguous first')
+        self._storage = dt
+        self._shape = tuple(t.shape)
+        stride = t.stride(0) if t.shape[0] > 1 else t.shape[1]
+        h = ctypes.c_void_p()
+        _lib.check(_lib.lib().rlh_bytes_create_device(ctypes.byref(h), _KINDS[dt], t.shape[0], t.shape[1],
+                                                      ctypes.c_void_p(t.data_ptr()), max(stride, t.shape[1])))
+        self._h = h
+        self._tensor = t
         self._dots = None
         self._absmax = None
 

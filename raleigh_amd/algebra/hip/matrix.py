@@ -8,8 +8,18 @@ Vectors, shape/order/data_type/dots/new_vectors/apply) with the GEMM of
 import numpy as np
 
 from ... import _lib
+from . import device_data
 from .memory import DeviceBuffer, upload
 from .vectors import Vectors, _padded
+
+
+class _Borrowed:
+    """Device memory that belongs to the caller (a torch tensor): an address, nothing to release."""
+
+    def __init__(self, owner):
+        self.owner = owner              # kept alive for as long as anything addresses its memory
+        self.ptr = int(owner.data_ptr())
+        self.nbytes = 0
 
 
 class Matrix:
@@ -43,10 +53,51 @@ class Matrix:
             self._buf = DeviceBuffer(max(rows, 1) * self._lda * es)
             self._off = 0
             upload(self._buf.ptr, self._lda * es, host)
+        elif device_data.is_device_tensor(arg):
+            self._from_device_tensor(arg)
         else:
             raise ValueError('wrong argument %s in Matrix constructor' % repr(type(arg)))
         self._code = _lib.DTYPE_CODE[self._dtype]
         self._es = _lib.DTYPE_SIZE[self._dtype]
+
+    def _from_device_tensor(self, t):
+        """A 2D strided tensor in device memory: BORROWED as it stands (no copy; the Matrix keeps the tensor alive and
+        never writes it) when the fast kernels take its layout -- unit stride along one axis, address and leading
+        dimension in bytes both multiples of 16, the storage reaching to the end of the last leading dimension --
+        otherwise copied once, device to device, into the padded layout the ndarray constructor makes."""
+        if t.dim() != 2:
+            raise ValueError('Matrix data must be a 2D tensor')
+        self._dtype = device_data.numpy_type(t)
+        if self._dtype not in _lib.DTYPE_CODE:
+            raise ValueError('data type %s not supported' % repr(self._dtype))
+        self._shape = tuple(t.shape)
+        es = t.element_size()
+        s0, s1 = t.stride()
+        if t.is_contiguous() or (s1 == 1 and s0 >= t.shape[1]):
+            self._order = 'C_CONTIGUOUS'
+            rows, cols, ld = t.shape[0], t.shape[1], (t.shape[1] if t.is_contiguous() else s0)
+        elif s0 == 1 and s1 >= t.shape[0]:
+            self._order = 'F_CONTIGUOUS'
+            rows, cols, ld = t.shape[1], t.shape[0], s1
+        else:
+            raise ValueError('Matrix data must have unit stride along one axis: make the tensor contiguous first')
+        self._tensor = None
+        if rows > 0 and cols > 0 and t.data_ptr() % 16 == 0 and (ld * es) % 16 == 0 \
+                and device_data.storage_room(t) >= rows * ld * es:
+            self._tensor = t                    # borrowed
+            self._buf = _Borrowed(t)
+            self._lda = ld
+        else:
+            self._lda = _padded(cols)
+            self._buf = DeviceBuffer(max(rows, 1) * self._lda * es)
+            if rows > 0 and cols > 0:
+                _lib.check(_lib.lib().rlh_copy2d(self._buf.ptr, self._lda * es, t.data_ptr(), ld * es, cols * es, rows, 2))
+                _lib.check(_lib.lib().rlh_sync())       # the caller's tensor is not needed after the constructor
+        self._off = 0
+
+    def borrowed(self):
+        """True when the data are the caller's device tensor itself, not a library allocation."""
+        return getattr(self, '_tensor', None) is not None
 
     def data_ptr(self):
         return (self._buf.ptr if self._buf is not None else 0) + self._off
@@ -73,6 +124,8 @@ class Matrix:
         return self._dtype in (np.complex64, np.complex128)
 
     def fill(self, data):
+        if self.borrowed():
+            raise ValueError('a Matrix over a borrowed tensor is never written')
         host = data if self._order == 'C_CONTIGUOUS' else data.T
         upload(self.data_ptr(), self._lda * self._es, np.ascontiguousarray(host, dtype=self._dtype))
 

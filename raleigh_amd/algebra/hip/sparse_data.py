@@ -12,6 +12,7 @@ import numpy as np
 import scipy.sparse as scs
 
 from ... import _lib
+from . import device_data
 from .vectors import Vectors
 
 
@@ -34,6 +35,10 @@ def canonical_csr(a):
 class SparseMatrix:
 
     def __init__(self, a):
+        self._dots = self._absmax = None
+        if device_data.is_device_tensor(a):
+            self._from_device_tensor(a)
+            return
         csr = canonical_csr(a)
         self._dtype = csr.dtype.type
         self._shape = csr.shape
@@ -55,6 +60,40 @@ class SparseMatrix:
         _lib.check(_lib.lib().rlh_spd_create(ctypes.byref(h), self._code, self._shape[0], self._shape[1],
                                              _lib.host_ptr(indptr), _lib.host_ptr(indices), _lib.host_ptr(values)))
         self._h = h
+
+    def _from_device_tensor(self, t):
+        """A torch.sparse_csr tensor in device memory: both CSR copies and the partition are built by kernels
+        (rlh_spd_create_device), which also check that the tensor is canonical -- rows with ascending columns and no
+        duplicates, as torch's own constructors and conversions produce; the squared row norms and the largest entry
+        come from the device copy when first asked for.  The tensor's arrays are copied, never written."""
+        import torch
+        if t.layout != torch.sparse_csr or t.dim() != 2:
+            raise ValueError('a 2D torch.sparse_csr tensor is needed')
+        self._dtype = device_data.numpy_type(t)
+        if self._dtype not in _lib.DTYPE_CODE:
+            raise ValueError('data type %s not supported' % repr(self._dtype))
+        crow, col, val = t.crow_indices(), t.col_indices(), t.values()
+        bits = {'int32': 32, 'int64': 64}.get(str(crow.dtype).split('.')[-1])
+        if bits is None or col.dtype != crow.dtype:
+            raise ValueError('sparse index type %s not supported (int32, int64)' % crow.dtype)
+        crow, col, val = crow.contiguous(), col.contiguous(), val.detach().resolve_conj().resolve_neg().contiguous()
+        if val.is_cuda:
+            torch.cuda.current_stream(val.device).synchronize()
+        self._shape = tuple(t.shape)
+        self._code = _lib.DTYPE_CODE[self._dtype]
+        h = ctypes.c_void_p()
+        try:
+            _lib.check(_lib.lib().rlh_spd_create_device(
+                ctypes.byref(h), self._code, self._shape[0], self._shape[1], bits, ctypes.c_void_p(crow.data_ptr()),
+                ctypes.c_void_p(col.data_ptr()), ctypes.c_void_p(val.data_ptr())))
+        except _lib.RlhError as e:
+            if ': rlh_spd_create_device:' in str(e):         # the library's own check, not a HIP failure
+                raise ValueError('the sparse tensor is not canonical CSR: %s' % e)
+            raise
+        self._h = h
+        nnz = ctypes.c_int64()
+        _lib.check(_lib.lib().rlh_spd_info(self._h, None, None, ctypes.byref(nnz), None))
+        self._nnz = int(nnz.value)
 
     def __del__(self):
         h, self._h = getattr(self, '_h', None), None
@@ -88,17 +127,27 @@ class SparseMatrix:
         return int(nb.value)
 
     def transpose_seconds(self):
-        """Host seconds taken by building the CSR copy of A^H when the operator was created."""
+        """Seconds taken by building the CSR copy of A^H when the operator was created: on the host threads, or on the
+        device (measured with events) for an operator built from device arrays."""
         nb, t = ctypes.c_int64(), ctypes.c_double()
         _lib.check(_lib.lib().rlh_spd_stats(self._h, ctypes.byref(nb), ctypes.byref(t)))
         return float(t.value)
 
     def dots(self):
-        """Squared norms of the rows (from the host values, once)."""
+        """Squared norms of the rows (float64): from the host values at construction, or from the device copy
+        (rlh_spd_row_sumsq) when the operator was built from device arrays; computed once."""
+        if self._dots is None:
+            out = np.zeros(self._shape[0], dtype=np.float64)
+            _lib.check(_lib.lib().rlh_spd_row_sumsq(self._h, _lib.host_ptr(out)))
+            self._dots = out
         return self._dots.copy()
 
     def absmax(self):
         """Largest modulus of the (real / imaginary parts of the) entries."""
+        if self._absmax is None:
+            out = ctypes.c_double()
+            _lib.check(_lib.lib().rlh_spd_absmax(self._h, ctypes.byref(out)))
+            self._absmax = float(out.value)
         return self._absmax
 
     def new_vectors(self, dim=None, nv=0):

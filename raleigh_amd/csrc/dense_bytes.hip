@@ -33,9 +33,12 @@
 
 struct rlh_bytes {
   int kind = 0;                        // RLH_BYTES_U8 / RLH_BYTES_I8
-  int64_t rows = 0, cols = 0, lda = 0; // lda: bytes per row on the device, a multiple of 16, zero padded
+  int64_t rows = 0, cols = 0, lda = 0; // lda: bytes per row on the device, a multiple of 16
+  int64_t ncp = 0;                     // cols rounded up to 16: what the kernels read of a row (zero padded when owned;
+                                       // a borrowed matrix has ncp == cols, so nothing beyond its columns is read)
   unsigned char *A = nullptr;
-  int64_t a_bytes = 0;
+  int64_t a_bytes = 0;                 // bytes owned by the handle: 0 for a borrowed matrix
+  bool owned = true;
   char *work = nullptr;                // split-K partial tiles
   int64_t work_bytes = 0;
 };
@@ -44,7 +47,7 @@ namespace rlh {
 namespace {
 
 struct BytesArgs {
-  const unsigned char *A; int64_t lda;
+  const unsigned char *A; int64_t lda, ncp;
   int64_t ny, nx;                      // Op is ny x nx
   const float *X; int64_t ldx;
   float *Y; int64_t ldy;
@@ -121,14 +124,14 @@ __global__ __launch_bounds__(256, 2) void bytes_mfma_kernel(BytesArgs a, float *
       const int64_t k = k0 + (tid & 1) * 16;
       if constexpr (EDGE) {
         ra = u32x4{0u, 0u, 0u, 0u};
-        if (k + 16 <= a.lda) ra = *reinterpret_cast<const u32x4 *>(A + i * a.lda + k);
+        if (k + 16 <= a.ncp) ra = *reinterpret_cast<const u32x4 *>(A + i * a.lda + k);
       } else {
         ra = *reinterpret_cast<const u32x4 *>(A + i * a.lda + k);
       }
     } else {                       // a 4 x 4 block: output rows iq .. iq + 3 at k = kq .. kq + 3
       const int kq = (tid >> 5) * 4;
       int64_t i = i0 + (tid & 31) * 4;
-      i = i < a.lda ? i : a.lda - 4;
+      i = i < a.ncp ? i : a.ncp - 4;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int64_t k = k0 + kq + q;
@@ -283,13 +286,13 @@ __global__ __launch_bounds__(256) void bytes_splitk_reduce(const float *__restri
 // exact sums of squares of the rows: one wave per row, 64-bit integer accumulation (255^2 N exceeds 32 bits)
 template <bool SGN>
 __global__ __launch_bounds__(256) void bytes_row_sumsq_kernel(const unsigned char *__restrict__ A, int64_t rows, int64_t lda,
-                                                              double *__restrict__ out) {
+                                                              int64_t ncp, double *__restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= rows) return;
   const unsigned *__restrict__ p = reinterpret_cast<const unsigned *>(A + r * lda);
   unsigned long long s = 0;
-  for (int64_t q = lane; q < lda / 4; q += 64) {
+  for (int64_t q = lane; q < ncp / 4; q += 64) {
     const unsigned d = p[q];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -302,14 +305,16 @@ __global__ __launch_bounds__(256) void bytes_row_sumsq_kernel(const unsigned cha
   if (lane == 0) out[r] = (double)s;              // below 2^53: exact
 }
 
-// largest modulus per workgroup (the padding holds zeros); the host takes the largest of them
+// largest modulus per workgroup (the padding holds zeros); the host takes the largest of them.  dwords = rows * rowdw,
+// rowdw dwords of every row of lda bytes.
 template <bool SGN>
-__global__ __launch_bounds__(256) void bytes_absmax_kernel(const unsigned char *__restrict__ A, int64_t dwords, int *__restrict__ out) {
+__global__ __launch_bounds__(256) void bytes_absmax_kernel(const unsigned char *__restrict__ A, int64_t dwords, int64_t rowdw,
+                                                           int64_t lda, int *__restrict__ out) {
   __shared__ int red[4];
-  const unsigned *__restrict__ p = reinterpret_cast<const unsigned *>(A);
   int mx = 0;
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < dwords; q += (int64_t)gridDim.x * 256) {
-    const unsigned d = p[q];
+    const int64_t r = q / rowdw;
+    const unsigned d = *reinterpret_cast<const unsigned *>(A + r * lda + (q - r * rowdw) * 4);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       int b = SGN ? (int)(signed char)((d >> (8 * j)) & 0xffu) : (int)((d >> (8 * j)) & 0xffu);
@@ -327,6 +332,21 @@ __global__ __launch_bounds__(256) void bytes_absmax_kernel(const unsigned char *
   if (threadIdx.x == 0) {
     for (int w = 1; w < 4; ++w) mx = red[w] > mx ? red[w] : mx;
     out[blockIdx.x] = mx;
+  }
+}
+
+// the padded copy of rlh_bytes_create made on the device: dst rows of lda bytes (a multiple of 16), four bytes per
+// thread, the pad zero; src rows row_stride bytes apart, read byte by byte (any alignment)
+__global__ __launch_bounds__(256) void bytes_pad_copy_kernel(unsigned char *__restrict__ dst, int64_t lda, const unsigned char *__restrict__ src,
+                                                             int64_t row_stride, int64_t rows, int64_t cols) {
+  const int64_t rowdw = lda / 4, dwords = rows * rowdw;
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < dwords; q += (int64_t)gridDim.x * 256) {
+    const int64_t r = q / rowdw, c0 = (q - r * rowdw) * 4;
+    unsigned d = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (c0 + j < cols) d |= (unsigned)src[r * row_stride + c0 + j] << (8 * j);
+    *reinterpret_cast<unsigned *>(dst + r * lda + c0) = d;
   }
 }
 
@@ -399,6 +419,7 @@ extern "C" int rlh_bytes_create(rlh_bytes_t *ph, int kind, int64_t n_rows, int64
   h->cols = n_cols;
   h->lda = (n_cols + 15) / 16 * 16;
   if (h->lda < 16) h->lda = 16;
+  h->ncp = h->lda;
   h->a_bytes = (n_rows > 0 ? n_rows : 1) * h->lda;
   hipError_t e = hipMalloc(&h->A, h->a_bytes);
   if (e == hipSuccess && h->lda != n_cols) e = hipMemset(h->A, 0, h->a_bytes);
@@ -413,11 +434,56 @@ extern "C" int rlh_bytes_create(rlh_bytes_t *ph, int kind, int64_t n_rows, int64
   return 0;
 }
 
+extern "C" int rlh_bytes_create_device(rlh_bytes_t *ph, int kind, int64_t n_rows, int64_t n_cols, const void *d_data,
+                                       int64_t row_stride) {
+  if (int rc = require_ready()) return rc;
+  RLH_REQUIRE(ph, "rlh_bytes_create_device: null handle pointer");
+  *ph = nullptr;
+  RLH_REQUIRE(kind == RLH_BYTES_U8 || kind == RLH_BYTES_I8, "rlh_bytes_create_device: kind must be 0 (uint8) or 1 (int8), got %d", kind);
+  RLH_REQUIRE(n_rows >= 0 && n_cols >= 0, "rlh_bytes_create_device: negative size");
+  RLH_REQUIRE(n_rows == 0 || n_cols == 0 || d_data, "rlh_bytes_create_device: null data");
+  RLH_REQUIRE(row_stride >= n_cols, "rlh_bytes_create_device: row stride smaller than the number of columns");
+  rlh_bytes *h = new rlh_bytes();
+  h->kind = kind;
+  h->rows = n_rows;
+  h->cols = n_cols;
+  if (n_rows > 0 && n_cols > 0 && n_cols % 16 == 0 && row_stride % 16 == 0 && (reinterpret_cast<uintptr_t>(d_data) & 15u) == 0) {
+    h->owned = false;                    // borrowed: every 16-byte piece the kernels read lies within the columns
+    h->A = (unsigned char *)const_cast<void *>(d_data);
+    h->lda = row_stride;
+    h->ncp = n_cols;
+    h->a_bytes = 0;
+    *ph = h;
+    return 0;
+  }
+  h->lda = (n_cols + 15) / 16 * 16;
+  if (h->lda < 16) h->lda = 16;
+  h->ncp = h->lda;
+  h->a_bytes = (n_rows > 0 ? n_rows : 1) * h->lda;
+  Context &c = ctx();
+  hipError_t e = hipMalloc(&h->A, h->a_bytes);
+  if (e == hipSuccess && n_rows == 0) e = hipMemsetAsync(h->A, 0, h->a_bytes, c.stream);
+  if (e == hipSuccess && n_rows > 0) {
+    int64_t nb = (n_rows * (h->lda / 4) + 255) / 256;
+    if (nb > 65536) nb = 65536;
+    hipLaunchKernelGGL(bytes_pad_copy_kernel, dim3((unsigned)nb), dim3(256), 0, c.stream, h->A, h->lda, (const unsigned char *)d_data,
+                       row_stride, n_rows, n_cols);
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) {
+    if (h->A) (void)hipFree(h->A);
+    delete h;
+    return hip_fail(e, "rlh_bytes_create_device: device copy", __FILE__, __LINE__);
+  }
+  *ph = h;
+  return 0;
+}
+
 extern "C" int rlh_bytes_destroy(rlh_bytes_t h) {
   if (!h) return 0;
   if (ctx().ready) (void)hipStreamSynchronize(ctx().stream);
   (void)hipFree(h->work);
-  (void)hipFree(h->A);
+  if (h->owned) (void)hipFree(h->A);
   delete h;
   return 0;
 }
@@ -444,7 +510,7 @@ extern "C" int rlh_bytes_apply(rlh_bytes_t h, int transp, int64_t m, const void 
   RLH_REQUIRE(ldx >= nx && ldy >= ny, "rlh_bytes_apply: Matrix and vectors dimensions incompatible");
   RLH_REQUIRE(m <= 65535, "rlh_bytes_apply: too many vectors");
   BytesArgs a;
-  a.A = h->A; a.lda = h->lda;
+  a.A = h->A; a.lda = h->lda; a.ncp = h->ncp;
   a.ny = ny; a.nx = nx;
   a.X = (const float *)X; a.ldx = ldx; a.Y = (float *)Y; a.ldy = ldy; a.m = (int)m;
   a.x_vec = ((reinterpret_cast<uintptr_t>(X) & 15u) == 0 && ldx % 4 == 0) ? 1 : 0;
@@ -463,8 +529,8 @@ extern "C" int rlh_bytes_row_sumsq(rlh_bytes_t h, double *h_out) {
   double *d = nullptr;
   RLH_HIP(hipMalloc(&d, h->rows * sizeof(double)));
   const dim3 grid((unsigned)((h->rows + 3) / 4));
-  if (h->kind == RLH_BYTES_I8) hipLaunchKernelGGL(bytes_row_sumsq_kernel<true>, grid, dim3(256), 0, c.stream, h->A, h->rows, h->lda, d);
-  else hipLaunchKernelGGL(bytes_row_sumsq_kernel<false>, grid, dim3(256), 0, c.stream, h->A, h->rows, h->lda, d);
+  if (h->kind == RLH_BYTES_I8) hipLaunchKernelGGL(bytes_row_sumsq_kernel<true>, grid, dim3(256), 0, c.stream, h->A, h->rows, h->lda, h->ncp, d);
+  else hipLaunchKernelGGL(bytes_row_sumsq_kernel<false>, grid, dim3(256), 0, c.stream, h->A, h->rows, h->lda, h->ncp, d);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
   if (e == hipSuccess) e = hipMemcpy(h_out, d, h->rows * sizeof(double), hipMemcpyDeviceToHost);
@@ -479,13 +545,13 @@ extern "C" int rlh_bytes_absmax(rlh_bytes_t h, double *h_out) {
   *h_out = 0.0;
   if (h->rows == 0 || h->cols == 0) return 0;
   Context &c = ctx();
-  const int64_t dwords = h->rows * h->lda / 4;
+  const int64_t rowdw = h->ncp / 4, dwords = h->rows * rowdw;
   int64_t nb = (dwords + 255) / 256;
   if (nb > 1024) nb = 1024;
   int *d = nullptr;
   RLH_HIP(hipMalloc(&d, nb * sizeof(int)));
-  if (h->kind == RLH_BYTES_I8) hipLaunchKernelGGL(bytes_absmax_kernel<true>, dim3((unsigned)nb), dim3(256), 0, c.stream, h->A, dwords, d);
-  else hipLaunchKernelGGL(bytes_absmax_kernel<false>, dim3((unsigned)nb), dim3(256), 0, c.stream, h->A, dwords, d);
+  if (h->kind == RLH_BYTES_I8) hipLaunchKernelGGL(bytes_absmax_kernel<true>, dim3((unsigned)nb), dim3(256), 0, c.stream, h->A, dwords, rowdw, h->lda, d);
+  else hipLaunchKernelGGL(bytes_absmax_kernel<false>, dim3((unsigned)nb), dim3(256), 0, c.stream, h->A, dwords, rowdw, h->lda, d);
   std::vector<int> host((size_t)nb);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(c.stream);

@@ -2,7 +2,8 @@
 //
 // The operator of truncated SVD / PCA on sparse data (rlh_spd_*, include/rlhip.h).  Both products run on the
 // same row-parallel kernel: the handle holds A and a CSR copy of A^H (values conjugated, entries of each row in
-// ascending order of A's row index) built once on the host threads.
+// ascending order of A's row index) built once: on the host threads from host arrays (rlh_spd_create), by kernels
+// from arrays that already lie in device memory (rlh_spd_create_device; the same arrays either way).
 //
 // One product of a panel of at most kPanel vectors is four launches on the library stream:
 //   1. interleave: the column-major input block -> a row-major workspace Xi (row stride wp >= w, padded with
@@ -324,6 +325,432 @@ int create_impl(rlh_spd *h, int64_t M, int64_t N, const int64_t *ip, const int32
   return upload_side(h->side[1], N, M, tp.data(), tx.data(), tv.data(), es);
 }
 
+// ---------------------------------------------------------------- the operator built on the device
+// rlh_spd_create_device: the same arrays as create_impl, made by kernels on the library stream from CSR arrays
+// that already lie in device memory.  The input is checked first (indptr, then the columns of every row); the
+// host sees one 16-byte status record (the first violation, the number of stored entries) and nothing else.
+// The transpose is transpose_host's stable counting sort with C row chunks of about equal nonzeros in place of
+// the host threads: entries per (chunk, column) counted with integer atomics (sums: their order does not
+// matter), a scan over the chunks within each column and over the columns, then one single-wave workgroup per
+// chunk walks its rows in order with the lanes on the entries of ONE row -- a canonical row has distinct
+// columns, so no two lanes take the same cursor and every entry's place is fixed by the matrix alone.
+
+struct BuildStatus {
+  unsigned long long err;         // ~0: none; else (code << 56) | position, the smallest of all found
+  long long nnz;                  // indptr[n_rows]
+};
+enum { kErrFirst = 1, kErrDecreasing = 2, kErrLast = 3, kErrRange = 4, kErrOrder = 5 };
+constexpr unsigned long long kNoError = ~0ull;
+
+__device__ __forceinline__ void build_error(BuildStatus *st, int code, int64_t pos) {
+  atomicMin(&st->err, ((unsigned long long)code << 56) | (unsigned long long)pos);
+}
+
+// indptr[0] == 0, non-decreasing, the last entry within [0, cap] (cap: the entries the index and value arrays
+// can hold): then every indptr[r] lies in [0, cap] and the kernels below stay inside the arrays
+template <typename I>
+__global__ __launch_bounds__(kBlock) void spd_check_indptr(int64_t M, const I *__restrict__ ip, int64_t cap, BuildStatus *st) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r <= M; r += stride) {
+    if (r == 0 && ip[0] != 0) build_error(st, kErrFirst, 0);
+    if (r < M && ip[r + 1] < ip[r]) build_error(st, kErrDecreasing, r);
+    if (r == M) {
+      const long long last = (long long)ip[M];
+      st->nnz = last;
+      if (last < 0 || last > cap) build_error(st, kErrLast, 0);
+    }
+  }
+}
+
+// columns inside [0, N) and strictly ascending within each row: one wave per row; nothing is read when indptr
+// has failed its check
+template <typename I>
+__global__ __launch_bounds__(kBlock) void spd_check_columns(int64_t M, int64_t N, const I *__restrict__ ip,
+                                                            const I *__restrict__ ix, BuildStatus *st) {
+  if (*(volatile unsigned long long *)&st->err != kNoError) return;
+  const int lane = threadIdx.x & 63;
+  const int64_t waves = (int64_t)gridDim.x * (kBlock / 64);
+  for (int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); r < M; r += waves) {
+    const int64_t kb = (int64_t)ip[r], ke = (int64_t)ip[r + 1];
+    for (int64_t k = kb + lane; k < ke; k += 64) {
+      const int64_t c = (int64_t)ix[k];
+      if (c < 0 || c >= N) build_error(st, kErrRange, k);
+      else if (k > kb && (int64_t)ix[k - 1] >= c) build_error(st, kErrOrder, k);
+    }
+  }
+}
+
+template <typename I, typename O>
+__global__ __launch_bounds__(kBlock) void spd_convert_index(int64_t n, const I *__restrict__ in, O *__restrict__ out) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) out[i] = (O)in[i];
+}
+
+// row_at[g], g <= G: partition() on the device, one binary search per subgroup
+__global__ __launch_bounds__(kBlock) void spd_partition(int64_t rows, int64_t nnz, int64_t G, const int64_t *__restrict__ indptr,
+                                                        int32_t *__restrict__ row_at) {
+  const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (g > G) return;
+  const int64_t d = std::min(g * (int64_t)kItems, rows + nnz);
+  int64_t lo = 0, hi = rows;               // invariant: lo + indptr[lo] <= d
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) / 2;
+    if (mid + indptr[mid] <= d) lo = mid; else hi = mid - 1;
+  }
+  row_at[g] = (int32_t)lo;
+}
+
+// rstart[t], t <= C: the first row whose entries begin at or after nnz * t / C (rstart[C] = M)
+__global__ __launch_bounds__(kBlock) void spd_chunk_rows(int64_t M, int64_t nnz, int64_t C, const int64_t *__restrict__ ip,
+                                                         int64_t *__restrict__ rstart) {
+  const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (t > C) return;
+  if (t == C) { rstart[t] = M; return; }
+  const int64_t target = (nnz / C) * t + (nnz % C) * t / C;
+  int64_t lo = 0, hi = M;                  // lower_bound over ip[0 .. M]: ip[M] = nnz >= target
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) / 2;
+    if (ip[mid] < target) lo = mid + 1; else hi = mid;
+  }
+  rstart[t] = lo;
+}
+
+// cnt[t][c] = entries of chunk t in column c; S workgroups share the entries of one chunk
+__global__ __launch_bounds__(kBlock) void spd_count(int64_t N, int S, const int64_t *__restrict__ ip, const int64_t *__restrict__ rstart,
+                                                    const int32_t *__restrict__ ix, unsigned long long *cnt) {
+  const int64_t t = blockIdx.x / S;
+  const int s = (int)(blockIdx.x % S);
+  const int64_t kb = ip[rstart[t]], ke = ip[rstart[t + 1]];
+  unsigned long long *row = cnt + t * N;
+  for (int64_t k = kb + (int64_t)s * kBlock + threadIdx.x; k < ke; k += (int64_t)S * kBlock) atomicAdd(row + ix[k], 1ull);
+}
+
+__global__ __launch_bounds__(kBlock) void spd_column_totals(int64_t N, int64_t C, const int64_t *__restrict__ cnt, int64_t *__restrict__ tot) {
+  const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (j >= N) return;
+  int64_t s = 0;
+  for (int64_t t = 0; t < C; ++t) s += cnt[t * N + j];
+  tot[j] = s;
+}
+
+// cnt[t][j] becomes chunk t's first place in column j
+__global__ __launch_bounds__(kBlock) void spd_chunk_places(int64_t N, int64_t C, const int64_t *__restrict__ tp, int64_t *__restrict__ cnt) {
+  const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (j >= N) return;
+  int64_t o = tp[j];
+  for (int64_t t = 0; t < C; ++t) {
+    const int64_t c = cnt[t * N + j];
+    cnt[t * N + j] = o;
+    o += c;
+  }
+}
+
+// exclusive scan of n int64 into out[0 .. n] (out[n] = the sum): tile sums, one workgroup over the tile sums,
+// tiles again with their offsets
+constexpr int kScanPer = 4;
+constexpr int kScanTile = kBlock * kScanPer;
+
+__device__ __forceinline__ int64_t block_scan_exclusive(int64_t v, int64_t *sh, int64_t *total) {
+  const int t = threadIdx.x;
+  sh[t] = v;
+  __syncthreads();
+  for (int o = 1; o < kBlock; o <<= 1) {
+    const int64_t a = t >= o ? sh[t - o] : 0;
+    __syncthreads();
+    sh[t] += a;
+    __syncthreads();
+  }
+  const int64_t incl = sh[t];
+  *total = sh[kBlock - 1];
+  __syncthreads();
+  return incl - v;
+}
+
+__global__ __launch_bounds__(kBlock) void scan_tile_sums(int64_t n, const int64_t *__restrict__ in, int64_t *__restrict__ bsum) {
+  __shared__ int64_t sh[kBlock];
+  const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanPer;
+  int64_t s = 0;
+  for (int e = 0; e < kScanPer; ++e)
+    if (base + e < n) s += in[base + e];
+  int64_t total;
+  block_scan_exclusive(s, sh, &total);
+  if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(kBlock) void scan_of_sums(int64_t nb, int64_t *__restrict__ bsum) {
+  __shared__ int64_t sh[kBlock];
+  int64_t carry = 0;
+  for (int64_t base = 0; base < nb; base += kBlock) {
+    const int64_t i = base + threadIdx.x;
+    const int64_t v = i < nb ? bsum[i] : 0;
+    int64_t total;
+    const int64_t ex = block_scan_exclusive(v, sh, &total);
+    if (i < nb) bsum[i] = carry + ex;
+    carry += total;
+  }
+  if (threadIdx.x == 0) bsum[nb] = carry;
+}
+
+__global__ __launch_bounds__(kBlock) void scan_tiles(int64_t n, int64_t nb, const int64_t *__restrict__ in,
+                                                     const int64_t *__restrict__ bsum, int64_t *__restrict__ out) {
+  __shared__ int64_t sh[kBlock];
+  const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanPer;
+  int64_t v[kScanPer], s = 0;
+  for (int e = 0; e < kScanPer; ++e) {
+    v[e] = base + e < n ? in[base + e] : 0;
+    s += v[e];
+  }
+  int64_t total;
+  int64_t run = block_scan_exclusive(s, sh, &total) + bsum[blockIdx.x];
+  for (int e = 0; e < kScanPer; ++e) {
+    if (base + e < n) out[base + e] = run;
+    run += v[e];
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = bsum[nb];
+}
+
+__device__ __forceinline__ float dev_conj(float a) { return a; }
+__device__ __forceinline__ double dev_conj(double a) { return a; }
+__device__ __forceinline__ c32 dev_conj(c32 a) { return c32{a.re, -a.im}; }
+__device__ __forceinline__ c64 dev_conj(c64 a) { return c64{a.re, -a.im}; }
+
+// one single-wave workgroup per chunk: the rows in order, the lanes on the entries of one row (distinct
+// columns: distinct cursors); the barrier orders the cursor updates of one row before the reads of the next
+template <typename T>
+__global__ __launch_bounds__(64) void spd_scatter(const int64_t *__restrict__ ip, const int64_t *__restrict__ rstart,
+                                                  const int32_t *__restrict__ ix, const T *__restrict__ va, int64_t N, int64_t *cur_all,
+                                                  int32_t *__restrict__ tx, T *__restrict__ tv) {
+  const int64_t t = blockIdx.x;
+  int64_t *cur = cur_all + t * N;
+  const int64_t r1 = rstart[t + 1];
+  for (int64_t r = rstart[t]; r < r1; ++r) {
+    const int64_t kb = ip[r], ke = ip[r + 1];
+    if (kb == ke) continue;                // (the same decision in every lane)
+    for (int64_t k = kb + threadIdx.x; k < ke; k += 64) {
+      const int32_t c = ix[k];
+      const int64_t p = cur[c];
+      cur[c] = p + 1;
+      tx[p] = (int32_t)r;
+      tv[p] = dev_conj(va[k]);
+    }
+    __syncthreads();
+  }
+}
+
+static inline unsigned blocks_for(int64_t n, int64_t per, int64_t most) {
+  int64_t nb = (n + per - 1) / per;
+  if (nb > most) nb = most;
+  return (unsigned)(nb < 1 ? 1 : nb);
+}
+
+// bytes that can be read from p on inside its allocation (-1: the runtime does not know the pointer)
+static inline int64_t bytes_from(const void *p) {
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (!p || hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+    (void)hipGetLastError();
+    return -1;
+  }
+  return (int64_t)size - (int64_t)((const char *)p - (const char *)base);
+}
+
+int alloc_side(Side &s, int64_t rows, int64_t cols, int64_t nnz, int64_t es) {
+  s.rows = rows;
+  s.cols = cols;
+  s.nnz = nnz;
+  s.G = (rows + nnz + kItems - 1) / kItems;
+  RLH_HIP(hipMalloc(&s.indptr, 8 * (rows + 1)));
+  RLH_HIP(hipMalloc(&s.idx, std::max<int64_t>(4 * nnz, 4)));
+  RLH_HIP(hipMalloc(&s.val, std::max<int64_t>(es * nnz, 16)));
+  RLH_HIP(hipMalloc(&s.row_at, 4 * (s.G + 1)));
+  return 0;
+}
+
+struct BuildScratch {               // released when the build returns, however it returns
+  BuildStatus *status = nullptr;
+  int64_t *rstart = nullptr, *cnt = nullptr, *tot = nullptr, *bsum = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~BuildScratch() {
+    (void)hipFree(status); (void)hipFree(rstart); (void)hipFree(cnt); (void)hipFree(tot); (void)hipFree(bsum);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+};
+
+// the number of row chunks: about kChunkNnz entries each, the C x N table of places within the cap
+// (RLH_SPD_TABLE_BYTES, 512 MB as transpose_host caps its own), at least one
+constexpr int64_t kChunkNnz = 8192;
+int64_t chunk_count(int64_t nnz, int64_t N) {
+  const char *e = getenv("RLH_SPD_TABLE_BYTES");
+  int64_t cap = (e && *e) ? atoll(e) : (int64_t)512 << 20;
+  int64_t C = nnz / kChunkNnz + 1;
+  C = std::min<int64_t>(C, cap / (8 * (N + 1)));
+  return std::max<int64_t>(C, 1);
+}
+
+template <typename T, typename I>
+int create_device_impl(rlh_spd *h, int64_t M, int64_t N, const I *ip, const I *ix, const T *va) {
+  const int64_t es = sizeof(T);
+  hipStream_t st = ctx().stream;
+  const dim3 blk(kBlock);
+  BuildScratch w;
+  // ---- the checks: one status record comes back
+  int64_t cap = INT64_MAX;
+  const int64_t room_p = bytes_from(ip), room_i = bytes_from(ix), room_v = bytes_from(va);
+  RLH_REQUIRE(room_p < 0 || room_p >= (int64_t)sizeof(I) * (M + 1), "rlh_spd_create_device: the indptr array holds fewer than n_rows + 1 entries");
+  if (!ix || !va) cap = 0;
+  if (room_i >= 0) cap = std::min<int64_t>(cap, room_i / (int64_t)sizeof(I));
+  if (room_v >= 0) cap = std::min<int64_t>(cap, room_v / es);
+  RLH_HIP(hipMalloc(&w.status, sizeof(BuildStatus)));
+  BuildStatus hs{kNoError, 0};
+  RLH_HIP(hipMemcpyAsync(w.status, &hs, sizeof hs, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(spd_check_indptr<I>, dim3(blocks_for(M + 1, kBlock, 4096)), blk, 0, st, M, ip, cap, w.status);
+  hipLaunchKernelGGL(spd_check_columns<I>, dim3(blocks_for(M, kBlock / 64, 8192)), blk, 0, st, M, N, ip, ix, w.status);
+  RLH_HIP(hipGetLastError());
+  RLH_HIP(hipMemcpyAsync(&hs, w.status, sizeof hs, hipMemcpyDeviceToHost, st));
+  RLH_HIP(hipStreamSynchronize(st));
+  if (hs.err != kNoError) {
+    const int code = (int)(hs.err >> 56);
+    const long long pos = (long long)(hs.err & (((unsigned long long)1 << 56) - 1));
+    switch (code) {
+      case kErrFirst: set_error("rlh_spd_create_device: indptr[0] must be 0"); break;
+      case kErrDecreasing: set_error("rlh_spd_create_device: indptr decreases at row %lld", pos); break;
+      case kErrLast:
+        set_error("rlh_spd_create_device: indptr's last entry (%lld) is not the number of stored entries (the index "
+                  "and value arrays hold at most %lld)", hs.nnz, (long long)cap);
+        break;
+      case kErrRange: set_error("rlh_spd_create_device: column index out of range at entry %lld", pos); break;
+      default:
+        set_error("rlh_spd_create_device: the columns of a row must ascend strictly (no duplicates): entry %lld", pos);
+    }
+    return 1;
+  }
+  const int64_t nnz = hs.nnz;
+  // ---- A: indptr as int64, columns as int32, the values
+  Side &a = h->side[0], &b = h->side[1];
+  if (int rc = alloc_side(a, M, N, nnz, es)) return rc;
+  hipLaunchKernelGGL((spd_convert_index<I, int64_t>), dim3(blocks_for(M + 1, kBlock, 4096)), blk, 0, st, M + 1, ip, a.indptr);
+  if (nnz) {
+    hipLaunchKernelGGL((spd_convert_index<I, int32_t>), dim3(blocks_for(nnz, kBlock, 8192)), blk, 0, st, nnz, ix, a.idx);
+    RLH_HIP(hipMemcpyAsync(a.val, va, es * nnz, hipMemcpyDeviceToDevice, st));
+  }
+  hipLaunchKernelGGL(spd_partition, dim3(blocks_for(a.G + 1, kBlock, INT32_MAX)), blk, 0, st, M, nnz, a.G, a.indptr, a.row_at);
+  RLH_HIP(hipGetLastError());
+  // ---- A^H
+  if (int rc = alloc_side(b, N, M, nnz, es)) return rc;
+  const int64_t C = chunk_count(nnz, N);
+  const int64_t nb = (N + kScanTile - 1) / kScanTile;
+  RLH_HIP(hipMalloc(&w.rstart, 8 * (C + 1)));
+  RLH_HIP(hipMalloc(&w.cnt, std::max<int64_t>(8 * C * N, 8)));
+  RLH_HIP(hipMalloc(&w.tot, std::max<int64_t>(8 * N, 8)));
+  RLH_HIP(hipMalloc(&w.bsum, 8 * (nb + 1)));
+  RLH_HIP(hipEventCreate(&w.e0));
+  RLH_HIP(hipEventCreate(&w.e1));
+  RLH_HIP(hipEventRecord(w.e0, st));
+  RLH_HIP(hipMemsetAsync(w.cnt, 0, std::max<int64_t>(8 * C * N, 8), st));
+  hipLaunchKernelGGL(spd_chunk_rows, dim3(blocks_for(C + 1, kBlock, INT32_MAX)), blk, 0, st, M, nnz, C, a.indptr, w.rstart);
+  const int S = (int)std::max<int64_t>(1, std::min<int64_t>(64, 2048 / C));
+  if (nnz && N)
+    hipLaunchKernelGGL(spd_count, dim3((unsigned)(C * S)), blk, 0, st, N, S, a.indptr, w.rstart, a.idx, (unsigned long long *)w.cnt);
+  if (N) hipLaunchKernelGGL(spd_column_totals, dim3(blocks_for(N, kBlock, INT32_MAX)), blk, 0, st, N, C, w.cnt, w.tot);
+  if (nb) hipLaunchKernelGGL(scan_tile_sums, dim3((unsigned)nb), blk, 0, st, N, w.tot, w.bsum);
+  hipLaunchKernelGGL(scan_of_sums, dim3(1), blk, 0, st, nb, w.bsum);
+  if (nb) hipLaunchKernelGGL(scan_tiles, dim3((unsigned)nb), blk, 0, st, N, nb, w.tot, w.bsum, b.indptr);
+  else RLH_HIP(hipMemsetAsync(b.indptr, 0, 8, st));
+  if (N) hipLaunchKernelGGL(spd_chunk_places, dim3(blocks_for(N, kBlock, INT32_MAX)), blk, 0, st, N, C, b.indptr, w.cnt);
+  if (nnz && N)
+    hipLaunchKernelGGL(spd_scatter<T>, dim3((unsigned)C), dim3(64), 0, st, a.indptr, w.rstart, a.idx, (const T *)a.val, N, w.cnt,
+                       b.idx, (T *)b.val);
+  hipLaunchKernelGGL(spd_partition, dim3(blocks_for(b.G + 1, kBlock, INT32_MAX)), blk, 0, st, N, nnz, b.G, b.indptr, b.row_at);
+  RLH_HIP(hipGetLastError());
+  RLH_HIP(hipEventRecord(w.e1, st));
+  RLH_HIP(hipEventSynchronize(w.e1));
+  float ms = 0.f;
+  RLH_HIP(hipEventElapsedTime(&ms, w.e0, w.e1));
+  h->transpose_seconds = 1e-3 * ms;
+  return 0;
+}
+
+// sums of squares of the rows in float64, entry by entry in the stored order (what numpy.bincount forms on the
+// host: the same bits for real data), the modulus first, as numpy.abs forms it, then squared
+// (the compiler must not contract these into fused multiply-adds: NumPy rounds every product and every sum)
+__device__ __forceinline__ double mul_rounded(double a, double b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ double add_rounded(double a, double b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ double modulus2(float v) { return mul_rounded((double)v, (double)v); }
+__device__ __forceinline__ double modulus2(double v) { return mul_rounded(v, v); }
+// numpy.abs of complex64 step by step in float32 (NumPy's vectorised loop: larger * sqrt(fma(r, r, 1)), r = smaller /
+// larger; division, square root and the fused multiply-add are correctly rounded on both sides), so the host values
+// of SparseMatrix.__init__ -- which carry this float32 rounding of the modulus -- are reproduced, not approximated
+__device__ __forceinline__ double modulus2(c32 v) {
+#pragma clang fp contract(off)
+  const float re = fabsf(v.re), im = fabsf(v.im);
+  const float larger = fmaxf(re, im), smaller = fminf(re, im);
+  float m;
+  if (larger == 0.f || isinf(larger)) m = larger;
+  else {
+    const float r = smaller / larger;
+    m = sqrtf(fmaf(r, r, 1.0f)) * larger;
+  }
+  return mul_rounded((double)m, (double)m);
+}
+__device__ __forceinline__ double modulus2(c64 v) {     // the same steps in float64, as numpy.abs of complex128
+#pragma clang fp contract(off)
+  const double re = fabs(v.re), im = fabs(v.im);
+  const double larger = fmax(re, im), smaller = fmin(re, im);
+  double m;
+  if (larger == 0.0 || isinf(larger)) m = larger;
+  else {
+    const double r = smaller / larger;
+    m = sqrt(fma(r, r, 1.0)) * larger;
+  }
+  return mul_rounded(m, m);
+}
+__device__ __forceinline__ double part_max(float v) { return fabs((double)v); }
+__device__ __forceinline__ double part_max(double v) { return fabs(v); }
+__device__ __forceinline__ double part_max(c32 v) { return fmax(fabs((double)v.re), fabs((double)v.im)); }
+__device__ __forceinline__ double part_max(c64 v) { return fmax(fabs(v.re), fabs(v.im)); }
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void spd_row_sumsq_kernel(int64_t M, const int64_t *__restrict__ ip, const T *__restrict__ va,
+                                                               double *__restrict__ out) {
+  const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (r >= M) return;
+  double s = 0.0;
+  for (int64_t k = ip[r]; k < ip[r + 1]; ++k) s = add_rounded(s, modulus2(va[k]));
+  out[r] = s;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void spd_absmax_kernel(int64_t nnz, const T *__restrict__ va, double *__restrict__ out) {
+  __shared__ double red[kBlock / 64];
+  double mx = 0.0;
+  for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < nnz; k += (int64_t)gridDim.x * kBlock) mx = fmax(mx, part_max(va[k]));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_down(mx, o, 64));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int q = 1; q < kBlock / 64; ++q) mx = fmax(mx, red[q]);
+    out[blockIdx.x] = mx;
+  }
+}
+
+template <typename T> int row_sumsq_impl(const Side &s, double *d_out) {
+  hipLaunchKernelGGL(spd_row_sumsq_kernel<T>, dim3((unsigned)((s.rows + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx().stream, s.rows,
+                     s.indptr, (const T *)s.val, d_out);
+  return 0;
+}
+template <typename T> int absmax_impl(const Side &s, unsigned nb, double *d_out) {
+  hipLaunchKernelGGL(spd_absmax_kernel<T>, dim3(nb), dim3(kBlock), 0, ctx().stream, s.nnz, (const T *)s.val, d_out);
+  return 0;
+}
+
 // panel geometry: L lanes of 16 bytes hold one interleaved row of wp >= w elements (L a power of two)
 void panel_shape(int w, int64_t es, int *Lshift, int *wp) {
   const int pieces = (int)((w * es + 15) / 16);
@@ -419,6 +846,88 @@ extern "C" int rlh_spd_create(rlh_spd_t *ph, int dtype, int64_t n_rows, int64_t 
     return rc;
   }
   *ph = h;
+  return 0;
+}
+
+extern "C" int rlh_spd_create_device(rlh_spd_t *ph, int dtype, int64_t n_rows, int64_t n_cols, int index_bits,
+                                     const void *d_indptr, const void *d_indices, const void *d_values) {
+  if (int rc = require_ready()) return rc;
+  RLH_REQUIRE(ph, "rlh_spd_create_device: null handle pointer");
+  *ph = nullptr;
+  RLH_REQUIRE(dtype_valid(dtype), "rlh_spd_create_device: unknown dtype %d", dtype);
+  RLH_REQUIRE(index_bits == 32 || index_bits == 64, "rlh_spd_create_device: index_bits must be 32 or 64, got %d", index_bits);
+  RLH_REQUIRE(n_rows >= 0 && n_cols >= 0 && n_rows < INT32_MAX && n_cols < INT32_MAX,
+              "rlh_spd_create_device: sizes must lie in [0, 2^31 - 1)");
+  RLH_REQUIRE(d_indptr, "rlh_spd_create_device: null indptr");
+  rlh_spd *h = new rlh_spd();
+  h->dtype = dtype;
+  int rc = 1;
+#define RLH_SPD_BUILD(T)                                                                                              \
+  rc = index_bits == 32 ? create_device_impl<T, int32_t>(h, n_rows, n_cols, (const int32_t *)d_indptr,                \
+                                                         (const int32_t *)d_indices, (const T *)d_values)             \
+                        : create_device_impl<T, int64_t>(h, n_rows, n_cols, (const int64_t *)d_indptr,                \
+                                                         (const int64_t *)d_indices, (const T *)d_values)
+  switch (dtype) {
+    case RLH_S: RLH_SPD_BUILD(float); break;
+    case RLH_D: RLH_SPD_BUILD(double); break;
+    case RLH_C: RLH_SPD_BUILD(c32); break;
+    case RLH_Z: RLH_SPD_BUILD(c64); break;
+  }
+#undef RLH_SPD_BUILD
+  if (rc) {
+    rlh_spd_destroy(h);
+    return rc;
+  }
+  *ph = h;
+  return 0;
+}
+
+extern "C" int rlh_spd_row_sumsq(rlh_spd_t h, double *h_out) {
+  if (int rc = require_ready()) return rc;
+  RLH_REQUIRE(h, "rlh_spd_row_sumsq: null handle");
+  const Side &s = h->side[0];
+  if (s.rows == 0) return 0;
+  RLH_REQUIRE(h_out, "rlh_spd_row_sumsq: null output");
+  double *d = nullptr;
+  RLH_HIP(hipMalloc(&d, s.rows * sizeof(double)));
+  switch (h->dtype) {
+    case RLH_S: row_sumsq_impl<float>(s, d); break;
+    case RLH_D: row_sumsq_impl<double>(s, d); break;
+    case RLH_C: row_sumsq_impl<c32>(s, d); break;
+    case RLH_Z: row_sumsq_impl<c64>(s, d); break;
+  }
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx().stream);
+  if (e == hipSuccess) e = hipMemcpy(h_out, d, s.rows * sizeof(double), hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  RLH_HIP(e);
+  return 0;
+}
+
+extern "C" int rlh_spd_absmax(rlh_spd_t h, double *h_out) {
+  if (int rc = require_ready()) return rc;
+  RLH_REQUIRE(h && h_out, "rlh_spd_absmax: null handle or output");
+  *h_out = 0.0;
+  const Side &s = h->side[0];
+  if (s.nnz == 0) return 0;
+  const unsigned nb = blocks_for(s.nnz, kBlock, 1024);
+  double *d = nullptr;
+  RLH_HIP(hipMalloc(&d, nb * sizeof(double)));
+  switch (h->dtype) {
+    case RLH_S: absmax_impl<float>(s, nb, d); break;
+    case RLH_D: absmax_impl<double>(s, nb, d); break;
+    case RLH_C: absmax_impl<c32>(s, nb, d); break;
+    case RLH_Z: absmax_impl<c64>(s, nb, d); break;
+  }
+  std::vector<double> host(nb);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx().stream);
+  if (e == hipSuccess) e = hipMemcpy(host.data(), d, nb * sizeof(double), hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  RLH_HIP(e);
+  double mx = 0.0;
+  for (double v : host) mx = v > mx ? v : mx;
+  *h_out = mx;
   return 0;
 }
 

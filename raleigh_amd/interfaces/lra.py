@@ -65,6 +65,46 @@ def _eigh(a, single=False):
     return sla.eigh(a, driver='evd', overwrite_a=True, check_finite=False)
 
 
+def _tensor_input(A, arch):
+    """A torch tensor given as data: (matrix, like, None) when it lies in device memory -- the wrap of the dense, the
+    8-bit or the sparse operator made from it without a host trip, and the tensor whose device the results go back
+    to -- else (None, None, host): a CPU tensor as the ndarray view or the scipy.sparse.csr_matrix of its arrays
+    that the host path takes."""
+    from ..algebra.hip import device_data
+    A = device_data.prepare(A)
+    if device_data._on_device(A):
+        wrap = {'dense': AMatrix, 'bytes': ByteAMatrix, 'sparse': SparseAMatrix}[device_data.kind(A)]
+        return wrap(A, arch=arch), A, None
+    return None, None, device_data.to_host(A)
+
+
+def _as_matrix_like(A, arch):
+    """(matrix, like): the operator wrap of the data A and, when A is a torch tensor in device memory, that tensor
+    (else None: results are ndarrays)."""
+    from ..algebra.hip import device_data
+    if device_data.is_tensor(A):
+        matrix, like, A = _tensor_input(A, arch)
+        if matrix is not None:
+            return matrix, like
+    return _as_matrix(A, arch), None
+
+
+def _have_vectors(x, dtype=None, transpose=False, shape=None):
+    """One member of `have` (an ndarray, a CPU tensor or a device tensor) as Vectors of its rows (of its columns if
+    `transpose`), as `dtype`; a device tensor is copied on the device."""
+    from ..algebra.hip import Vectors, device_data
+    if device_data.is_tensor(x):
+        if shape is not None:
+            x = x.reshape(shape)
+        if device_data._on_device(x):
+            return device_data.vectors_from(x, dtype, transpose)
+        x = x.detach().resolve_conj().resolve_neg().numpy()
+    x = numpy.asarray(x) if dtype is None else numpy.asarray(x, dtype=dtype)
+    if shape is not None:
+        x = numpy.reshape(x, shape)
+    return Vectors(numpy.ascontiguousarray(x.T if transpose else x))
+
+
 def _as_matrix(A, arch):
     if hasattr(A, 'as_operator'):
         return A
@@ -92,17 +132,19 @@ class LowerRankApproximation:
         self.operator_time = 0.0
         self.sigma = None
         if have is not None:
-            mean, left, right = have
-            from ..algebra.hip import Vectors
-            right = numpy.ascontiguousarray(right)
-            left = numpy.ascontiguousarray(numpy.asarray(left, dtype=right.dtype).T)
-            if left.shape[0] != right.shape[0]:
+            mean, left, right = have       # ndarrays or torch tensors (device tensors are copied on the device)
+            from ..algebra.hip import device_data
+            right = right if device_data.is_tensor(right) else numpy.asarray(right)
+            left = left if device_data.is_tensor(left) else numpy.asarray(left)
+            if len(right.shape) != 2 or len(left.shape) != 2:
+                raise ValueError('have: trans and comps must be 2D')
+            if left.shape[1] != right.shape[0]:
                 raise ValueError('have: trans and comps disagree on the number of components')
-            self.__left_v = Vectors(left)
-            self.__right_v = Vectors(right)
+            self.__right_v = _have_vectors(right)
+            dtype = self.__right_v.data_type()
+            self.__left_v = _have_vectors(left, dtype, transpose=True)
             if mean is not None:
-                mean = numpy.ascontiguousarray(numpy.reshape(numpy.asarray(mean, dtype=right.dtype), (1, right.shape[1])))
-                self.__mean_v = Vectors(mean)
+                self.__mean_v = _have_vectors(mean, dtype, shape=(1, right.shape[1]))
             self.__rank = right.shape[0]
 
     # ------------------------------------------------------------------ compute

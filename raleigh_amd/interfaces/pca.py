@@ -281,7 +281,9 @@ class PartialSVD:
 
 
 def pca(A, npc=-1, tol=0, have=None, batch_size=None, verb=0, arch='hip', norm='f', mpc=-1, svtol=1e-3, opt=None):
-    '''PCA of the rows of A (a C-contiguous ndarray or a scipy.sparse matrix / array: the mean shift is then
+    '''PCA of the rows of A (a C-contiguous ndarray, a 2D torch tensor -- strided or torch.sparse_csr; one that lies
+    on the bound GPU is used where it is and mean, trans, comps come back as tensors on that device, a CPU tensor
+    takes the host path -- or a scipy.sparse matrix / array: the mean shift is then
     applied implicitly, A - e mean is never formed; an ndarray of uint8 / int8 stays bytes on the host and in
     HBM and the results are float32 -- `have` from a float32 run may be continued with 8-bit rows and the other
     way round; other integer types, bool, float16 and arrays that are not C-contiguous raise ValueError): returns (mean (1, n), trans (m, k), comps (k, n)) with
@@ -291,19 +293,24 @@ def pca(A, npc=-1, tol=0, have=None, batch_size=None, verb=0, arch='hip', norm='
     npc : number of components, or negative to use `tol`;
     tol : with npc < 0, stop when the norm of A_s - L R is at most tol times that of A_s (tol > 0) or -tol;
     norm : 'f' Frobenius, 's' largest singular value, 'm' largest row norm;
-    have : (mean0, trans0, comps0) of data A0 seen earlier -- the result then describes
+    have : (mean0, trans0, comps0) of data A0 seen earlier, ndarrays or tensors -- the result then describes
         numpy.concatenate((A0, A)); with neither npc nor tol, as many components as comps0 has;
-    batch_size : incremental PCA, `batch_size` rows of A in HBM at a time;
+    batch_size : incremental PCA, `batch_size` rows of A in HBM at a time (host data only: ValueError for a tensor);
     mpc : cap on the number of components when tol is used;
     svtol : singular value tolerance relative to the largest one.'''
-    from .lra import LowerRankApproximation, _as_matrix
+    from .lra import LowerRankApproximation, _as_matrix_like
+    from ..algebra.hip import device_data
     if norm not in ('f', 's', 'm'):
         raise ValueError('norm %s is not supported' % repr(norm))
     if opt is None:
         opt = Options()
+    like = None
+    if batch_size is not None and device_data.is_tensor(A):
+        raise ValueError('batch_size is not available for a torch tensor: incremental PCA takes host data')
+    if batch_size is None:
+        matrix, like = _as_matrix_like(A, arch)     # an ndarray, a tensor, or an AMatrix-like wrap, e.g. dist.ShardedAMatrix
     lra = LowerRankApproximation(have)
     if batch_size is None:
-        matrix = _as_matrix(A, arch)        # an ndarray, or an AMatrix-like wrap, e.g. dist.ShardedAMatrix
         if have is None:
             m, n = matrix.shape()
             lra.compute(matrix, opt=opt, rank=npc, tol=tol, norm=norm, max_rank=mpc, svtol=svtol, shift=True, verb=verb,
@@ -316,6 +323,11 @@ def pca(A, npc=-1, tol=0, have=None, batch_size=None, verb=0, arch='hip', norm='
         lra.icompute(A, batch_size, opt=opt, rank=npc, tol=tol, norm=norm, max_rank=mpc, svtol=svtol, shift=True,
                      verb=verb, arch=arch)
     pca.last = {'iterations': lra.iterations, 'operator_time': lra.operator_time, 'sigma': lra.sigma}
+    if like is not None:        # device data: device results, copied device to device out of the vectors
+        out = (device_data.export(lra.mean_v(), like), device_data.export(lra.left_v(), like, transpose=True),
+               device_data.export(lra.right_v(), like))
+        device_data.finish()
+        return out
     return lra.mean(), lra.left(), lra.right()
 
 

@@ -140,7 +140,10 @@ def truncated_svd(A, opt=None, nsv=-1, tol=0, norm='s', msv=-1, vtol=0, arch='hi
     A : a 2D ndarray of float32 / float64 / complex64 / complex128, or of uint8 / int8 (kept as bytes in HBM,
         the products on the bfloat16 matrix cores with float32 accumulation: u, sigma, vt come back as
         float32; every other integer type, bool and float16 raise ValueError), a scipy.sparse matrix or array
-        (the device operator of SparseAMatrix: never densified), or an AMatrix-like wrap;
+        (the device operator of SparseAMatrix: never densified), a 2D torch tensor (strided of one of these six
+        types, or torch.sparse_csr of the four float types with int32 / int64 indices: one that lies on the bound
+        GPU is used where it is, without a host trip, and u, sigma, vt come back as tensors on that device; a CPU
+        tensor takes the host path), or an AMatrix-like wrap;
     nsv : number of singular values, or negative to stop by `tol`;
     tol, norm : with nsv < 0, stop when the `norm` ('s', 'f' or 'm') of A - u diag(sigma) vt is at most
         tol times that of A (tol > 0) or -tol (tol < 0);
@@ -150,7 +153,14 @@ def truncated_svd(A, opt=None, nsv=-1, tol=0, norm='s', msv=-1, vtol=0, arch='hi
         raise ValueError('norm %s is not supported' % repr(norm))
     if opt is None:
         opt = Options()
-    if hasattr(A, 'as_operator'):
+    matrix = like = None
+    from ..algebra.hip import device_data
+    if device_data.is_tensor(A):    # a device tensor is used where it is; a CPU tensor goes on as host data
+        from .lra import _tensor_input
+        matrix, like, A = _tensor_input(A, arch)
+    if matrix is not None:
+        pass
+    elif hasattr(A, 'as_operator'):
         matrix = A
     elif scipy.sparse.issparse(A):
         matrix = SparseAMatrix(A, arch=arch)
@@ -187,4 +197,9 @@ def truncated_svd(A, opt=None, nsv=-1, tol=0, norm='s', msv=-1, vtol=0, arch='hi
     right.select(k)
     truncated_svd.last = {'iterations': psvd.iterations, 'operator_time': psvd.op_svd().time}
     # rows of vt = the right vectors themselves, as the reference returns them (v.T, truncated_svd.py:127)
+    if like is not None:        # device data: device results, copied device to device out of the vectors
+        out = (device_data.export(left, like, transpose=True), device_data.small(sigma[:k], like),
+               device_data.export(right, like))
+        device_data.finish()
+        return out
     return left.data().T, sigma[:k], right.data()
