@@ -194,6 +194,20 @@ int rlh_csr_create(rlh_csr_t *h, int dtype, int64_t n_rows, int64_t n_cols,
  * entries below the diagonal, if stored, are ignored.  Single-GPU operator (n_own = n). */
 int rlh_csr_create_upper(rlh_csr_t *h, int dtype, int64_t n, const int64_t *indptr,
                          const int32_t *indices, const void *values);
+/* The operator from a FULL 0-based CSR matrix that already lies in DEVICE memory (`index_bits` 32 or 64: the type
+ * of both index arrays), built by kernels on the library stream: no entry, index or value visits the host.  The
+ * input must be canonical -- indptr[0] == 0, indptr non-decreasing, its last entry the number of stored entries,
+ * columns inside [0, n_cols) and strictly ascending within each row -- and is checked on the device first: a
+ * violation returns non-zero, a message that names the first offending row and a null handle.  mirror_upper = 1
+ * (square matrices): the Hermitian operator defined by the upper triangle, as rlh_csr_create_upper defines it -- an
+ * entry (i, j), j < i, takes the conjugate of the stored (j, i).  The stored STRUCTURE must be symmetric: an entry
+ * without its partner on the other side is an error that names its row and column (the device build creates no
+ * entries).  The caller's arrays are never written and are not referenced after the call returns.  The result is
+ * an ordinary handle in the interleaved layout (2) or, where that one does not qualify, sliced ELL (0); the
+ * 1024-row windowed layout (1) is built from host arrays only: RLH_SPMM_FORMAT=sell|wide act as at rlh_csr_create,
+ * =well is an error here. */
+int rlh_csr_create_device(rlh_csr_t *h, int dtype, int64_t n_rows, int64_t n_cols, int index_bits,
+                          const void *d_indptr, const void *d_indices, const void *d_values, int mirror_upper);
 int rlh_csr_destroy(rlh_csr_t h);
 int rlh_csr_info(rlh_csr_t h, int64_t *n_rows, int64_t *n_cols, int64_t *nnz,
                  int64_t *device_bytes);

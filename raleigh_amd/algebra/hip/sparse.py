@@ -1,10 +1,16 @@
-"""MI355X sparse symmetric/Hermitian operator for SciPy sparse matrices.
+"""MI355X sparse symmetric/Hermitian operator for SciPy sparse matrices and for
+square ``torch.sparse_csr`` tensors that already lie on the bound GPU.
 
 Counterpart of raleigh/algebra/sparse_mkl.py:16-48 (SparseSymmetricMatrix) and
 :143-154 (Operator): same constructor argument (a SciPy sparse matrix whose
 UPPER triangle defines the symmetric/Hermitian operator, as MKL's 'SUNF'/'HUNF'
 descriptor does), same ``apply(x, y)``, but x and y are device Vectors and the
 product runs in librlhip.so (rlh_spmm) on a sliced-ELL copy of the full matrix.
+
+A tensor on the GPU becomes the operator without a host trip: the library builds
+the device layout from the tensor's three arrays by kernels (rlh_csr_create_device).
+It must store BOTH triangles (a symmetric structure): the device build creates no
+entries; the values below the diagonal are ignored, as on the host path.
 """
 
 import ctypes
@@ -13,6 +19,7 @@ import numpy as np
 import scipy.sparse as scs
 
 from ... import _lib
+from . import device_data
 
 
 def full_from_upper(matrix):
@@ -61,6 +68,37 @@ class CsrOperator:
                                                  csr.shape[1], _lib.host_ptr(indptr),
                                                  _lib.host_ptr(indices), _lib.host_ptr(values)))
         self._h = h
+
+    @classmethod
+    def from_tensor(cls, t, upper=False):
+        """The operator of a ``torch.sparse_csr`` tensor on the bound GPU (checked by ``operator_tensor`` or
+        ``device_data.prepare``), built on the device from its three arrays, which are read in place and not kept.
+        upper=True: the Hermitian operator defined by the upper triangle (rlh_csr_create_device, mirror_upper)."""
+        self = cls.__new__(cls)
+        dt = device_data.numpy_type(t)
+        if dt not in _lib.DTYPE_CODE:
+            raise ValueError('unsupported data type')
+        if upper and t.shape[0] != t.shape[1]:
+            raise ValueError('an operator given by its upper triangle is square and unsharded')
+        import torch
+        crow, col, val = t.crow_indices(), t.col_indices(), t.values()
+        if col.dtype != crow.dtype:                 # (torch takes mixed index types: both as the wider one)
+            crow, col = crow.to(torch.int64), col.to(torch.int64)
+        crow, col, val = crow.contiguous(), col.contiguous(), val.detach().resolve_conj().resolve_neg().contiguous()
+        # the conversions above may have launched work on torch's stream after device_data.prepare synchronised
+        # it; the library reads the arrays on its own stream, so that work has to be finished first
+        if val.is_cuda:
+            torch.cuda.current_stream(val.device).synchronize()
+        self._dtype = dt
+        self._shape = tuple(t.shape)
+        self._n_own = self._shape[1]
+        h = ctypes.c_void_p()
+        _lib.check(_lib.lib().rlh_csr_create_device(ctypes.byref(h), _lib.DTYPE_CODE[dt], self._shape[0], self._shape[1],
+                                                    32 if crow.element_size() == 4 else 64, crow.data_ptr(),
+                                                    col.data_ptr(), val.data_ptr(), 1 if upper else 0))
+        self._h = h
+        self._nnz = int(val.numel())
+        return self
 
     def __del__(self):
         h, self._h = getattr(self, '_h', None), None
@@ -140,11 +178,40 @@ class Bf16Block:
         _lib.check(_lib.lib().rlh_bf16_unpack(y._code, self.n, y.nvec(), self._buf.ptr, self.ld, y.data_ptr(), y.ld()))
 
 
+def operator_tensor(t):
+    """Checks a torch tensor given as the matrix of an eigenproblem and returns it prepared (device_data.prepare):
+    a square ``torch.sparse_csr`` tensor of a float or complex type, on the CPU or on the bound GPU."""
+    import torch
+    if t.layout != torch.sparse_csr:
+        raise ValueError('tensor layout %s not supported for a sparse operator: torch.sparse_csr (use to_sparse_csr())'
+                         % t.layout)
+    t = device_data.prepare(t)
+    if t.shape[0] != t.shape[1]:
+        raise ValueError('a square matrix is needed, got %d x %d' % tuple(t.shape))
+    return t
+
+
+def tensor_to_scipy(t):
+    """A sparse_csr tensor as a scipy.sparse.csr_matrix: ONE copy to the host if it lies on a GPU."""
+    return device_data.to_host(t.cpu())
+
+
 class SparseSymmetricMatrix:
 
     def __init__(self, matrix):
         # the UPPER triangle of `matrix` defines the operator (sparse_mkl.py:16-40); the library mirrors it, so the
         # matrix goes in as it comes (both triangles or one) and triu() is only taken if somebody asks for csr()
+        self.__tensor = None
+        if device_data.is_tensor(matrix):
+            t = operator_tensor(matrix)
+            if device_data._on_device(t):
+                # built on the device from the tensor's arrays; the tensor is kept (not copied) for csr()
+                self.__tensor = t
+                self.__given = None
+                self.__upper = None
+                self.__op = CsrOperator.from_tensor(t, upper=True)
+                return
+            matrix = device_data.to_host(t)
         try:
             self.__given = matrix.csr()
         except Exception:
@@ -153,12 +220,16 @@ class SparseSymmetricMatrix:
         self.__op = CsrOperator(self.__given, upper=True)
 
     def size(self):
-        return self.__given.shape[0]
+        return self.__op.shape()[0]
 
     def data_type(self):
-        return self.__given.data.dtype
+        return np.dtype(self.__op.data_type())
 
     def csr(self):
+        """The upper triangle as SciPy CSR.  Of an operator built from a GPU tensor: one copy of the matrix to the
+        host, made here on first use (only the direct factorisation asks for it)."""
+        if self.__upper is None and self.__tensor is not None:
+            self.__given = tensor_to_scipy(self.__tensor)
         if self.__upper is None:
             self.__upper = scs.triu(self.__given, format='csr')
             self.__upper.sort_indices()

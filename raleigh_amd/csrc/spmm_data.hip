@@ -19,6 +19,7 @@
 // The partition (the row at which each subgroup starts) depends on the matrix alone and is built with the
 // handle.  Every offset that scales with nnz or rows x vectors is 64-bit.
 #include "common.h"
+#include "device_build.h"
 
 #include <algorithm>
 #include <chrono>
@@ -28,7 +29,6 @@ namespace {
 
 constexpr int kItems = 256;       // merge-path items (row ends + nonzeros) per subgroup
 constexpr int kPanel = 64;        // vectors per panel: one interleaved row is at most 64 x 16 B
-constexpr int kBlock = 256;
 constexpr int kUnroll = 8;
 
 template <typename T> struct alignas(16) Pack {
@@ -335,33 +335,6 @@ int create_impl(rlh_spd *h, int64_t M, int64_t N, const int64_t *ip, const int32
 // chunk walks its rows in order with the lanes on the entries of ONE row -- a canonical row has distinct
 // columns, so no two lanes take the same cursor and every entry's place is fixed by the matrix alone.
 
-struct BuildStatus {
-  unsigned long long err;         // ~0: none; else (code << 56) | position, the smallest of all found
-  long long nnz;                  // indptr[n_rows]
-};
-enum { kErrFirst = 1, kErrDecreasing = 2, kErrLast = 3, kErrRange = 4, kErrOrder = 5 };
-constexpr unsigned long long kNoError = ~0ull;
-
-__device__ __forceinline__ void build_error(BuildStatus *st, int code, int64_t pos) {
-  atomicMin(&st->err, ((unsigned long long)code << 56) | (unsigned long long)pos);
-}
-
-// indptr[0] == 0, non-decreasing, the last entry within [0, cap] (cap: the entries the index and value arrays
-// can hold): then every indptr[r] lies in [0, cap] and the kernels below stay inside the arrays
-template <typename I>
-__global__ __launch_bounds__(kBlock) void spd_check_indptr(int64_t M, const I *__restrict__ ip, int64_t cap, BuildStatus *st) {
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r <= M; r += stride) {
-    if (r == 0 && ip[0] != 0) build_error(st, kErrFirst, 0);
-    if (r < M && ip[r + 1] < ip[r]) build_error(st, kErrDecreasing, r);
-    if (r == M) {
-      const long long last = (long long)ip[M];
-      st->nnz = last;
-      if (last < 0 || last > cap) build_error(st, kErrLast, 0);
-    }
-  }
-}
-
 // columns inside [0, N) and strictly ascending within each row: one wave per row; nothing is read when indptr
 // has failed its check
 template <typename I>
@@ -378,12 +351,6 @@ __global__ __launch_bounds__(kBlock) void spd_check_columns(int64_t M, int64_t N
       else if (k > kb && (int64_t)ix[k - 1] >= c) build_error(st, kErrOrder, k);
     }
   }
-}
-
-template <typename I, typename O>
-__global__ __launch_bounds__(kBlock) void spd_convert_index(int64_t n, const I *__restrict__ in, O *__restrict__ out) {
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) out[i] = (O)in[i];
 }
 
 // row_at[g], g <= G: partition() on the device, one binary search per subgroup
@@ -445,75 +412,6 @@ __global__ __launch_bounds__(kBlock) void spd_chunk_places(int64_t N, int64_t C,
   }
 }
 
-// exclusive scan of n int64 into out[0 .. n] (out[n] = the sum): tile sums, one workgroup over the tile sums,
-// tiles again with their offsets
-constexpr int kScanPer = 4;
-constexpr int kScanTile = kBlock * kScanPer;
-
-__device__ __forceinline__ int64_t block_scan_exclusive(int64_t v, int64_t *sh, int64_t *total) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int o = 1; o < kBlock; o <<= 1) {
-    const int64_t a = t >= o ? sh[t - o] : 0;
-    __syncthreads();
-    sh[t] += a;
-    __syncthreads();
-  }
-  const int64_t incl = sh[t];
-  *total = sh[kBlock - 1];
-  __syncthreads();
-  return incl - v;
-}
-
-__global__ __launch_bounds__(kBlock) void scan_tile_sums(int64_t n, const int64_t *__restrict__ in, int64_t *__restrict__ bsum) {
-  __shared__ int64_t sh[kBlock];
-  const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanPer;
-  int64_t s = 0;
-  for (int e = 0; e < kScanPer; ++e)
-    if (base + e < n) s += in[base + e];
-  int64_t total;
-  block_scan_exclusive(s, sh, &total);
-  if (threadIdx.x == 0) bsum[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(kBlock) void scan_of_sums(int64_t nb, int64_t *__restrict__ bsum) {
-  __shared__ int64_t sh[kBlock];
-  int64_t carry = 0;
-  for (int64_t base = 0; base < nb; base += kBlock) {
-    const int64_t i = base + threadIdx.x;
-    const int64_t v = i < nb ? bsum[i] : 0;
-    int64_t total;
-    const int64_t ex = block_scan_exclusive(v, sh, &total);
-    if (i < nb) bsum[i] = carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) bsum[nb] = carry;
-}
-
-__global__ __launch_bounds__(kBlock) void scan_tiles(int64_t n, int64_t nb, const int64_t *__restrict__ in,
-                                                     const int64_t *__restrict__ bsum, int64_t *__restrict__ out) {
-  __shared__ int64_t sh[kBlock];
-  const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanPer;
-  int64_t v[kScanPer], s = 0;
-  for (int e = 0; e < kScanPer; ++e) {
-    v[e] = base + e < n ? in[base + e] : 0;
-    s += v[e];
-  }
-  int64_t total;
-  int64_t run = block_scan_exclusive(s, sh, &total) + bsum[blockIdx.x];
-  for (int e = 0; e < kScanPer; ++e) {
-    if (base + e < n) out[base + e] = run;
-    run += v[e];
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = bsum[nb];
-}
-
-__device__ __forceinline__ float dev_conj(float a) { return a; }
-__device__ __forceinline__ double dev_conj(double a) { return a; }
-__device__ __forceinline__ c32 dev_conj(c32 a) { return c32{a.re, -a.im}; }
-__device__ __forceinline__ c64 dev_conj(c64 a) { return c64{a.re, -a.im}; }
-
 // one single-wave workgroup per chunk: the rows in order, the lanes on the entries of one row (distinct
 // columns: distinct cursors); the barrier orders the cursor updates of one row before the reads of the next
 template <typename T>
@@ -535,23 +433,6 @@ __global__ __launch_bounds__(64) void spd_scatter(const int64_t *__restrict__ ip
     }
     __syncthreads();
   }
-}
-
-static inline unsigned blocks_for(int64_t n, int64_t per, int64_t most) {
-  int64_t nb = (n + per - 1) / per;
-  if (nb > most) nb = most;
-  return (unsigned)(nb < 1 ? 1 : nb);
-}
-
-// bytes that can be read from p on inside its allocation (-1: the runtime does not know the pointer)
-static inline int64_t bytes_from(const void *p) {
-  hipDeviceptr_t base = nullptr;
-  size_t size = 0;
-  if (!p || hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
-    (void)hipGetLastError();
-    return -1;
-  }
-  return (int64_t)size - (int64_t)((const char *)p - (const char *)base);
 }
 
 int alloc_side(Side &s, int64_t rows, int64_t cols, int64_t nnz, int64_t es) {

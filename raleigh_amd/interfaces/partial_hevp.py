@@ -11,7 +11,8 @@ import time
 
 import numpy
 
-from ..algebra.hip import Vectors, SparseSymmetricMatrix
+from ..algebra.hip import Vectors, SparseSymmetricMatrix, device_data
+from ..algebra.hip.sparse import operator_tensor, tensor_to_scipy
 from ..algebra.hip.host_ops import SparseSymmetricSolver
 from ..algebra.hip.shift_invert import IterativeSymmetricSolver
 from ..core.solver import Problem, Solver, Options, DefaultConvergenceCriteria
@@ -31,6 +32,15 @@ def partial_hevp(A, B=None, T=None, buckling=False, sigma=0, which=6, tol=1e-4, 
     unless it already is.  With an inexact solver the converged pairs get a final Rayleigh-Ritz step
     with A itself, so that the eigenvalue errors are the square of the eigenvector errors.
 
+    `A` and `B` may be square ``torch.sparse_csr`` tensors (float32, float64, complex64, complex128; both
+    triangles stored).  On the bound GPU they become operators there, built by kernels from the tensor's arrays
+    (SparseSymmetricMatrix): in preconditioned mode (`T` given, or ``T=True`` for none) and with
+    ``solver=IterativeSymmetricSolver(...)`` nothing of the matrix goes to the host, and `x` comes back as an
+    ``(n, k)`` tensor on that GPU (`lmd` stays an ndarray: the solver holds it on the host anyway).  The direct
+    factorisation (no `T`, no `solver`) is a host algorithm: the tensor is copied to the host ONCE for it, while the
+    operator of the error estimate is still built on the device.  An IncompleteLU preconditioner is set up from a
+    SciPy matrix only.  A CPU tensor is taken as the SciPy matrix of its arrays (ndarrays come back).
+
     Returns (lmd, x, status): eigenvalues ascending, eigenvectors as columns, status as
     in the reference (0 success, 1 iteration limit, 2 no search directions, 3/4 some
     requested eigenvalues may not exist, <0 error).'''
@@ -39,6 +49,20 @@ def partial_hevp(A, B=None, T=None, buckling=False, sigma=0, which=6, tol=1e-4, 
     if buckling and sigma >= 0:
         raise ValueError('sigma must be negative in buckling mode')
     make_vectors = vectors if vectors is not None else (lambda n, data_type: Vectors(n, data_type=data_type))
+    # tensors: one on the GPU stays there (`like`: where the eigenvectors go back to), a CPU one is its SciPy matrix
+    like = None
+    if device_data.is_tensor(A):
+        A = operator_tensor(A)
+        if device_data.is_device_tensor(A):
+            like = A
+        else:
+            A = device_data.to_host(A)
+    if device_data.is_tensor(B):
+        B = operator_tensor(B)
+        if device_data.is_device_tensor(B):
+            like = B if like is None else like
+        else:
+            B = device_data.to_host(B)
     if B is not None:
         opB = SparseSymmetricMatrix(A if buckling else B)
     else:
@@ -58,19 +82,24 @@ def partial_hevp(A, B=None, T=None, buckling=False, sigma=0, which=6, tol=1e-4, 
                 if verb > -1:
                     print('setting up the iterative linear system solver...')
                 mk0 = (lambda n_, nv, data_type: _with(make_vectors(n_, data_type=data_type), nv)) if vectors is not None else None
-                solver.analyse(operator if operator is not None else A, sigma, B, vectors=mk0)
+                # (a GPU tensor goes in as the operator built from it: the solver then asks nothing of a host matrix)
+                a_ = operator if operator is not None else (SparseSymmetricMatrix(A) if device_data.is_tensor(A) else A)
+                solver.analyse(a_, sigma, B, vectors=mk0)
                 solver.factorize()
             n, dtype, sigma = solver.size(), solver.data_type(), solver.sigma()
         else:
             m, n = A.shape
             if m != n:
                 raise ValueError('the matrix must be square')
-            dtype = A.data.dtype.type
+            # the factorisation is a host algorithm: a GPU tensor is copied to the host once, here
+            A_host = tensor_to_scipy(A) if device_data.is_tensor(A) else A
+            B_host = tensor_to_scipy(B) if device_data.is_tensor(B) else B
+            dtype = A_host.data.dtype.type
             solver = SparseSymmetricSolver(dtype=dtype)
             if verb > -1:
                 print('setting up the linear system solver...')
             start = time.time()
-            solver.analyse(A, sigma, B)
+            solver.analyse(A_host, sigma, B_host)
             solver.factorize()
             # estimate the factorization error on three random vectors (partial_hevp.py:126-162)
             opA_ = SparseSymmetricMatrix(A)
@@ -177,6 +206,14 @@ def partial_hevp(A, B=None, T=None, buckling=False, sigma=0, which=6, tol=1e-4, 
     if inexact is not None and not buckling and eigenvectors.nvec() > 0:
         # (the per-pair records above are those of the iteration, in its order; the refined pairs are a rotation of them)
         lmd, ind = _refine(eigenvectors, inexact.operator(), opB, lmd)
+    if like is not None:
+        # the eigenvectors stay in HBM: copied device to device into a tensor, reordered there
+        x = device_data.export(eigenvectors, like, transpose=True)
+        device_data.finish()
+        if eigenvectors.nvec() > 0 and not numpy.array_equal(ind, numpy.arange(len(ind))):
+            import torch
+            x = x[:, torch.as_tensor(numpy.ascontiguousarray(ind), device=x.device)]
+        return lmd, x, status
     x = eigenvectors.data().T
     if eigenvectors.nvec() > 0:
         x = x[:, ind]
