@@ -139,13 +139,21 @@ class FakeLib:
     # ---- reductions
     def rlh_gram(self, code, n, mx, X, ldx, my, Y, ldy, d_out, h_out):
         self._count('gram')
+        if code not in _DT:
+            return self._fail('rlh_gram: unknown dtype %d' % code)
+        if n < 0 or mx < 0 or my < 0:
+            return self._fail('rlh_gram: negative size')
         if mx > 32768 or my > 32768:
             return self._fail('rlh_gram: more than 32768 vectors in a window')
         if mx == 0 or my == 0:
             return 0
+        if not (_addr(X) and _addr(Y)):
+            return self._fail('rlh_gram: null block pointer')
         if ldx < n or ldy < n:
             return self._fail('rlh_gram: leading dimension smaller than n')
-        g = ops.gram(_block(X, code, n, mx, ldx), _block(Y, code, n, my, ldy)).astype(_DT[code])
+        if not (_addr(d_out) or _addr(h_out)):
+            return self._fail('rlh_gram: no output buffer')
+        g = (ops.gram(_block(X, code, n, mx, ldx), _block(Y, code, n, my, ldy)) + 0).astype(_DT[code])     # (+ 0: no -0.0, as the kernels)
         for out in (d_out, h_out):
             if _addr(out):
                 _flat(out, _DT[code], my * mx)[:] = g.ravel()
@@ -155,11 +163,25 @@ class FakeLib:
 
     def rlh_gram_multi(self, code, n, nx, X, ldx, mx, ny, Y, ldy, my, d_out, h_out):
         self._count('gram_multi')
+        if code not in _DT:
+            return self._fail('rlh_gram_multi: unknown dtype %d' % code)
+        if not (1 <= nx <= 4 and 1 <= ny <= 4):
+            return self._fail('rlh_gram_multi: 1 to 4 blocks per window')
+        if n < 0 or any(a is None or (not hasattr(a, '__getitem__') and not _addr(a)) for a in (X, ldx, mx, Y, ldy, my)):
+            return self._fail('rlh_gram_multi: bad arguments')
+        for side, P, l, m, cnt in (('right', X, ldx, mx, nx), ('left', Y, ldy, my, ny)):
+            for k in range(cnt):
+                if _flat(m, np.int64, cnt)[k] < 1 or not _addr(P[k]) or _flat(l, np.int64, cnt)[k] < n:
+                    return self._fail('rlh_gram_multi: bad block %d of the %s window' % (k, side))
+        if _flat(mx, np.int64, nx).sum() > 32768 or _flat(my, np.int64, ny).sum() > 32768:
+            return self._fail('rlh_gram_multi: more than 32768 vectors in a window')
+        if not (_addr(d_out) or _addr(h_out)):
+            return self._fail('rlh_gram_multi: no output buffer')
         lx, mxs = _flat(ldx, np.int64, nx), _flat(mx, np.int64, nx)
         ly, mys = _flat(ldy, np.int64, ny), _flat(my, np.int64, ny)
         xs = np.concatenate([_block(X[k], code, n, int(mxs[k]), int(lx[k])) for k in range(nx)], axis=0)
         ys = np.concatenate([_block(Y[k], code, n, int(mys[k]), int(ly[k])) for k in range(ny)], axis=0)
-        g = ops.gram(xs, ys).astype(_DT[code])
+        g = (ops.gram(xs, ys) + 0).astype(_DT[code])
         for out in (d_out, h_out):
             if _addr(out):
                 _flat(out, _DT[code], g.size)[:] = g.ravel()
