@@ -226,10 +226,12 @@ int rlh_csr_layout(rlh_csr_t h, int *layout, int64_t *stored, double *staged_per
  * stacks (3.42 / 2.42 for the 7-point stencil on 215^3).  rlh_spmm on the whole operator uses the stacks when they exist;
  * RLH_SPMM_STACK=0 in the environment (create or call time) turns them off, =2 at create time builds them regardless. */
 int rlh_csr_stacks(rlh_csr_t h, int64_t *stacks, double *staged_per_row, double *staged_per_row_stacked);
-/* Whether rlh_spmm_cheb_bf16_part would take this operator: *ok = 1 if it is a float32 operator in the 1024-row windowed
- * layout whose staging groups all lie inside the column range and -- with a halo block (n_own < the column count: a row
- * shard) of leading dimension ldh -- n_own and ldh are multiples of 8 and the groups start on multiples of 8 columns, so
- * that the 2-byte staging stays on 16-byte pieces.  The layout conditions depend on the SHARD, so ranks of one row-sharded
+/* Whether rlh_spmm_cheb_bf16_part would take this operator: *ok = 1 if it is a float32 operator in the 256-row interleaved
+ * layout (built on the host or by rlh_csr_create_device; any shape: groups that reach past the last column are staged
+ * element by element) or in the 1024-row windowed layout with every staging group inside the column range, and -- with a
+ * halo block (n_own < the column count: a row shard) of leading dimension ldh -- n_own and ldh are multiples of 8 and the
+ * groups start on multiples of 8 columns, so that the 2-byte staging stays on 16-byte pieces.  0 for the sliced layout and
+ * for every other element type.  The layout conditions depend on the SHARD, so ranks of one row-sharded
  * operator can differ: callers agree on the answer (all-reduce MIN) BEFORE the first halo exchange of a bfloat16 step,
  * never by catching the launch's error afterwards. */
 int rlh_csr_bf16_ready(rlh_csr_t h, int64_t n_own, int64_t ldh, int *ok);
@@ -260,8 +262,11 @@ int rlh_spmm_cheb_part(rlh_csr_t h, int part, int64_t m, const void *Y, int64_t 
  * is a column-major array of 16-bit words, leading dimension in elements (a multiple of 8), base
  * 16-byte aligned.  pack: Y16 = bf16(scale * X) (round to nearest even) from a float32 / float64
  * block; unpack: back to float32 / float64.  rlh_spmm_cheb_bf16 is rlh_spmm_cheb on three bf16
- * blocks with float32 arithmetic against a square float32 operator in the windowed layout
- * (returns an error otherwise, the caller then stays in float32). */
+ * blocks with float32 arithmetic against a square float32 operator in the 1024-row windowed layout
+ * (and its stacks) or in the 256-row interleaved layout, wide_k 1 or 2 (rlh_csr_bf16_ready tells;
+ * an error otherwise -- sliced layout, other types --, the caller then stays in float32): t = A y
+ * accumulated in float32, p <- cy y + cp p + cb (b - t) rounded once to bfloat16 (nearest even);
+ * y and b, rows from n_rows on and vectors from m on are not written. */
 int rlh_bf16_pack(int src_dtype, int64_t n, int64_t m, const void *X, int64_t ldx, double scale,
                   void *Y16, int64_t ldy);
 int rlh_bf16_unpack(int dst_dtype, int64_t n, int64_t m, const void *X16, int64_t ldx, void *Y,

@@ -211,10 +211,12 @@ class ChebyshevPreconditioner:
             raise ValueError('degree must be at least 1')
         if storage not in (None, 'bf16'):
             raise ValueError("storage must be None or 'bf16'")
-        # storage='bf16' (with a float32 low_precision_op in the windowed device layout): the
-        # three work blocks are kept in bfloat16, arithmetic stays float32 -- half the bytes again
-        # per step; on lap3d 64^3 (degree 24) the iteration count goes from 27 to 28.  Ignored
-        # (float32 storage) where the operator cannot do it (sharded, sliced layout, complex).
+        # storage='bf16' (with a float32 low_precision_op in the 1024-row windowed or the 256-row
+        # interleaved device layout -- the latter is what an operator built from a GPU tensor, rows
+        # of more than 8 entries, FE matrices and bands get): the three work blocks are kept in
+        # bfloat16, arithmetic stays float32 -- half the bytes again per step; on lap3d 64^3
+        # (degree 24) the iteration count goes from 27 to 28.  Ignored (float32 storage) where the
+        # operator cannot do it (supports_bf16() false: sliced layout, float64, complex).
         self._bf16 = storage == 'bf16'
         self._work16 = None
         self._op = op if low_precision_op is None else low_precision_op

@@ -253,7 +253,9 @@ class SparseSymmetricMatrix:
 
     def cheb_step_bf16(self, m, y, p, b, cy, cp, cb):
         """The same step on bfloat16 blocks (Bf16Block), float32 arithmetic; float32 operators in
-        the windowed layout only (the library reports an error otherwise)."""
+        the 1024-row windowed or the 256-row interleaved layout -- built on the host or from a GPU
+        tensor -- and not in the sliced one (supports_bf16() tells; the library reports an error
+        otherwise)."""
         self.__op.cheb_step_bf16(m, y, p, b, cy, cp, cb)
 
     def supports_bf16(self):

@@ -145,6 +145,19 @@ __device__ __forceinline__ double sub_of(double a, double b) { return a - b; }
 __device__ __forceinline__ c32 sub_of(c32 a, c32 b) { return c32{a.re - b.re, a.im - b.im}; }
 __device__ __forceinline__ c64 sub_of(c64 a, c64 b) { return c64{a.re - b.re, a.im - b.im}; }
 
+// ---- bfloat16 work blocks of the fused Chebyshev step (spmm.hip, spmm_wide_bf16.hip)
+__device__ __forceinline__ float bf16_to_f32(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
+__device__ __forceinline__ unsigned short f32_to_bf16(float f) {           // round to nearest even
+  unsigned u = __float_as_uint(f);
+  u += 0x7FFFu + ((u >> 16) & 1u);
+  return (unsigned short)(u >> 16);
+}
+// p' = cy y + cp p + cb (b - t) with the roundings pinned (left to the compiler, the two kernels that share this step
+// contracted it differently: one bfloat16 ulp apart in 3 of 10^5 elements)
+__device__ __forceinline__ float cheb_update(float cy, float y, float cp, float p, float cb, float b, float t) {
+  return __fmaf_rn(cy, y, __fmaf_rn(cp, p, __fmul_rn(cb, __fsub_rn(b, t))));
+}
+
 // 16-byte pieces of a block of vectors: natural alignment of T on the global side (a group may
 // start on any column), 16 bytes on the LDS side.
 template <typename T, int EPL> struct VecU { T e[EPL]; };
@@ -485,5 +498,9 @@ int wide_spmm_c(rlh_csr *h, int part, int64_t m, const void *X, int64_t ldx, int
                 void *Y, int64_t ldy, const void *B, int64_t ldb, double cy, double cp, double cb);
 int wide_spmm_z(rlh_csr *h, int part, int64_t m, const void *X, int64_t ldx, int64_t n_own, const void *H, int64_t ldh,
                 void *Y, int64_t ldy, const void *B, int64_t ldb, double cy, double cp, double cb);
+// the fused Chebyshev step on bfloat16 blocks against a float32 handle in this layout (spmm_wide_bf16.hip; the caller,
+// rlh_spmm_cheb_bf16_part, has checked the blocks); H16 == nullptr: no halo block
+int wide_cheb_bf16(rlh_csr *h, int part, int64_t m, const void *Y16, int64_t ldy, int64_t n_own, const void *H16,
+                   int64_t ldh, void *P16, int64_t ldp, const void *B16, int64_t ldb, double cy, double cp, double cb);
 
 }  // namespace rlh

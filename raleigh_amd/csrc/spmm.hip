@@ -918,17 +918,7 @@ __global__ __launch_bounds__(1024) void well_stack_dma_kernel(const WellMeta *__
 //  * the row results of 8 vectors go through a wave-private LDS tile [vector][row] and come back
 //    as 8 consecutive rows of ONE vector per lane, so y, p, b are read and p is written as 16-byte
 //    pieces (one wave access = the wave's 64 rows x 8 vectors).
-__device__ __forceinline__ float bf16_to_f32(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
-__device__ __forceinline__ unsigned short f32_to_bf16(float f) {           // round to nearest even
-  unsigned u = __float_as_uint(f);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-// p' = cy y + cp p + cb (b - t) with the roundings pinned (left to the compiler, the two kernels that share this step
-// contracted it differently: one bfloat16 ulp apart in 3 of 10^5 elements)
-__device__ __forceinline__ float cheb_update(float cy, float y, float cp, float p, float cb, float b, float t) {
-  return __fmaf_rn(cy, y, __fmaf_rn(cp, p, __fmul_rn(cb, __fsub_rn(b, t))));
-}
+// (bf16_to_f32, f32_to_bf16 and cheb_update are in spmm.h: the interleaved layout's step shares them)
 struct alignas(16) Bf8 { unsigned short e[8]; };
 struct alignas(8) Bf8U { unsigned short e[8]; };                           // staging piece: groups start on multiples of 4 columns
 
@@ -2412,7 +2402,11 @@ int rlh_csr_info(rlh_csr_t h, int64_t *n_rows, int64_t *n_cols, int64_t *nnz, in
 
 }  // extern "C"
 // the layout conditions of the bfloat16 Chebyshev step: ONE definition for the launch and for rlh_csr_bf16_ready
-static inline bool bf16_layout_ok(const rlh_csr *h) { return h->dtype == RLH_S && h->well_blocks > 0 && h->well_inbounds; }
+// (the 1024-row windowed layout stages by 16-byte pieces only: every group inside the column range; the interleaved layout
+// has an element-wise staging for the others, so any float32 handle in it is taken)
+static inline bool bf16_layout_ok(const rlh_csr *h) {
+  return h->dtype == RLH_S && ((h->well_blocks > 0 && h->well_inbounds) || h->wide_blocks > 0);
+}
 static inline bool bf16_halo_ok(const rlh_csr *h, int64_t n_own, int64_t ldh) {
   return h->well_aligned && n_own % 8 == 0 && ldh % 8 == 0;
 }
@@ -2503,8 +2497,8 @@ int rlh_spmm_cheb_bf16_part(rlh_csr_t h, int part, int64_t m, const void *Y16, i
   RLH_REQUIRE(m >= 0, "rlh_spmm_cheb_bf16: negative block size");
   if (m == 0 || h->n_rows == 0) return 0;
   RLH_REQUIRE(bf16_layout_ok(h),
-              "rlh_spmm_cheb_bf16: needs a float32 operator in the 1024-row windowed layout (rows of at most 8 "
-              "entries) with every staging group inside the column range");
+              "rlh_spmm_cheb_bf16: needs a float32 operator in the 256-row interleaved layout or in the 1024-row windowed layout "
+              "(rows of at most 8 entries) with every staging group inside the column range; the sliced layout is not taken");
   RLH_REQUIRE(h->n_rows <= n_own && n_own <= h->n_cols, "rlh_spmm_cheb_bf16: the operator block must be square in its own rows");
   RLH_REQUIRE(n_own == h->n_cols || (H16 && bf16_halo_ok(h, n_own, ldh) && ((uintptr_t)H16 % 16) == 0),
               "rlh_spmm_cheb_bf16: a halo block needs n_own and ldh to be multiples of 8, a 16-byte aligned block "
@@ -2513,6 +2507,7 @@ int rlh_spmm_cheb_bf16_part(rlh_csr_t h, int part, int64_t m, const void *Y16, i
   RLH_REQUIRE(ldy >= n_own && ldp >= h->n_rows && ldb >= h->n_rows && ldy % 8 == 0 && ldp % 8 == 0 && ldb % 8 == 0 &&
                   ((uintptr_t)Y16 % 16) == 0 && ((uintptr_t)P16 % 16) == 0 && ((uintptr_t)B16 % 16) == 0,
               "rlh_spmm_cheb_bf16: blocks must be 16-byte aligned with leading dimensions that are multiples of 8");
+  if (h->wide_blocks > 0) return wide_cheb_bf16(h, part, m, Y16, ldy, n_own, H16, ldh, P16, ldp, B16, ldb, cy, cp, cb);
   Context &c = ctx();
   const unsigned short *Y = (const unsigned short *)Y16, *B = (const unsigned short *)B16;
   const unsigned short *H = H16 ? (const unsigned short *)H16 : Y;
