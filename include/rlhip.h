@@ -472,6 +472,43 @@ int rlh_bytes_row_sumsq(rlh_bytes_t h, double *h_out);
  * double; the call synchronises. */
 int rlh_bytes_absmax(rlh_bytes_t h, double *h_out);
 
+/* ---- factorised sparse approximate inverse preconditioner T = G^H G ~ A^-1 (Kolotilina-Yeremin), built and
+ *      applied on the device
+ *      (the reference preconditions with MKL's ILUT, factorised and applied on the host: raleigh/algebra/
+ *      mkl_wrap.py:279-347; its device counterpart here is the rlh_ilut_factor / rlh_sptrsv_* pair, whose application
+ *      is bound by the dependency chain of the triangular solves.  This one is set up by independent small dense
+ *      solves, one per row, and applied by two sparse products.)
+ * A: Hermitian positive definite, n x n, a full 0-based canonical CSR matrix (both triangles stored, columns
+ * strictly ascending within a row).  The UPPER triangle defines A: values stored below the diagonal are never read.
+ * Row i of G, lower triangular, lives on P_i = the stored columns j <= i of row i -- the `max_row` (1 .. 64) largest
+ * of them if there are more -- and is g = conj(y)^T / sqrt(y_k), S y = e_k, S = A[P_i, P_i], k = |P_i|: then
+ * S g^H = e_k / g_kk with g_kk > 0 and G^H G is Hermitian positive definite.  The local systems are solved in
+ * double / complex double for every dtype and G is rounded to the dtype once.  G is the same bits in every run,
+ * for either index type and from host or device arrays.  Needs rlh_init; n < 2^31 - 1.
+ * A violation returns non-zero, a message that names the entry point, what is wrong and the smallest offending row,
+ * and a null handle: indptr / columns not canonical; a row that does not store its diagonal; an entry below the
+ * diagonal whose partner above is not stored; a local block that is not positive definite.
+ * rlh_fsai_create_device: the three arrays lie in DEVICE memory (`index_bits` 32 or 64: the type of both index
+ * arrays); they are never written and not referenced after the return; nothing but status records visits the host.
+ * rlh_fsai_create: the same from HOST arrays, which are uploaded and take the same path. */
+typedef struct rlh_fsai *rlh_fsai_t;
+int rlh_fsai_create_device(rlh_fsai_t *h, int dtype, int64_t n, int index_bits, const void *d_indptr,
+                           const void *d_indices, const void *d_values, int max_row);
+int rlh_fsai_create(rlh_fsai_t *h, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
+                    const void *values, int max_row);
+/* Y = G^H (G X) for column-major DEVICE blocks of m vectors (leading dimensions >= n; Y may be X): two sparse
+ * products (the kernels of rlh_spd_apply, bit-identical from call to call) through an n x m workspace of the handle,
+ * which grows when a wider block than before arrives (that call synchronises the stream once); otherwise
+ * asynchronous on the library stream. */
+int rlh_fsai_apply(rlh_fsai_t h, int64_t m, const void *X, int64_t ldx, void *Y, int64_t ldy);
+/* size, stored entries of G, its longest row, the rows cut to max_row, device bytes held (G, G^H, their partitions,
+ * the workspaces) and the seconds the set-up took on the device (events around the whole build) */
+int rlh_fsai_info(rlh_fsai_t h, int64_t *n, int64_t *nnz, int64_t *longest_row, int64_t *truncated_rows,
+                  int64_t *device_bytes, double *setup_seconds);
+/* G as CSR in HOST arrays: n + 1 int64 row pointers, nnz int32 columns, nnz values of the dtype; synchronises */
+int rlh_fsai_get(rlh_fsai_t h, int64_t *indptr, int32_t *indices, void *values);
+int rlh_fsai_destroy(rlh_fsai_t h);
+
 /* ---- profiling aid: HIP-event time of the last `count` kernels ---- */
 int rlh_timer_start(void);
 int rlh_timer_stop(float *milliseconds);

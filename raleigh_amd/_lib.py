@@ -117,6 +117,13 @@ SIGNATURES = {
     'rlh_bytes_apply': [_p, _int, _i64, _p, _i64, _p, _i64, _p, _p],
     'rlh_bytes_row_sumsq': [_p, _p],
     'rlh_bytes_absmax': [_p, ctypes.POINTER(ctypes.c_double)],
+    'rlh_fsai_create_device': [ctypes.POINTER(_p), _int, _i64, _int, _p, _p, _p, _int],
+    'rlh_fsai_create': [ctypes.POINTER(_p), _int, _i64, _p, _p, _p, _int],
+    'rlh_fsai_apply': [_p, _i64, _p, _i64, _p, _i64],
+    'rlh_fsai_info': [_p, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                      ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)],
+    'rlh_fsai_get': [_p, _p, _p, _p],
+    'rlh_fsai_destroy': [_p],
     'rlh_timer_start': [],
     'rlh_timer_stop': [ctypes.POINTER(ctypes.c_float)],
 }

@@ -3,8 +3,10 @@
 The reference's preconditioner is MKL's ILUT applied on the host with two triangular solves
 per vector (raleigh/algebra/mkl_wrap.py:279-347).  `IncompleteLU` is its device counterpart:
 the same dual-threshold factorisation on the host once, the triangular solves on the whole
-block in HBM (`TriangularChain`: one persistent launch per application).  `ChebyshevPreconditioner`
-is what the survey lists as the alternative: a
+block in HBM (`TriangularChain`: one persistent launch per application).  `ApproximateInverse` is
+the preconditioner that is also SET UP on the device (a factorised sparse approximate inverse: one
+small dense solve per row, applied by two sparse products), from a SciPy matrix or a tensor on the GPU.
+`ChebyshevPreconditioner` is what the survey lists as the alternative: a
 fixed polynomial p(A) ~ A^-1 (Chebyshev semi-iteration on [lo, hi]) built only from the
 operator's ``apply`` and the block operations, so every block stays in HBM.  p(A) is
 symmetric positive definite for a positive definite A (0 < 1 - r(x) on (0, hi], r the
@@ -189,6 +191,136 @@ class IncompleteLU:
         if self._chain is None:
             self.factorize()
         self._chain.solve(x, y)
+
+
+class ApproximateInverse:
+    """Factorised sparse approximate inverse T = G^H G ~ A^-1 (Kolotilina-Yeremin) of a Hermitian positive definite
+    matrix, built AND applied on the device (rlh_fsai_*): the preconditioner for a matrix that already lies on the
+    GPU, and for matrices whose ILU application is bound by the triangular solves' dependency chain.
+
+    matrix: a SciPy sparse matrix, a square ``torch.sparse_csr`` tensor on the bound GPU (built by kernels from its
+    three arrays: nothing visits the host) or a CPU tensor (taken as its SciPy matrix).  Both triangles must be stored;
+    the UPPER one defines the operator, as for SparseSymmetricMatrix, and values below the diagonal are never read.
+
+    Row i of the lower triangular G lives on the stored columns j <= i of row i (the `max_row` largest of them, 1 ..
+    64, if there are more) and solves S g^H = e_k / g_kk, g_kk > 0, S the matching block of A, in double precision
+    whatever the storage type.  T is Hermitian positive definite by construction, as the solver requires;
+    ``apply`` is two sparse products.  It changes iteration counts relative to ILU, so runs using it are reported
+    separately from the reference's."""
+
+    def __init__(self, matrix, max_row=64):
+        from . import device_data
+        L = self._L = _lib.lib()                          # (the handle belongs to THIS library object)
+        self._h = None
+        max_row = int(max_row)
+        if not 1 <= max_row <= 64:
+            raise ValueError('max_row must lie in [1, 64], got %d' % max_row)
+        h = ctypes.c_void_p()
+        if device_data.is_tensor(matrix):
+            from .sparse import operator_tensor
+            t = operator_tensor(matrix)
+            if device_data._on_device(t):
+                import torch
+                self._dtype = device_data.numpy_type(t)
+                crow, col, val = t.crow_indices(), t.col_indices(), t.values()
+                if col.dtype != crow.dtype:                 # (torch takes mixed index types: both as the wider one)
+                    crow, col = crow.to(torch.int64), col.to(torch.int64)
+                crow, col = crow.contiguous(), col.contiguous()
+                val = val.detach().resolve_conj().resolve_neg().contiguous()
+                if val.is_cuda:                             # the conversions may have launched work on torch's stream
+                    torch.cuda.current_stream(val.device).synchronize()
+                self._n = int(t.shape[0])
+                self._nnz_a = int(val.numel())
+                self._create(L.rlh_fsai_create_device, 'rlh_fsai_create_device', h, _lib.DTYPE_CODE[self._dtype], self._n,
+                             32 if crow.element_size() == 4 else 64, ctypes.c_void_p(crow.data_ptr()),
+                             ctypes.c_void_p(col.data_ptr()), ctypes.c_void_p(val.data_ptr()), max_row)
+                self._finish(h)
+                return
+            matrix = device_data.to_host(t)
+        from .sparse_data import canonical_csr
+        a = canonical_csr(matrix)
+        if a.shape[0] != a.shape[1]:
+            raise ValueError('a square matrix is needed, got %d x %d' % a.shape)
+        self._dtype = a.dtype.type
+        self._n = int(a.shape[0])
+        self._nnz_a = int(a.nnz)
+        indptr = np.ascontiguousarray(a.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(a.indices, dtype=np.int32)
+        values = np.ascontiguousarray(a.data)
+        self._create(L.rlh_fsai_create, 'rlh_fsai_create', h, _lib.DTYPE_CODE[self._dtype], self._n, _lib.host_ptr(indptr),
+                     _lib.host_ptr(indices), _lib.host_ptr(values), max_row)
+        self._finish(h)
+
+    @staticmethod
+    def _create(fn, name, h, *args):
+        try:
+            _lib.check(fn(ctypes.byref(h), *args))
+        except _lib.RlhError as e:
+            text = str(e)
+            if ': %s:' % name not in text:                  # a HIP failure, not the library's own check
+                raise
+            if 'indptr' in text or 'column' in text:
+                raise ValueError('the sparse matrix is not canonical CSR: %s' % e)
+            raise
+
+    def _finish(self, h):
+        self._h = h
+        n, nnz, longest, cut, nbytes, sec = (ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(),
+                                             ctypes.c_int64(), ctypes.c_double())
+        _lib.check(self._L.rlh_fsai_info(h, ctypes.byref(n), ctypes.byref(nnz), ctypes.byref(longest), ctypes.byref(cut),
+                                         ctypes.byref(nbytes), ctypes.byref(sec)))
+        self.nnz = int(nnz.value)
+        self.longest_row = int(longest.value)
+        self.truncated_rows = int(cut.value)
+        self.setup_seconds = float(sec.value)
+        self.fill = self.nnz / float(max(self._nnz_a, 1))
+
+    def __del__(self):
+        h, self._h = getattr(self, '_h', None), None
+        if h:
+            try:
+                self._L.rlh_fsai_destroy(h)
+            except Exception:
+                pass
+
+    def size(self):
+        return self._n
+
+    def data_type(self):
+        return np.dtype(self._dtype)
+
+    def device_bytes(self):
+        """Device memory held: G, G^H, their partitions and the workspaces."""
+        nb = ctypes.c_int64()
+        _lib.check(self._L.rlh_fsai_info(self._h, None, None, None, None, ctypes.byref(nb), None))
+        return int(nb.value)
+
+    def csr(self):
+        """G as a SciPy CSR matrix (one copy to the host: rlh_fsai_get)."""
+        import scipy.sparse as scs
+        ip = np.zeros(self._n + 1, dtype=np.int64)
+        ix = np.zeros(max(self.nnz, 1), dtype=np.int32)
+        va = np.zeros(max(self.nnz, 1), dtype=self._dtype)
+        _lib.check(self._L.rlh_fsai_get(self._h, _lib.host_ptr(ip), _lib.host_ptr(ix), _lib.host_ptr(va)))
+        return scs.csr_matrix((va[:self.nnz], ix[:self.nnz], ip), shape=(self._n, self._n))
+
+    def algorithmic_bytes(self, m):
+        """Entries of G and of G^H (value + 4-byte column index) + one read and one write of a block per product."""
+        es = np.dtype(self._dtype).itemsize
+        return 2 * self.nnz * (es + 4) + 4 * self._n * m * es
+
+    def apply(self, x, y):
+        """y = G^H (G x) for Vectors windows of equal size (y may be x)."""
+        if hasattr(x, 'comm') or hasattr(y, 'comm'):
+            raise ValueError('ApproximateInverse does not take row-sharded blocks')
+        m = x.nvec()
+        if m != y.nvec():
+            raise ValueError('Numbers of input and output vectors differ')
+        if x.data_type() != self._dtype or y.data_type() != self._dtype:
+            raise ValueError('Matrix and vectors data types differ')
+        if x.dimension() != self._n or y.dimension() != self._n:
+            raise ValueError('Matrix and vectors dimensions incompatible')
+        _lib.check(self._L.rlh_fsai_apply(self._h, m, x.data_ptr(), x.ld(), y.data_ptr(), y.ld()))
 
 
 def gershgorin_upper_bound(matrix):

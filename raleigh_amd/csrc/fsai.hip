@@ -1,0 +1,565 @@
+// Factorised sparse approximate inverse (Kolotilina-Yeremin): T = G^H G ~ A^-1 for a Hermitian positive definite A
+// given as a full CSR matrix in device memory (rlh_fsai_*, include/rlhip.h).  The UPPER triangle defines A: no value
+// stored below the diagonal is ever read.
+//
+// Row i of G lives on P_i, the (at most max_row, the largest) stored columns j <= i of row i of A.  With S =
+// A[P_i, P_i] = R^H R (R upper triangular, positive diagonal) the row is g = conj(u), R u = e_k: then
+// S g^H = e_k / g_kk and g_kk = 1 / R_kk > 0.  Every local system is solved in double / complex double whatever the
+// storage type; G is rounded to it once, at the store.
+//
+// The build, all on the library stream:
+//   checks          indptr (device_build.h), the columns of every row, then per row: the diagonal is stored and every
+//                   entry below it has its partner above (fsai_count)
+//   pattern         kept entries per row, exclusive scans, columns of G and the rows of the two bins (fsai_fill)
+//   set-up          fsai_setup<T, 8>: 8 lanes per row for k <= 8, 32 rows per workgroup;  fsai_setup<T, 64>: one
+//                   single-wave workgroup per row for k <= 64.  The packed upper triangle of S (then R) lies in the
+//                   LDS: 64 * 65 / 2 complex doubles = 33 KB at most, so four such workgroups fit the 160 KB of a CU.
+//                   S is gathered by a binary search for column P[q] in the sorted row P[p], p <= q.
+//   operators       G and G^H as the two orientations of one sparse data operator (rlh_spd_create_device), which
+//                   copies G's arrays; the build's own are scratch and released.
+// A row is one lane group's work from the gather to the store: no floating-point atomics, no order that depends on
+// scheduling, G is the same bits in every run.  Lanes of a group exchange data through the LDS and shuffles only
+// within their own wave, at points every lane of the group reaches together (the trip counts are the group's k).
+// What a kernel finds wrong goes to the status record (code and the smallest position), never to a trap.
+#include "device_build.h"
+#include "spmm_data.h"
+
+#include <type_traits>
+
+namespace rlh {
+namespace {
+
+constexpr int kShort = 8;                      // rows of at most kShort kept entries: kShort lanes per row
+constexpr int kMaxRow = 64;
+constexpr int kSetupBlocksPerCu = 8;           // grid of a set-up kernel: at most this many workgroups per CU
+enum { kErrDiag = 6, kErrPartner = 7, kErrNotPd = 8 };
+
+struct FsaiStatus : BuildStatus {
+  long long row, col;                          // row and column of the entry a partner error points at
+  unsigned long long truncated;                // rows cut to max_row
+  int longest;                                 // longest row of G
+};
+
+__device__ __forceinline__ bool failed(const BuildStatus *st) { return *(const volatile unsigned long long *)&st->err != kNoError; }
+
+template <typename P, typename I>
+__global__ __launch_bounds__(kBlock) void fsai_check_columns(int64_t n, const P *__restrict__ ip, const I *__restrict__ ix,
+                                                             BuildStatus *st) {
+  if (failed(st)) return;
+  const int lane = threadIdx.x & 63;
+  const int64_t waves = (int64_t)gridDim.x * (kBlock / 64);
+  for (int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); r < n; r += waves) {
+    const int64_t kb = (int64_t)ip[r], ke = (int64_t)ip[r + 1];
+    for (int64_t k = kb + lane; k < ke; k += 64) {
+      const int64_t c = (int64_t)ix[k];
+      if (c < 0 || c >= n) build_error(st, kErrRange, r);
+      else if (k > kb && (int64_t)ix[k - 1] >= c) build_error(st, kErrOrder, r);
+    }
+  }
+}
+
+// the first entry of [lo, hi) whose column is not below c (rows are sorted)
+__device__ __forceinline__ int64_t lower_bound_col(const int32_t *__restrict__ ix, int64_t lo, int64_t hi, int64_t c) {
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) / 2;
+    if ((int64_t)ix[mid] < c) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// per row: the diagonal is stored, every entry below it has its partner; the kept entries (the last
+// min(lower, max_row) up to the diagonal) and where they begin in A's row
+__global__ __launch_bounds__(kBlock) void fsai_count(int64_t n, int max_row, const int64_t *__restrict__ ip,
+                                                     const int32_t *__restrict__ ix, int64_t *__restrict__ cnt,
+                                                     int64_t *__restrict__ is_short, int64_t *__restrict__ start, FsaiStatus *st) {
+  if (failed(st)) return;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+    const int64_t kb = ip[i], ke = ip[i + 1];
+    const int64_t d = lower_bound_col(ix, kb, ke, i);
+    int64_t k = 0;
+    if (d == ke || (int64_t)ix[d] != i) {
+      build_error(st, kErrDiag, i);
+    } else {
+      for (int64_t e = kb; e < d; ++e) {
+        const int64_t j = ix[e];
+        const int64_t je = ip[j + 1], f = lower_bound_col(ix, ip[j], je, i);
+        if (f == je || (int64_t)ix[f] != i) build_error(st, kErrPartner, e);
+      }
+      const int64_t lower = d + 1 - kb;
+      k = lower < max_row ? lower : max_row;
+      if (lower > max_row) atomicAdd(&st->truncated, 1ull);
+      atomicMax(&st->longest, (int)k);
+      start[i] = d + 1 - k;
+    }
+    cnt[i] = k;
+    is_short[i] = k <= kShort ? 1 : 0;
+  }
+}
+
+// row and column of the entry a partner error points at (one thread)
+__global__ void fsai_resolve_error(int64_t n, const int64_t *__restrict__ ip, const int32_t *__restrict__ ix, FsaiStatus *st) {
+  if (st->err == kNoError || (int)(st->err >> 56) != kErrPartner) return;
+  const int64_t k = (int64_t)(st->err & (((unsigned long long)1 << 56) - 1));
+  int64_t lo = 0, hi = n;                  // the last row with ip[row] <= k (ip[0] = 0 <= k < ip[n])
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) / 2;
+    if (ip[mid] <= k) lo = mid; else hi = mid;
+  }
+  st->row = lo;
+  st->col = (long long)ix[k];
+}
+
+// the columns of G and the rows of the two bins, each in ascending order (sp: the exclusive scan of is_short)
+__global__ __launch_bounds__(kBlock) void fsai_fill(int64_t n, const int32_t *__restrict__ ix, const int64_t *__restrict__ start,
+                                                    const int64_t *__restrict__ gp, const int64_t *__restrict__ sp,
+                                                    int32_t *__restrict__ gi, int32_t *__restrict__ rows_short,
+                                                    int32_t *__restrict__ rows_long) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+    const int64_t g0 = gp[i], k = gp[i + 1] - g0, a0 = start[i];
+    for (int64_t t = 0; t < k; ++t) gi[g0 + t] = ix[a0 + t];
+    const int64_t s = sp[i];
+    if (sp[i + 1] > s) rows_short[s] = (int32_t)i; else rows_long[i - s] = (int32_t)i;
+  }
+}
+
+// ---------------------------------------------------------------- the local solves, in double / complex double
+template <typename T> struct Wide { using type = double; };
+template <> struct Wide<c32> { using type = c64; };
+template <> struct Wide<c64> { using type = c64; };
+
+__device__ __forceinline__ double widen(float a) { return (double)a; }
+__device__ __forceinline__ double widen(double a) { return a; }
+__device__ __forceinline__ c64 widen(c32 a) { return c64{(double)a.re, (double)a.im}; }
+__device__ __forceinline__ c64 widen(c64 a) { return a; }
+__device__ __forceinline__ void narrow(double a, float *out) { *out = (float)a; }
+__device__ __forceinline__ void narrow(double a, double *out) { *out = a; }
+__device__ __forceinline__ void narrow(c64 a, c32 *out) { *out = c32{(float)a.re, (float)a.im}; }
+__device__ __forceinline__ void narrow(c64 a, c64 *out) { *out = a; }
+__device__ __forceinline__ double real_of(double a) { return a; }
+__device__ __forceinline__ double real_of(c64 a) { return a.re; }
+__device__ __forceinline__ double from_real(double r, double) { return r; }
+__device__ __forceinline__ c64 from_real(double r, c64) { return c64{r, 0.0}; }
+__device__ __forceinline__ double neg_of(double a) { return -a; }
+__device__ __forceinline__ c64 neg_of(c64 a) { return c64{-a.re, -a.im}; }
+__device__ __forceinline__ double div_real(double a, double r) { return a / r; }
+__device__ __forceinline__ c64 div_real(c64 a, double r) { return c64{a.re / r, a.im / r}; }
+__device__ __forceinline__ double shfl_of(double a, int src, int width) { return __shfl(a, src, width); }
+__device__ __forceinline__ c64 shfl_of(c64 a, int src, int width) { return c64{__shfl(a.re, src, width), __shfl(a.im, src, width)}; }
+
+// lanes of one wave that exchange data through the LDS: the LDS serves a wave's accesses in order; this keeps the
+// compiler from moving one across
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// d^(-1/2), correctly rounded up to the rarest of ties: 1 / sqrt(d) (two roundings) and one Newton step whose
+// residual 1 - d g^2 is formed without rounding d g (its low part comes from a fused multiply-add)
+__device__ __forceinline__ double inv_sqrt(double d) {
+  const double g = 1.0 / sqrt(d);
+  const double h = d * g, hl = fma(d, g, -h);
+  double e = fma(-h, g, 1.0);
+  e = fma(-hl, g, e);
+  return fma(0.5 * g, e, g);
+}
+
+__device__ __forceinline__ int tri_at(int p, int q) { return q * (q + 1) / 2 + p; }     // p <= q, packed by columns
+
+template <typename T, int LANES>
+__global__ __launch_bounds__(LANES == 64 ? 64 : kBlock) void fsai_setup(int64_t nlist, const int32_t *__restrict__ list,
+                                                                          const int64_t *__restrict__ ip,
+                                                                          const int32_t *__restrict__ ix, const T *__restrict__ va,
+                                                                          const int64_t *__restrict__ start,
+                                                                          const int64_t *__restrict__ gp, T *__restrict__ gv,
+                                                                          FsaiStatus *st) {
+  using D = typename Wide<T>::type;
+  constexpr int kThreads = LANES == 64 ? 64 : kBlock, kGroups = kThreads / LANES, kTri = LANES * (LANES + 1) / 2;
+  __shared__ D tri[kGroups][kTri];
+  __shared__ int32_t pcol[kGroups][LANES];
+  __shared__ int64_t pbeg[kGroups][LANES], pend[kGroups][LANES];
+  const int grp = threadIdx.x / LANES, lane = threadIdx.x % LANES;
+  D *R = tri[grp];
+  for (int64_t s = (int64_t)blockIdx.x * kGroups + grp; s < nlist; s += (int64_t)gridDim.x * kGroups) {
+    const int64_t i = list[s];
+    const int64_t g0 = gp[i], a0 = start[i];
+    const int k = (int)(gp[i + 1] - g0);             // 1 <= k <= LANES: the bins are made from these counts
+    wave_sync();                                     // (the row before this one is done with the LDS)
+    if (lane < k) {
+      const int32_t c = ix[a0 + lane];
+      pcol[grp][lane] = c;
+      pbeg[grp][lane] = ip[c];
+      pend[grp][lane] = ip[c + 1];
+    }
+    wave_sync();
+    // S[p, q], p <= q: the stored entry (P[p], P[q]) -- on or above the diagonal -- or 0
+    const int pairs = k * (k + 1) / 2;
+    for (int e = lane; e < pairs; e += LANES) {
+      int q = (int)((sqrtf(8.f * (float)e + 1.f) - 1.f) * 0.5f);
+      while (q * (q + 1) / 2 > e) --q;
+      while ((q + 1) * (q + 2) / 2 <= e) ++q;
+      const int p = e - q * (q + 1) / 2;
+      const int64_t c = pcol[grp][q], hi = pend[grp][p];
+      const int64_t f = lower_bound_col(ix, pbeg[grp][p], hi, c);
+      R[e] = (f < hi && (int64_t)ix[f] == c) ? widen(va[f]) : from_real(0.0, D());
+    }
+    wave_sync();
+    // S = R^H R row by row: lane q holds column q; R[p, q] = (S[p, q] - sum_{t < p} conj(R[t, p]) R[t, q]) / R[p, p]
+    bool bad = false;
+    double last = 1.0;
+    for (int p = 0; p < k; ++p) {
+      D acc = from_real(0.0, D());
+      const bool mine = lane >= p && lane < k;
+      if (mine) {
+        acc = R[tri_at(p, lane)];
+        for (int t = 0; t < p; ++t) fma_conj_acc(acc, R[tri_at(t, p)], neg_of(R[tri_at(t, lane)]));
+      }
+      const double d = __shfl(real_of(acc), p, LANES);
+      if (!(d > 0.0) || !(d < INFINITY)) { bad = true; break; }          // (the same decision in every lane of the group)
+      last = d;
+      const double r = sqrt(d);
+      if (mine) R[tri_at(p, lane)] = lane == p ? from_real(r, D()) : div_real(acc, r);
+      wave_sync();
+    }
+    if (bad) {
+      if (lane == 0) build_error(st, kErrNotPd, i);
+      continue;
+    }
+    // R u = e_k from the last column back; lane p carries the right-hand side of row p
+    D rhs = from_real(0.0, D()), u = from_real(0.0, D());
+    for (int q = k - 1; q >= 0; --q) {
+      const D cand = q == k - 1 ? from_real(inv_sqrt(last), D()) : div_real(rhs, real_of(R[tri_at(q, q)]));
+      const D uq = shfl_of(cand, q, LANES);
+      if (lane == q) u = uq;
+      if (lane < q) fma_acc(rhs, R[tri_at(lane, q)], neg_of(uq));
+    }
+    if (lane < k) narrow(dev_conj(u), &gv[g0 + lane]);
+  }
+}
+
+struct FsaiScratch {                // released when the build returns, however it returns
+  FsaiStatus *status = nullptr;
+  int64_t *indptr = nullptr, *cnt = nullptr, *is_short = nullptr, *start = nullptr, *gp = nullptr, *sp = nullptr, *bsum = nullptr;
+  int32_t *cols = nullptr, *gi = nullptr, *gp32 = nullptr, *rows_short = nullptr, *rows_long = nullptr;
+  void *gv = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~FsaiScratch() {
+    (void)hipFree(status); (void)hipFree(indptr); (void)hipFree(cnt); (void)hipFree(is_short); (void)hipFree(start);
+    (void)hipFree(gp); (void)hipFree(sp); (void)hipFree(bsum); (void)hipFree(cols); (void)hipFree(gi); (void)hipFree(gp32);
+    (void)hipFree(rows_short); (void)hipFree(rows_long); (void)hipFree(gv);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+};
+
+}  // namespace
+}  // namespace rlh
+
+struct rlh_fsai {
+  int dtype = 0;
+  int64_t n = 0, nnz = 0, truncated = 0;
+  int longest = 0;
+  double setup_seconds = 0;
+  rlh_spd_t spd = nullptr;          // G and G^H with their partitions
+  char *work = nullptr;             // the n x m block between the two products
+  int64_t work_bytes = 0;
+};
+
+namespace rlh {
+namespace {
+
+int exclusive_scan(int64_t n, const int64_t *in, int64_t *bsum, int64_t *out) {
+  hipStream_t st = ctx().stream;
+  const int64_t nb = (n + kScanTile - 1) / kScanTile;
+  hipLaunchKernelGGL(scan_tile_sums, dim3((unsigned)nb), dim3(kBlock), 0, st, n, in, bsum);
+  hipLaunchKernelGGL(scan_of_sums, dim3(1), dim3(kBlock), 0, st, nb, bsum);
+  hipLaunchKernelGGL(scan_tiles, dim3((unsigned)nb), dim3(kBlock), 0, st, n, nb, in, bsum, out);
+  RLH_HIP(hipGetLastError());
+  return 0;
+}
+
+// `name`: the entry point the messages speak for.  ip, ix, va: device arrays, n >= 1.
+template <typename T, typename P, typename I>
+int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T *va, int max_row) {
+  const int64_t es = sizeof(T), n = h->n;
+  hipStream_t st = ctx().stream;
+  const dim3 blk(kBlock);
+  FsaiScratch w;
+  RLH_HIP(hipEventCreate(&w.e0));
+  RLH_HIP(hipEventCreate(&w.e1));
+  RLH_HIP(hipEventRecord(w.e0, st));
+  // ---- the checks on the arrays as they came
+  int64_t cap = INT64_MAX;
+  const int64_t room_p = bytes_from(ip), room_i = bytes_from(ix), room_v = bytes_from(va);
+  RLH_REQUIRE(room_p < 0 || room_p >= (int64_t)sizeof(P) * (n + 1), "%s: the indptr array holds fewer than n + 1 entries", name);
+  if (!ix || !va) cap = 0;
+  if (room_i >= 0) cap = std::min<int64_t>(cap, room_i / (int64_t)sizeof(I));
+  if (room_v >= 0) cap = std::min<int64_t>(cap, room_v / es);
+  RLH_HIP(hipMalloc((void **)&w.status, sizeof(FsaiStatus)));
+  FsaiStatus hs{};
+  hs.err = kNoError;
+  RLH_HIP(hipMemcpyAsync(w.status, &hs, sizeof hs, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(spd_check_indptr<P>, dim3(blocks_for(n + 1, kBlock, 4096)), blk, 0, st, n, ip, cap, w.status);
+  hipLaunchKernelGGL((fsai_check_columns<P, I>), dim3(blocks_for(n, kBlock / 64, 8192)), blk, 0, st, n, ip, ix, w.status);
+  RLH_HIP(hipGetLastError());
+  RLH_HIP(hipMemcpyAsync(&hs, w.status, sizeof hs, hipMemcpyDeviceToHost, st));
+  RLH_HIP(hipStreamSynchronize(st));
+  auto report = [&](const FsaiStatus &s) {
+    const int code = (int)(s.err >> 56);
+    const long long pos = (long long)(s.err & (((unsigned long long)1 << 56) - 1));
+    switch (code) {
+      case kErrFirst: set_error("%s: indptr[0] must be 0", name); break;
+      case kErrDecreasing: set_error("%s: indptr decreases at row %lld", name, pos); break;
+      case kErrLast:
+        set_error("%s: indptr's last entry (%lld) is not the number of stored entries (the index and value arrays "
+                  "hold at most %lld)", name, s.nnz, (long long)cap);
+        break;
+      case kErrRange: set_error("%s: column index out of range in row %lld", name, pos); break;
+      case kErrOrder: set_error("%s: the columns of row %lld must ascend strictly (no duplicates)", name, pos); break;
+      case kErrDiag: set_error("%s: row %lld does not store its diagonal entry", name, pos); break;
+      case kErrPartner:
+        set_error("%s: the stored structure is not symmetric: entry (%lld, %lld) has no partner (%lld, %lld); the "
+                  "device build creates no entries", name, s.row, s.col, s.col, s.row);
+        break;
+      default: set_error("%s: local block of row %lld is not positive definite", name, pos);
+    }
+    return 1;
+  };
+  if (hs.err != kNoError) return report(hs);
+  const int64_t nnz = hs.nnz;
+  // ---- indptr as int64 and columns as int32 (the caller's own arrays where they already are)
+  const int64_t *ip64;
+  const int32_t *ix32;
+  if constexpr (std::is_same<P, int64_t>::value) {
+    ip64 = ip;
+  } else {
+    RLH_HIP(hipMalloc((void **)&w.indptr, (size_t)(n + 1) * sizeof(int64_t)));
+    hipLaunchKernelGGL((spd_convert_index<P, int64_t>), dim3(blocks_for(n + 1, kBlock, 4096)), blk, 0, st, n + 1, ip, w.indptr);
+    ip64 = w.indptr;
+  }
+  if constexpr (std::is_same<I, int32_t>::value) {
+    ix32 = ix;
+  } else {
+    RLH_HIP(hipMalloc((void **)&w.cols, (size_t)std::max<int64_t>(4 * nnz, 4)));
+    if (nnz) hipLaunchKernelGGL((spd_convert_index<I, int32_t>), dim3(blocks_for(nnz, kBlock, 8192)), blk, 0, st, nnz, ix, w.cols);
+    ix32 = w.cols;
+  }
+  // ---- the pattern
+  const int64_t nb = (n + kScanTile - 1) / kScanTile;
+  RLH_HIP(hipMalloc((void **)&w.cnt, (size_t)n * 8));
+  RLH_HIP(hipMalloc((void **)&w.is_short, (size_t)n * 8));
+  RLH_HIP(hipMalloc((void **)&w.start, (size_t)n * 8));
+  RLH_HIP(hipMalloc((void **)&w.gp, (size_t)(n + 1) * 8));
+  RLH_HIP(hipMalloc((void **)&w.sp, (size_t)(n + 1) * 8));
+  RLH_HIP(hipMalloc((void **)&w.bsum, (size_t)(nb + 1) * 8));
+  hipLaunchKernelGGL(fsai_count, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, max_row, ip64, ix32, w.cnt, w.is_short, w.start,
+                     w.status);
+  hipLaunchKernelGGL(fsai_resolve_error, dim3(1), dim3(1), 0, st, n, ip64, ix32, w.status);
+  if (int rc = exclusive_scan(n, w.cnt, w.bsum, w.gp)) return rc;
+  if (int rc = exclusive_scan(n, w.is_short, w.bsum, w.sp)) return rc;
+  int64_t tot[2] = {0, 0};
+  RLH_HIP(hipMemcpyAsync(&hs, w.status, sizeof hs, hipMemcpyDeviceToHost, st));
+  RLH_HIP(hipMemcpyAsync(&tot[0], w.gp + n, 8, hipMemcpyDeviceToHost, st));
+  RLH_HIP(hipMemcpyAsync(&tot[1], w.sp + n, 8, hipMemcpyDeviceToHost, st));
+  RLH_HIP(hipStreamSynchronize(st));
+  if (hs.err != kNoError) return report(hs);
+  const int64_t gnnz = tot[0], n_short = tot[1], n_long = n - n_short;
+  h->nnz = gnnz;
+  h->truncated = (int64_t)hs.truncated;
+  h->longest = hs.longest;
+  RLH_HIP(hipMalloc((void **)&w.gi, (size_t)gnnz * 4));
+  RLH_HIP(hipMalloc(&w.gv, (size_t)gnnz * es));
+  RLH_HIP(hipMalloc((void **)&w.rows_short, (size_t)std::max<int64_t>(n_short, 1) * 4));
+  RLH_HIP(hipMalloc((void **)&w.rows_long, (size_t)std::max<int64_t>(n_long, 1) * 4));
+  hipLaunchKernelGGL(fsai_fill, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, ix32, w.start, w.gp, w.sp, w.gi, w.rows_short,
+                     w.rows_long);
+  // ---- the rows
+  const int64_t most = (int64_t)ctx().num_cu * kSetupBlocksPerCu;
+  if (n_short)
+    hipLaunchKernelGGL((fsai_setup<T, kShort>), dim3(blocks_for(n_short, kBlock / kShort, most)), blk, 0, st, n_short, w.rows_short,
+                       ip64, ix32, va, w.start, w.gp, (T *)w.gv, w.status);
+  if (n_long)
+    hipLaunchKernelGGL((fsai_setup<T, kMaxRow>), dim3(blocks_for(n_long, 1, most)), dim3(64), 0, st, n_long, w.rows_long, ip64, ix32,
+                       va, w.start, w.gp, (T *)w.gv, w.status);
+  RLH_HIP(hipGetLastError());
+  RLH_HIP(hipMemcpyAsync(&hs, w.status, sizeof hs, hipMemcpyDeviceToHost, st));
+  RLH_HIP(hipStreamSynchronize(st));
+  if (hs.err != kNoError) return report(hs);
+  // ---- G and G^H as one sparse data operator (it copies the arrays: 32-bit row pointers where they can hold nnz)
+  int rc;
+  if (gnnz < INT32_MAX) {
+    RLH_HIP(hipMalloc((void **)&w.gp32, (size_t)(n + 1) * 4));
+    hipLaunchKernelGGL((spd_convert_index<int64_t, int32_t>), dim3(blocks_for(n + 1, kBlock, 4096)), blk, 0, st, n + 1, w.gp, w.gp32);
+    RLH_HIP(hipGetLastError());
+    rc = rlh_spd_create_device(&h->spd, h->dtype, n, n, 32, w.gp32, w.gi, w.gv);
+  } else {
+    RLH_HIP(hipFree(w.cols));
+    w.cols = nullptr;
+    int64_t *gi64 = nullptr;
+    RLH_HIP(hipMalloc((void **)&gi64, (size_t)gnnz * 8));
+    hipLaunchKernelGGL((spd_convert_index<int32_t, int64_t>), dim3(blocks_for(gnnz, kBlock, 8192)), blk, 0, st, gnnz, w.gi, gi64);
+    rc = rlh_spd_create_device(&h->spd, h->dtype, n, n, 64, w.gp, gi64, w.gv);
+    (void)hipFree(gi64);
+  }
+  if (rc) return rc;
+  RLH_HIP(hipEventRecord(w.e1, st));
+  RLH_HIP(hipEventSynchronize(w.e1));        // the caller's arrays and the scratch are not referenced after the return
+  float ms = 0.f;
+  RLH_HIP(hipEventElapsedTime(&ms, w.e0, w.e1));
+  h->setup_seconds = 1e-3 * ms;
+  return 0;
+}
+
+template <typename P, typename I>
+int fsai_build_any(rlh_fsai *h, const char *name, const void *ip, const void *ix, const void *va, int max_row) {
+  switch (h->dtype) {
+    case RLH_S: return fsai_build<float, P, I>(h, name, (const P *)ip, (const I *)ix, (const float *)va, max_row);
+    case RLH_D: return fsai_build<double, P, I>(h, name, (const P *)ip, (const I *)ix, (const double *)va, max_row);
+    case RLH_C: return fsai_build<c32, P, I>(h, name, (const P *)ip, (const I *)ix, (const c32 *)va, max_row);
+    case RLH_Z: return fsai_build<c64, P, I>(h, name, (const P *)ip, (const I *)ix, (const c64 *)va, max_row);
+  }
+  return 1;
+}
+
+int check_create_args(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, const void *indptr, int max_row) {
+  RLH_REQUIRE(ph != nullptr, "%s: null handle pointer", name);
+  *ph = nullptr;
+  RLH_REQUIRE(dtype_valid(dtype), "%s: unknown dtype %d", name, dtype);
+  RLH_REQUIRE(n >= 0 && n < INT32_MAX, "%s: the size must lie in [0, 2^31 - 1)", name);
+  RLH_REQUIRE(max_row >= 1 && max_row <= kMaxRow, "%s: max_row must lie in [1, %d], got %d", name, kMaxRow, max_row);
+  RLH_REQUIRE(indptr, "%s: null indptr", name);
+  return 0;
+}
+
+}  // namespace
+}  // namespace rlh
+
+using namespace rlh;
+
+extern "C" int rlh_fsai_create_device(rlh_fsai_t *ph, int dtype, int64_t n, int index_bits, const void *d_indptr,
+                                      const void *d_indices, const void *d_values, int max_row) {
+  const char *name = "rlh_fsai_create_device";
+  if (int rc = require_ready()) return rc;
+  if (int rc = check_create_args(name, ph, dtype, n, d_indptr, max_row)) return rc;
+  RLH_REQUIRE(index_bits == 32 || index_bits == 64, "%s: index_bits must be 32 or 64, got %d", name, index_bits);
+  rlh_fsai *h = new rlh_fsai();
+  h->dtype = dtype;
+  h->n = n;
+  int rc = 0;
+  if (n > 0)
+    rc = index_bits == 32 ? fsai_build_any<int32_t, int32_t>(h, name, d_indptr, d_indices, d_values, max_row)
+                          : fsai_build_any<int64_t, int64_t>(h, name, d_indptr, d_indices, d_values, max_row);
+  if (rc) {
+    rlh_fsai_destroy(h);
+    return rc;
+  }
+  *ph = h;
+  return 0;
+}
+
+extern "C" int rlh_fsai_create(rlh_fsai_t *ph, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
+                               const void *values, int max_row) {
+  const char *name = "rlh_fsai_create";
+  if (int rc = require_ready()) return rc;
+  if (int rc = check_create_args(name, ph, dtype, n, indptr, max_row)) return rc;
+  // what decides how much is uploaded is checked here; everything else by the kernels, as for device arrays
+  RLH_REQUIRE(indptr[0] == 0, "%s: indptr[0] must be 0", name);
+  for (int64_t r = 0; r < n; ++r) RLH_REQUIRE(indptr[r + 1] >= indptr[r], "%s: indptr decreases at row %lld", name, (long long)r);
+  const int64_t nnz = indptr[n], es = dtype_size(dtype);
+  RLH_REQUIRE(nnz == 0 || (indices && values), "%s: null indices or values", name);
+  rlh_fsai *h = new rlh_fsai();
+  h->dtype = dtype;
+  h->n = n;
+  int rc = 0;
+  if (n > 0) {
+    int64_t *d_ip = nullptr;
+    int32_t *d_ix = nullptr;
+    void *d_va = nullptr;
+    hipError_t e = hipMalloc((void **)&d_ip, (size_t)(n + 1) * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_ix, (size_t)std::max<int64_t>(4 * nnz, 4));
+    if (e == hipSuccess) e = hipMalloc(&d_va, (size_t)std::max<int64_t>(es * nnz, 16));
+    if (e == hipSuccess) e = hipMemcpy(d_ip, indptr, (size_t)(n + 1) * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess && nnz) e = hipMemcpy(d_ix, indices, (size_t)nnz * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && nnz) e = hipMemcpy(d_va, values, (size_t)(nnz * es), hipMemcpyHostToDevice);
+    if (e == hipSuccess) rc = fsai_build_any<int64_t, int32_t>(h, name, d_ip, d_ix, d_va, max_row);
+    (void)hipFree(d_ip);
+    (void)hipFree(d_ix);
+    (void)hipFree(d_va);
+    if (e != hipSuccess) {
+      rlh_fsai_destroy(h);
+      RLH_HIP(e);
+    }
+  }
+  if (rc) {
+    rlh_fsai_destroy(h);
+    return rc;
+  }
+  *ph = h;
+  return 0;
+}
+
+extern "C" int rlh_fsai_destroy(rlh_fsai_t h) {
+  if (!h) return 0;
+  if (h->work) (void)hipStreamSynchronize(ctx().stream);
+  if (h->spd) rlh_spd_destroy(h->spd);
+  (void)hipFree(h->work);
+  delete h;
+  return 0;
+}
+
+extern "C" int rlh_fsai_info(rlh_fsai_t h, int64_t *n, int64_t *nnz, int64_t *longest_row, int64_t *truncated_rows,
+                             int64_t *device_bytes, double *setup_seconds) {
+  RLH_REQUIRE(h, "rlh_fsai_info: null handle");
+  if (n) *n = h->n;
+  if (nnz) *nnz = h->nnz;
+  if (longest_row) *longest_row = h->longest;
+  if (truncated_rows) *truncated_rows = h->truncated;
+  if (device_bytes) {
+    int64_t held = 0;
+    if (h->spd)
+      if (int rc = rlh_spd_info(h->spd, nullptr, nullptr, nullptr, &held)) return rc;
+    *device_bytes = held + h->work_bytes;
+  }
+  if (setup_seconds) *setup_seconds = h->setup_seconds;
+  return 0;
+}
+
+extern "C" int rlh_fsai_get(rlh_fsai_t h, int64_t *indptr, int32_t *indices, void *values) {
+  if (int rc = require_ready()) return rc;
+  RLH_REQUIRE(h, "rlh_fsai_get: null handle");
+  RLH_REQUIRE(indptr && (h->nnz == 0 || (indices && values)), "rlh_fsai_get: null output");
+  if (!h->spd) {
+    indptr[0] = 0;
+    return 0;
+  }
+  const SpdArrays g = spd_arrays(h->spd, 0);
+  RLH_HIP(hipStreamSynchronize(ctx().stream));
+  RLH_HIP(hipMemcpy(indptr, g.indptr, (size_t)(g.rows + 1) * 8, hipMemcpyDeviceToHost));
+  if (g.nnz) {
+    RLH_HIP(hipMemcpy(indices, g.idx, (size_t)g.nnz * 4, hipMemcpyDeviceToHost));
+    RLH_HIP(hipMemcpy(values, g.val, (size_t)(g.nnz * dtype_size(h->dtype)), hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+extern "C" int rlh_fsai_apply(rlh_fsai_t h, int64_t m, const void *X, int64_t ldx, void *Y, int64_t ldy) {
+  if (int rc = require_ready()) return rc;
+  RLH_REQUIRE(h, "rlh_fsai_apply: null handle");
+  RLH_REQUIRE(m >= 0, "rlh_fsai_apply: negative number of vectors");
+  if (m == 0 || h->n == 0) return 0;
+  RLH_REQUIRE(X && Y, "rlh_fsai_apply: null pointer");
+  RLH_REQUIRE(ldx >= h->n && ldy >= h->n, "rlh_fsai_apply: Matrix and vectors dimensions incompatible");
+  const int64_t ldw = (h->n + 15) & ~(int64_t)15;
+  const int64_t need = ldw * m * dtype_size(h->dtype);
+  if (need > h->work_bytes) {              // grows once per wider block, then reused without allocation
+    RLH_HIP(hipStreamSynchronize(ctx().stream));
+    if (h->work) RLH_HIP(hipFree(h->work));
+    h->work = nullptr;
+    h->work_bytes = 0;
+    RLH_HIP(hipMalloc((void **)&h->work, (size_t)need));
+    h->work_bytes = need;
+  }
+  if (int rc = rlh_spd_apply(h->spd, 0, m, X, ldx, h->work, ldw, nullptr, nullptr)) return rc;
+  return rlh_spd_apply(h->spd, 1, m, h->work, ldw, Y, ldy, nullptr, nullptr);
+}

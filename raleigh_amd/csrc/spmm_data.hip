@@ -20,6 +20,7 @@
 // handle.  Every offset that scales with nnz or rows x vectors is 64-bit.
 #include "common.h"
 #include "device_build.h"
+#include "spmm_data.h"
 
 #include <algorithm>
 #include <chrono>
@@ -693,6 +694,14 @@ int apply_impl(rlh_spd *h, const Side &s, int64_t m, const T *X, int64_t ldx, T 
 
 }  // namespace
 }  // namespace rlh
+
+rlh::SpdArrays rlh::spd_arrays(const rlh_spd *h, int transp) {
+  const Side &s = h->side[transp ? 1 : 0];
+  SpdArrays a;
+  a.rows = s.rows; a.cols = s.cols; a.nnz = s.nnz;
+  a.indptr = s.indptr; a.idx = s.idx; a.val = s.val;
+  return a;
+}
 
 using namespace rlh;
 

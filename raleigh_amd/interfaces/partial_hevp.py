@@ -38,8 +38,10 @@ def partial_hevp(A, B=None, T=None, buckling=False, sigma=0, which=6, tol=1e-4, 
     ``solver=IterativeSymmetricSolver(...)`` nothing of the matrix goes to the host, and `x` comes back as an
     ``(n, k)`` tensor on that GPU (`lmd` stays an ndarray: the solver holds it on the host anyway).  The direct
     factorisation (no `T`, no `solver`) is a host algorithm: the tensor is copied to the host ONCE for it, while the
-    operator of the error estimate is still built on the device.  An IncompleteLU preconditioner is set up from a
-    SciPy matrix only.  A CPU tensor is taken as the SciPy matrix of its arrays (ndarrays come back).
+    operator of the error estimate is still built on the device.  Of the preconditioners, `ApproximateInverse`
+    (algebra/hip/precond.py) takes the same tensor and is set up by kernels on the GPU, as `ChebyshevPreconditioner`
+    is from the operator; an IncompleteLU preconditioner is a host factorisation and is set up from a SciPy matrix
+    only.  A CPU tensor is taken as the SciPy matrix of its arrays (ndarrays come back).
 
     Returns (lmd, x, status): eigenvalues ascending, eigenvectors as columns, status as
     in the reference (0 success, 1 iteration limit, 2 no search directions, 3/4 some

@@ -1,0 +1,162 @@
+"""ApproximateInverse (factorised sparse approximate inverse, set up and applied on the GPU) against IncompleteLU
+(host ILUT, triangular solves on the GPU) and no preconditioner, in the same run, float64 (GPU box):
+
+  (i)  the config-3 FE surrogate (raleigh_amd/synthetic.py)      (ii) lap3d 64^3      -- the sizes of tools/ilu_bench.py
+
+  set-up       ApproximateInverse from a torch.sparse_csr tensor on the GPU: the device time the library reports
+               (events around the whole build) and the host wall time; IncompleteLU.factorize on the same matrix
+               (host wall time: ILUT on the host, then the set-up of the two triangular solves)
+  application  milliseconds per call at m = 16: HIP events (rlh_timer_start / rlh_timer_stop) around --calls calls, the
+               two preconditioners taking turns inside each of --repeats repeats; algorithmic GB/s at the fastest
+  solve        partial_hevp(which=10, tol=1e-6) with T = ApproximateInverse, IncompleteLU, True: iterations and seconds
+
+Every timing is repeated --repeats times and reported as fastest .. slowest; "A beats B" means A's slowest repeat is
+faster than B's fastest.  Nothing here is a threshold.
+
+    python tools/approx_inverse_bench.py [--out profiles/r10_approx_inverse.txt] [--m 16] [--calls 20] [--repeats 5]
+"""
+import argparse
+import ctypes
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def resource_lines():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'kernel_resources.py'), 'fsai'], capture_output=True, text=True)
+    out = ['== tools/kernel_resources.py fsai (-Rpass-analysis=kernel-resource-usage; scr = scratch bytes per lane)']
+    return out + ['   ' + ln for ln in (r.stdout.strip().splitlines() or ['(no compiler here: %s)' % r.stderr.strip()[-200:]])]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'r10_approx_inverse.txt'))
+    ap.add_argument('--m', type=int, default=16)
+    ap.add_argument('--calls', type=int, default=20)
+    ap.add_argument('--repeats', type=int, default=5)
+    ap.add_argument('--lap', type=int, default=64)
+    ap.add_argument('--no-resources', action='store_true', help='skip the compiler\'s resource lines (needs hipcc)')
+    args = ap.parse_args()
+    import torch
+    import scipy.sparse as sp
+    from raleigh_amd import _lib
+    from raleigh_amd.algebra.hip import Vectors
+    from raleigh_amd.algebra.hip.precond import ApproximateInverse, IncompleteLU
+    from raleigh_amd.interfaces import partial_hevp
+    from raleigh_amd.core.solver import Options
+    from raleigh_amd.synthetic import lap3d_rows, fe_surrogate
+    assert torch.cuda.is_available(), 'this tool measures on the GPU'
+    L = _lib.lib()
+    m = args.m
+    out_file = open(args.out, 'w')
+
+    def say(text=''):
+        print(text, flush=True)
+        out_file.write(text + '\n')
+        out_file.flush()
+
+    def span(ts, scale=1.0, fmt='%.3f'):
+        return (fmt + ' .. ' + fmt) % (min(ts) * scale, max(ts) * scale)
+
+    def beats(a, b, ta, tb):
+        if max(ta) < min(tb):
+            return '%s beats %s (slowest %.4g < fastest %.4g)' % (a, b, max(ta), min(tb))
+        if max(tb) < min(ta):
+            return '%s beats %s (slowest %.4g < fastest %.4g)' % (b, a, max(tb), min(ta))
+        return 'no winner between %s and %s (the ranges overlap)' % (a, b)
+
+    say('# ApproximateInverse against IncompleteLU and no preconditioner, float64, m = %d' % m)
+    say('# %s, %d calls per timing, %d repeats, fastest .. slowest; written by tools/approx_inverse_bench.py'
+        % (torch.cuda.get_device_name(0), args.calls, args.repeats))
+    say()
+    side = args.lap
+    cases = [('(i) config-3 FE surrogate', lambda: fe_surrogate()),
+             ('(ii) lap3d %d^3' % side, lambda: lap3d_rows(side, side, side, 1.0, 1.01, 1.02, 0, side ** 3))]
+    for title, make in cases:
+        A = sp.csr_matrix(make().astype(np.float64))
+        A.sort_indices()
+        n = A.shape[0]
+        t = torch.sparse_csr_tensor(torch.from_numpy(A.indptr.astype(np.int32)), torch.from_numpy(A.indices.astype(np.int32)),
+                                    torch.from_numpy(A.data), size=A.shape).to('cuda')
+        torch.cuda.synchronize()
+        say('== %s: n = %d, nnz = %d (%.1f per row)' % (title, n, A.nnz, A.nnz / n))
+        # ---- set-up
+        dev_s, wall_s, ilu_s = [], [], []
+        T = None
+        for _ in range(args.repeats):
+            T = None
+            t0 = time.perf_counter()
+            T = ApproximateInverse(t)
+            _lib.check(L.rlh_sync())
+            wall_s.append(time.perf_counter() - t0)
+            dev_s.append(T.setup_seconds)
+        ilu = None
+        for _ in range(args.repeats):
+            ilu = None
+            t0 = time.perf_counter()
+            ilu = IncompleteLU(A)
+            ilu.factorize()
+            _lib.check(L.rlh_sync())
+            ilu_s.append(time.perf_counter() - t0)
+        say('   set-up  ApproximateInverse(tensor)   device %s s, host wall %s s; nnz(G) = %d (fill %.2f, longest row %d, '
+            '%d rows cut), %.1f MB held' % (span(dev_s, fmt='%.4f'), span(wall_s, fmt='%.4f'), T.nnz, T.fill, T.longest_row,
+                                            T.truncated_rows, T.device_bytes() / 1e6))
+        say('   set-up  IncompleteLU.factorize        host wall %s s; fill %.2f, levels %s'
+            % (span(ilu_s, fmt='%.4f'), ilu.fill, ilu.levels))
+        say('           ' + beats('ApproximateInverse', 'IncompleteLU', wall_s, ilu_s))
+        # ---- application
+        B, X = Vectors(n, m), Vectors(n, m)
+        B.fill_random()
+        ops = [('ApproximateInverse', T, T.algorithmic_bytes(m)), ('IncompleteLU', ilu, ilu.chain().algorithmic_bytes(m))]
+        for _, op, _ in ops:
+            for _ in range(3):
+                op.apply(B, X)
+        _lib.check(L.rlh_sync())
+        ms = ctypes.c_float()
+        times = {name: [] for name, _, _ in ops}
+        for _ in range(args.repeats):
+            for name, op, _ in ops:
+                _lib.check(L.rlh_timer_start())
+                for _ in range(args.calls):
+                    op.apply(B, X)
+                _lib.check(L.rlh_timer_stop(ctypes.byref(ms)))
+                times[name].append(ms.value / args.calls)
+        for name, op, nb in ops:
+            say('   apply   %-20s %s ms per call; %.1f MB algorithmic -> %.0f GB/s at the fastest'
+                % (name, span(times[name], fmt='%.4f'), nb / 1e6, nb / min(times[name]) / 1e6))
+        say('           ' + beats('ApproximateInverse', 'IncompleteLU', times['ApproximateInverse'], times['IncompleteLU']))
+        # ---- solve
+        solves = {}
+        for name, prec in (('ApproximateInverse', T), ('IncompleteLU', ilu), ('True (none)', True)):
+            ts, its, status = [], None, None
+            for _ in range(args.repeats):
+                np.random.seed(1)
+                opt = Options()
+                opt.max_iter = 5000
+                _lib.check(L.rlh_sync())
+                t0 = time.perf_counter()
+                lmd, x, status = partial_hevp(t, T=prec, which=10, tol=1e-6, verb=-1, opt=opt)
+                _lib.check(L.rlh_sync())
+                ts.append(time.perf_counter() - t0)
+                its = partial_hevp.last['iterations'] if status is not None and status >= 0 else -1
+            solves[name] = ts
+            say('   solve   T = %-20s %s s, %d iterations, status %d, smallest eigenvalue %.10g'
+                % (name, span(ts, fmt='%.4f'), its, status, lmd[0] if lmd is not None and len(lmd) else float('nan')))
+        say('           ' + beats('ApproximateInverse', 'IncompleteLU', solves['ApproximateInverse'], solves['IncompleteLU']))
+        say('           ' + beats('ApproximateInverse', 'no preconditioner', solves['ApproximateInverse'], solves['True (none)']))
+        say()
+        del T, ilu, t
+    if not args.no_resources:
+        for ln in resource_lines():
+            say(ln)
+    out_file.close()
+
+
+if __name__ == '__main__':
+    main()
