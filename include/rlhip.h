@@ -490,12 +490,23 @@ int rlh_bytes_absmax(rlh_bytes_t h, double *h_out);
  * diagonal whose partner above is not stored; a local block that is not positive definite.
  * rlh_fsai_create_device: the three arrays lie in DEVICE memory (`index_bits` 32 or 64: the type of both index
  * arrays); they are never written and not referenced after the return; nothing but status records visits the host.
- * rlh_fsai_create: the same from HOST arrays, which are uploaded and take the same path. */
+ * rlh_fsai_create: the same from HOST arrays, which are uploaded and take the same path.
+ * The _levels forms put row i of G on the pattern of row i of tril(A)^levels, levels in [1, 8]: with L(i) the stored
+ * columns j <= i of row i, P_1(i) = L(i) and P_{l+1}(i) the union of L(j) over j in P_l(i); the row keeps the max_row
+ * largest columns of P_levels(i), and truncated_rows counts the rows whose full pattern has more.  levels = 1 is what
+ * the two forms above build, bit for bit.  A build takes rows of at most 8, 16, 32 and 64 kept entries on as many lanes
+ * each; with RLH_FSAI_BINS=0 in the environment (read by every create call) only on 8 or 64.  G does not depend on it. */
 typedef struct rlh_fsai *rlh_fsai_t;
 int rlh_fsai_create_device(rlh_fsai_t *h, int dtype, int64_t n, int index_bits, const void *d_indptr,
                            const void *d_indices, const void *d_values, int max_row);
 int rlh_fsai_create(rlh_fsai_t *h, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
                     const void *values, int max_row);
+int rlh_fsai_create_levels_device(rlh_fsai_t *h, int dtype, int64_t n, int index_bits, const void *d_indptr,
+                                  const void *d_indices, const void *d_values, int max_row, int levels);
+int rlh_fsai_create_levels(rlh_fsai_t *h, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
+                           const void *values, int max_row, int levels);
+/* the levels a handle was built with */
+int rlh_fsai_levels(rlh_fsai_t h, int *levels);
 /* Y = G^H (G X) for column-major DEVICE blocks of m vectors (leading dimensions >= n; Y may be X): two sparse
  * products (the kernels of rlh_spd_apply, bit-identical from call to call) through an n x m workspace of the handle,
  * which grows when a wider block than before arrives (that call synchronises the stream once); otherwise

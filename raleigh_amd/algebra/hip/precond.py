@@ -206,15 +206,27 @@ class ApproximateInverse:
     64, if there are more) and solves S g^H = e_k / g_kk, g_kk > 0, S the matching block of A, in double precision
     whatever the storage type.  T is Hermitian positive definite by construction, as the solver requires;
     ``apply`` is two sparse products.  It changes iteration counts relative to ILU, so runs using it are reported
-    separately from the reference's."""
+    separately from the reference's.
 
-    def __init__(self, matrix, max_row=64):
+    levels (1 .. 8) widens the pattern to that of the `levels`-th power of the lower triangle of A: with L(i) the
+    stored columns j <= i of row i, level 1 is L(i) and level l + 1 the union of L(j) over the columns j of level l.
+    The patterns are nested, so without truncation a higher level never has a larger Kaporin number; it costs more
+    entries per row (on a 7-point stencil 4, 10 and 20 at levels 1, 2 and 3) and a longer set-up.  Rows keep the
+    `max_row` largest columns of their pattern; `truncated_rows` counts those whose full pattern has more.
+    ``levels=1`` is the build described above, bit for bit."""
+
+    def __init__(self, matrix, max_row=64, levels=1):
         from . import device_data
         L = self._L = _lib.lib()                          # (the handle belongs to THIS library object)
         self._h = None
         max_row = int(max_row)
         if not 1 <= max_row <= 64:
             raise ValueError('max_row must lie in [1, 64], got %d' % max_row)
+        levels = int(levels)
+        if not 1 <= levels <= 8:
+            raise ValueError('levels must lie in [1, 8], got %d' % levels)
+        self.levels = levels
+        more = () if levels == 1 else (levels,)             # (level 1 goes through the entry points it always had)
         h = ctypes.c_void_p()
         if device_data.is_tensor(matrix):
             from .sparse import operator_tensor
@@ -231,9 +243,10 @@ class ApproximateInverse:
                     torch.cuda.current_stream(val.device).synchronize()
                 self._n = int(t.shape[0])
                 self._nnz_a = int(val.numel())
-                self._create(L.rlh_fsai_create_device, 'rlh_fsai_create_device', h, _lib.DTYPE_CODE[self._dtype], self._n,
+                name = 'rlh_fsai_create_levels_device' if more else 'rlh_fsai_create_device'
+                self._create(getattr(L, name), name, h, _lib.DTYPE_CODE[self._dtype], self._n,
                              32 if crow.element_size() == 4 else 64, ctypes.c_void_p(crow.data_ptr()),
-                             ctypes.c_void_p(col.data_ptr()), ctypes.c_void_p(val.data_ptr()), max_row)
+                             ctypes.c_void_p(col.data_ptr()), ctypes.c_void_p(val.data_ptr()), max_row, *more)
                 self._finish(h)
                 return
             matrix = device_data.to_host(t)
@@ -247,8 +260,9 @@ class ApproximateInverse:
         indptr = np.ascontiguousarray(a.indptr, dtype=np.int64)
         indices = np.ascontiguousarray(a.indices, dtype=np.int32)
         values = np.ascontiguousarray(a.data)
-        self._create(L.rlh_fsai_create, 'rlh_fsai_create', h, _lib.DTYPE_CODE[self._dtype], self._n, _lib.host_ptr(indptr),
-                     _lib.host_ptr(indices), _lib.host_ptr(values), max_row)
+        name = 'rlh_fsai_create_levels' if more else 'rlh_fsai_create'
+        self._create(getattr(L, name), name, h, _lib.DTYPE_CODE[self._dtype], self._n, _lib.host_ptr(indptr),
+                     _lib.host_ptr(indices), _lib.host_ptr(values), max_row, *more)
         self._finish(h)
 
     @staticmethod

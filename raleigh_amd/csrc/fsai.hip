@@ -2,7 +2,9 @@
 // given as a full CSR matrix in device memory (rlh_fsai_*, include/rlhip.h).  The UPPER triangle defines A: no value
 // stored below the diagonal is ever read.
 //
-// Row i of G lives on P_i, the (at most max_row, the largest) stored columns j <= i of row i of A.  With S =
+// Row i of G lives on P_i, the (at most max_row, the largest) columns of the level pattern of row i: with L(i) the
+// stored columns j <= i of row i of A, P_1(i) = L(i) and P_{l+1}(i) is the union of L(j) over j in P_l(i) -- the
+// pattern of tril(A)^levels, nested because j lies in L(j).  With S =
 // A[P_i, P_i] = R^H R (R upper triangular, positive diagonal) the row is g = conj(u), R u = e_k: then
 // S g^H = e_k / g_kk and g_kk = 1 / R_kk > 0.  Every local system is solved in double / complex double whatever the
 // storage type; G is rounded to it once, at the store.
@@ -10,10 +12,18 @@
 // The build, all on the library stream:
 //   checks          indptr (device_build.h), the columns of every row, then per row: the diagonal is stored and every
 //                   entry below it has its partner above (fsai_count)
-//   pattern         kept entries per row, exclusive scans, columns of G and the rows of the two bins (fsai_fill)
-//   set-up          fsai_setup<T, 8>: 8 lanes per row for k <= 8, 32 rows per workgroup;  fsai_setup<T, 64>: one
-//                   single-wave workgroup per row for k <= 64.  The packed upper triangle of S (then R) lies in the
-//                   LDS: 64 * 65 / 2 complex doubles = 33 KB at most, so four such workgroups fit the 160 KB of a CU.
+//   pattern         kept entries per row, exclusive scans, columns of G and the rows of the bins.  Level 1: a slice
+//                   of A's row (fsai_count, fsai_fill).  Higher levels: one wave per row (fsai_pattern_count, then
+//                   fsai_pattern_fill, which forms the row again).  Lane q walks L(P[q]) downwards from its diagonal;
+//                   the wave's maximum of the lanes' current columns is the next member, every lane that shows it
+//                   steps on: a descending selection without a sort, at most max_row + 1 steps per level.  Capping
+//                   to the max_row largest after every level gives the capped final pattern: what a dropped column
+//                   j reaches is <= j, below every kept column, and the kept ones are in the next union themselves.
+//   set-up          fsai_setup<T, LANES>: LANES = 8, 16, 32 or 64 lanes per row for k <= LANES (RLH_FSAI_BINS=0: 8
+//                   and 64 only), 256 threads per workgroup (128 for 32 lanes in complex, 64 for 64 lanes).  The
+//                   packed upper triangle of S (then R) lies in the LDS: at most 40 KB per workgroup, so four
+//                   workgroups fit the 160 KB of a CU.  Lane q owns column q and every sum runs over t in order, so
+//                   a row's bits do not depend on its bin.  The pattern is read from G's own column array;
 //                   S is gathered by a binary search for column P[q] in the sorted row P[p], p <= q.
 //   operators       G and G^H as the two orientations of one sparse data operator (rlh_spd_create_device), which
 //                   copies G's arrays; the build's own are scratch and released.
@@ -24,6 +34,7 @@
 #include "device_build.h"
 #include "spmm_data.h"
 
+#include <cstdlib>
 #include <type_traits>
 
 namespace rlh {
@@ -31,6 +42,7 @@ namespace {
 
 constexpr int kShort = 8;                      // rows of at most kShort kept entries: kShort lanes per row
 constexpr int kMaxRow = 64;
+constexpr int kMaxLevels = 8;
 constexpr int kSetupBlocksPerCu = 8;           // grid of a set-up kernel: at most this many workgroups per CU
 enum { kErrDiag = 6, kErrPartner = 7, kErrNotPd = 8 };
 
@@ -67,11 +79,37 @@ __device__ __forceinline__ int64_t lower_bound_col(const int32_t *__restrict__ i
   return lo;
 }
 
-// per row: the diagonal is stored, every entry below it has its partner; the kept entries (the last
-// min(lower, max_row) up to the diagonal) and where they begin in A's row
-__global__ __launch_bounds__(kBlock) void fsai_count(int64_t n, int max_row, const int64_t *__restrict__ ip,
+// The rows of a build go to bins by their kept entries k: 8, 16, 32 or 64 lanes per row (two bins: 8 or 64).  Two
+// scans carry the three running counts of rows with k <= 8, k <= 16 (high half of the first key) and k <= 32; with two
+// bins all three count k <= 8.  n < 2^31, so the halves do not meet.
+__device__ __forceinline__ void bin_keys(int64_t k, int four, int64_t *ka, int64_t *kb) {
+  const int64_t a = k <= kShort ? 1 : 0, b = four ? (k <= 16 ? 1 : 0) : a, c = four ? (k <= 32 ? 1 : 0) : a;
+  *ka = a | (b << 32);
+  *kb = c;
+}
+
+struct Bins {
+  const int64_t *sa, *sb;        // exclusive scans of the two keys
+  int64_t c8, c16, c32;          // their totals: rows with k <= 8, <= 16, <= 32
+  int32_t *rows;                 // the rows of bin 8, then 16, 32 and 64, each in ascending order
+};
+
+__device__ __forceinline__ void put_row(const Bins &b, int64_t i, int64_t k) {
+  const int64_t a = b.sa[i], p8 = a & 0xffffffff, p16 = a >> 32, p32 = b.sb[i];
+  int64_t at;
+  if (k <= kShort) at = p8;
+  else if (p16 + 1 == (b.sa[i + 1] >> 32)) at = b.c8 + (p16 - p8);
+  else if (p32 + 1 == b.sb[i + 1]) at = b.c16 + (p32 - p16);
+  else at = b.c32 + (i - p32);
+  b.rows[at] = (int32_t)i;
+}
+
+// per row: the diagonal is stored, every entry below it has its partner; at level 1 (tally) the kept entries (the
+// last min(lower, max_row) up to the diagonal), where they begin in A's row, and the keys of the row's bin
+__global__ __launch_bounds__(kBlock) void fsai_count(int64_t n, int max_row, int tally, int four, const int64_t *__restrict__ ip,
                                                      const int32_t *__restrict__ ix, int64_t *__restrict__ cnt,
-                                                     int64_t *__restrict__ is_short, int64_t *__restrict__ start, FsaiStatus *st) {
+                                                     int64_t *__restrict__ keya, int64_t *__restrict__ keyb,
+                                                     int64_t *__restrict__ start, FsaiStatus *st) {
   if (failed(st)) return;
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
@@ -88,12 +126,16 @@ __global__ __launch_bounds__(kBlock) void fsai_count(int64_t n, int max_row, con
       }
       const int64_t lower = d + 1 - kb;
       k = lower < max_row ? lower : max_row;
-      if (lower > max_row) atomicAdd(&st->truncated, 1ull);
-      atomicMax(&st->longest, (int)k);
+      if (tally) {
+        if (lower > max_row) atomicAdd(&st->truncated, 1ull);
+        atomicMax(&st->longest, (int)k);
+      }
       start[i] = d + 1 - k;
     }
-    cnt[i] = k;
-    is_short[i] = k <= kShort ? 1 : 0;
+    if (tally) {
+      cnt[i] = k;
+      bin_keys(k, four, &keya[i], &keyb[i]);
+    }
   }
 }
 
@@ -110,17 +152,111 @@ __global__ void fsai_resolve_error(int64_t n, const int64_t *__restrict__ ip, co
   st->col = (long long)ix[k];
 }
 
-// the columns of G and the rows of the two bins, each in ascending order (sp: the exclusive scan of is_short)
+// level 1: the columns of G (a slice of A's row) and the rows of the bins
 __global__ __launch_bounds__(kBlock) void fsai_fill(int64_t n, const int32_t *__restrict__ ix, const int64_t *__restrict__ start,
-                                                    const int64_t *__restrict__ gp, const int64_t *__restrict__ sp,
-                                                    int32_t *__restrict__ gi, int32_t *__restrict__ rows_short,
-                                                    int32_t *__restrict__ rows_long) {
+                                                    const int64_t *__restrict__ gp, int32_t *__restrict__ gi, Bins bins) {
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
     const int64_t g0 = gp[i], k = gp[i + 1] - g0, a0 = start[i];
     for (int64_t t = 0; t < k; ++t) gi[g0 + t] = ix[a0 + t];
-    const int64_t s = sp[i];
-    if (sp[i + 1] > s) rows_short[s] = (int32_t)i; else rows_long[i - s] = (int32_t)i;
+    put_row(bins, i, k);
+  }
+}
+
+// lanes of one wave that exchange data through the LDS: the LDS serves a wave's accesses in order; this keeps the
+// compiler from moving one across
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ int wave_max(int v) {
+  for (int o = 32; o; o >>= 1) {
+    const int w = __shfl_xor(v, o, 64);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+
+// The level pattern of row i by one wave: its (at most max_row, the largest) columns ascending in cur[0 .. k), k
+// returned in every lane; *over: the full pattern has more than max_row members.  Every lane of the wave gets here
+// together; the trip counts are the wave's.
+__device__ __forceinline__ int row_pattern(int64_t i, int max_row, int levels, const int64_t *__restrict__ ip,
+                                           const int32_t *__restrict__ ix, int32_t *cur, int lane, bool *over) {
+  const int64_t kb = ip[i], ke = ip[i + 1], d = lower_bound_col(ix, kb, ke, i);
+  const int64_t lower = d - kb + ((d < ke && (int64_t)ix[d] == i) ? 1 : 0);
+  int k = (int)(lower < max_row ? lower : max_row);
+  *over = lower > max_row;
+  wave_sync();                                       // (the row before this one is done with the LDS)
+  if (lane < k) cur[lane] = ix[kb + lower - k + lane];
+  wave_sync();
+  for (int l = 1; l < levels; ++l) {
+    // lane q < k walks L(cur[q]) downwards: pos is the entry it shows, from the diagonal of that row on
+    int64_t beg = 0, pos = -1;
+    if (lane < k) {
+      const int64_t j = cur[lane], je = ip[j + 1];
+      beg = ip[j];
+      const int64_t f = lower_bound_col(ix, beg, je, j);
+      pos = (f < je && (int64_t)ix[f] == j) ? f : f - 1;
+    }
+    int cand = pos >= beg ? ix[pos] : -1, mine = -1, kn = 0;
+    for (;;) {
+      const int m = wave_max(cand);                  // the largest column not yet taken: the same in every lane
+      if (m < 0) break;
+      if (kn == max_row) {
+        *over = true;
+        break;
+      }
+      if (lane == kn) mine = m;
+      ++kn;
+      if (cand == m) {
+        --pos;
+        cand = pos >= beg ? ix[pos] : -1;
+      }
+    }
+    wave_sync();
+    if (lane < kn) cur[kn - 1 - lane] = mine;
+    wave_sync();
+    k = kn;
+  }
+  return k;
+}
+
+// levels > 1: the kept entries per row and the keys of its bin (one wave per row)
+__global__ __launch_bounds__(kBlock) void fsai_pattern_count(int64_t n, int max_row, int levels, int four,
+                                                             const int64_t *__restrict__ ip, const int32_t *__restrict__ ix,
+                                                             int64_t *__restrict__ cnt, int64_t *__restrict__ ka,
+                                                             int64_t *__restrict__ kb, FsaiStatus *st) {
+  if (failed(st)) return;
+  __shared__ int32_t cur[kBlock / 64][64];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t waves = (int64_t)gridDim.x * (kBlock / 64);
+  for (int64_t i = (int64_t)blockIdx.x * (kBlock / 64) + wave; i < n; i += waves) {
+    bool over;
+    const int k = row_pattern(i, max_row, levels, ip, ix, cur[wave], lane, &over);
+    if (lane == 0) {
+      cnt[i] = k;
+      bin_keys(k, four, &ka[i], &kb[i]);
+      if (over) atomicAdd(&st->truncated, 1ull);
+      atomicMax(&st->longest, k);
+    }
+  }
+}
+
+// levels > 1: the columns of G and the rows of the bins (the same walk again: nothing but the counts is kept between)
+__global__ __launch_bounds__(kBlock) void fsai_pattern_fill(int64_t n, int max_row, int levels, const int64_t *__restrict__ ip,
+                                                            const int32_t *__restrict__ ix, const int64_t *__restrict__ gp,
+                                                            int32_t *__restrict__ gi, Bins bins) {
+  __shared__ int32_t cur[kBlock / 64][64];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t waves = (int64_t)gridDim.x * (kBlock / 64);
+  for (int64_t i = (int64_t)blockIdx.x * (kBlock / 64) + wave; i < n; i += waves) {
+    bool over;
+    const int64_t g0 = gp[i];
+    int k = row_pattern(i, max_row, levels, ip, ix, cur[wave], lane, &over);
+    if ((int64_t)k > gp[i + 1] - g0) k = (int)(gp[i + 1] - g0);      // (equal: the walk is the counting kernel's)
+    if (lane < k) gi[g0 + lane] = cur[wave][lane];
+    if (lane == 0) put_row(bins, i, k);
   }
 }
 
@@ -148,13 +284,6 @@ __device__ __forceinline__ c64 div_real(c64 a, double r) { return c64{a.re / r, 
 __device__ __forceinline__ double shfl_of(double a, int src, int width) { return __shfl(a, src, width); }
 __device__ __forceinline__ c64 shfl_of(c64 a, int src, int width) { return c64{__shfl(a.re, src, width), __shfl(a.im, src, width)}; }
 
-// lanes of one wave that exchange data through the LDS: the LDS serves a wave's accesses in order; this keeps the
-// compiler from moving one across
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // d^(-1/2), correctly rounded up to the rarest of ties: 1 / sqrt(d) (two roundings) and one Newton step whose
 // residual 1 - d g^2 is formed without rounding d g (its low part comes from a fused multiply-add)
 __device__ __forceinline__ double inv_sqrt(double d) {
@@ -167,15 +296,20 @@ __device__ __forceinline__ double inv_sqrt(double d) {
 
 __device__ __forceinline__ int tri_at(int p, int q) { return q * (q + 1) / 2 + p; }     // p <= q, packed by columns
 
+// threads of a set-up workgroup: the packed triangles of its rows stay within 40 KB of LDS
+template <typename T, int LANES> constexpr int setup_threads() {
+  return LANES == 64 ? 64 : (LANES == 32 && sizeof(typename Wide<T>::type) == 16) ? 128 : kBlock;
+}
+
 template <typename T, int LANES>
-__global__ __launch_bounds__(LANES == 64 ? 64 : kBlock) void fsai_setup(int64_t nlist, const int32_t *__restrict__ list,
-                                                                          const int64_t *__restrict__ ip,
-                                                                          const int32_t *__restrict__ ix, const T *__restrict__ va,
-                                                                          const int64_t *__restrict__ start,
-                                                                          const int64_t *__restrict__ gp, T *__restrict__ gv,
-                                                                          FsaiStatus *st) {
+__global__ __launch_bounds__((setup_threads<T, LANES>())) void fsai_setup(int64_t nlist, const int32_t *__restrict__ list,
+                                                                        const int64_t *__restrict__ ip,
+                                                                        const int32_t *__restrict__ ix, const T *__restrict__ va,
+                                                                        const int64_t *__restrict__ gp,
+                                                                        const int32_t *__restrict__ gi, T *__restrict__ gv,
+                                                                        FsaiStatus *st) {
   using D = typename Wide<T>::type;
-  constexpr int kThreads = LANES == 64 ? 64 : kBlock, kGroups = kThreads / LANES, kTri = LANES * (LANES + 1) / 2;
+  constexpr int kThreads = setup_threads<T, LANES>(), kGroups = kThreads / LANES, kTri = LANES * (LANES + 1) / 2;
   __shared__ D tri[kGroups][kTri];
   __shared__ int32_t pcol[kGroups][LANES];
   __shared__ int64_t pbeg[kGroups][LANES], pend[kGroups][LANES];
@@ -183,11 +317,11 @@ __global__ __launch_bounds__(LANES == 64 ? 64 : kBlock) void fsai_setup(int64_t 
   D *R = tri[grp];
   for (int64_t s = (int64_t)blockIdx.x * kGroups + grp; s < nlist; s += (int64_t)gridDim.x * kGroups) {
     const int64_t i = list[s];
-    const int64_t g0 = gp[i], a0 = start[i];
+    const int64_t g0 = gp[i];
     const int k = (int)(gp[i + 1] - g0);             // 1 <= k <= LANES: the bins are made from these counts
     wave_sync();                                     // (the row before this one is done with the LDS)
     if (lane < k) {
-      const int32_t c = ix[a0 + lane];
+      const int32_t c = gi[g0 + lane];
       pcol[grp][lane] = c;
       pbeg[grp][lane] = ip[c];
       pend[grp][lane] = ip[c + 1];
@@ -240,14 +374,15 @@ __global__ __launch_bounds__(LANES == 64 ? 64 : kBlock) void fsai_setup(int64_t 
 
 struct FsaiScratch {                // released when the build returns, however it returns
   FsaiStatus *status = nullptr;
-  int64_t *indptr = nullptr, *cnt = nullptr, *is_short = nullptr, *start = nullptr, *gp = nullptr, *sp = nullptr, *bsum = nullptr;
-  int32_t *cols = nullptr, *gi = nullptr, *gp32 = nullptr, *rows_short = nullptr, *rows_long = nullptr;
+  int64_t *indptr = nullptr, *cnt = nullptr, *ka = nullptr, *kb = nullptr, *start = nullptr, *gp = nullptr, *sa = nullptr,
+          *sb = nullptr, *bsum = nullptr;
+  int32_t *cols = nullptr, *gi = nullptr, *gp32 = nullptr, *rows = nullptr;
   void *gv = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   ~FsaiScratch() {
-    (void)hipFree(status); (void)hipFree(indptr); (void)hipFree(cnt); (void)hipFree(is_short); (void)hipFree(start);
-    (void)hipFree(gp); (void)hipFree(sp); (void)hipFree(bsum); (void)hipFree(cols); (void)hipFree(gi); (void)hipFree(gp32);
-    (void)hipFree(rows_short); (void)hipFree(rows_long); (void)hipFree(gv);
+    (void)hipFree(status); (void)hipFree(indptr); (void)hipFree(cnt); (void)hipFree(ka); (void)hipFree(kb); (void)hipFree(start);
+    (void)hipFree(gp); (void)hipFree(sa); (void)hipFree(sb); (void)hipFree(bsum); (void)hipFree(cols); (void)hipFree(gi);
+    (void)hipFree(gp32); (void)hipFree(rows); (void)hipFree(gv);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
   }
@@ -259,7 +394,7 @@ struct FsaiScratch {                // released when the build returns, however 
 struct rlh_fsai {
   int dtype = 0;
   int64_t n = 0, nnz = 0, truncated = 0;
-  int longest = 0;
+  int longest = 0, levels = 1;
   double setup_seconds = 0;
   rlh_spd_t spd = nullptr;          // G and G^H with their partitions
   char *work = nullptr;             // the n x m block between the two products
@@ -279,10 +414,23 @@ int exclusive_scan(int64_t n, const int64_t *in, int64_t *bsum, int64_t *out) {
   return 0;
 }
 
-// `name`: the entry point the messages speak for.  ip, ix, va: device arrays, n >= 1.
+// one set-up kernel over the rows of one bin
+template <typename T, int LANES>
+void launch_setup(int64_t count, const int32_t *list, const int64_t *ip, const int32_t *ix, const T *va, const int64_t *gp,
+                  const int32_t *gi, T *gv, FsaiStatus *status) {
+  if (!count) return;
+  constexpr int kThreads = setup_threads<T, LANES>();
+  const int64_t most = (int64_t)ctx().num_cu * kSetupBlocksPerCu;
+  hipLaunchKernelGGL((fsai_setup<T, LANES>), dim3(blocks_for(count, kThreads / LANES, most)), dim3(kThreads), 0, ctx().stream, count,
+                     list, ip, ix, va, gp, gi, gv, status);
+}
+
+// `name`: the entry point the messages speak for.  ip, ix, va: device arrays, n >= 1.  four: bins of 8, 16, 32 and 64
+// lanes per row (else 8 and 64).
 template <typename T, typename P, typename I>
-int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T *va, int max_row) {
+int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T *va, int max_row, int four) {
   const int64_t es = sizeof(T), n = h->n;
+  const int levels = h->levels;
   hipStream_t st = ctx().stream;
   const dim3 blk(kBlock);
   FsaiScratch w;
@@ -347,41 +495,51 @@ int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T 
   }
   // ---- the pattern
   const int64_t nb = (n + kScanTile - 1) / kScanTile;
+  const int64_t most = (int64_t)ctx().num_cu * kSetupBlocksPerCu;
   RLH_HIP(hipMalloc((void **)&w.cnt, (size_t)n * 8));
-  RLH_HIP(hipMalloc((void **)&w.is_short, (size_t)n * 8));
+  RLH_HIP(hipMalloc((void **)&w.ka, (size_t)n * 8));
+  RLH_HIP(hipMalloc((void **)&w.kb, (size_t)n * 8));
   RLH_HIP(hipMalloc((void **)&w.start, (size_t)n * 8));
   RLH_HIP(hipMalloc((void **)&w.gp, (size_t)(n + 1) * 8));
-  RLH_HIP(hipMalloc((void **)&w.sp, (size_t)(n + 1) * 8));
+  RLH_HIP(hipMalloc((void **)&w.sa, (size_t)(n + 1) * 8));
+  RLH_HIP(hipMalloc((void **)&w.sb, (size_t)(n + 1) * 8));
   RLH_HIP(hipMalloc((void **)&w.bsum, (size_t)(nb + 1) * 8));
-  hipLaunchKernelGGL(fsai_count, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, max_row, ip64, ix32, w.cnt, w.is_short, w.start,
-                     w.status);
+  hipLaunchKernelGGL(fsai_count, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, max_row, levels == 1 ? 1 : 0, four, ip64, ix32,
+                     w.cnt, w.ka, w.kb, w.start, w.status);
   hipLaunchKernelGGL(fsai_resolve_error, dim3(1), dim3(1), 0, st, n, ip64, ix32, w.status);
+  if (levels > 1)
+    hipLaunchKernelGGL(fsai_pattern_count, dim3(blocks_for(n, kBlock / 64, most)), blk, 0, st, n, max_row, levels, four, ip64, ix32,
+                       w.cnt, w.ka, w.kb, w.status);
   if (int rc = exclusive_scan(n, w.cnt, w.bsum, w.gp)) return rc;
-  if (int rc = exclusive_scan(n, w.is_short, w.bsum, w.sp)) return rc;
-  int64_t tot[2] = {0, 0};
+  if (int rc = exclusive_scan(n, w.ka, w.bsum, w.sa)) return rc;
+  if (int rc = exclusive_scan(n, w.kb, w.bsum, w.sb)) return rc;
+  int64_t tot[3] = {0, 0, 0};
   RLH_HIP(hipMemcpyAsync(&hs, w.status, sizeof hs, hipMemcpyDeviceToHost, st));
   RLH_HIP(hipMemcpyAsync(&tot[0], w.gp + n, 8, hipMemcpyDeviceToHost, st));
-  RLH_HIP(hipMemcpyAsync(&tot[1], w.sp + n, 8, hipMemcpyDeviceToHost, st));
+  RLH_HIP(hipMemcpyAsync(&tot[1], w.sa + n, 8, hipMemcpyDeviceToHost, st));
+  RLH_HIP(hipMemcpyAsync(&tot[2], w.sb + n, 8, hipMemcpyDeviceToHost, st));
   RLH_HIP(hipStreamSynchronize(st));
   if (hs.err != kNoError) return report(hs);
-  const int64_t gnnz = tot[0], n_short = tot[1], n_long = n - n_short;
+  const int64_t gnnz = tot[0], c8 = tot[1] & 0xffffffff, c16 = tot[1] >> 32, c32 = tot[2];
+  RLH_REQUIRE(gnnz >= n && gnnz <= n * (int64_t)max_row && c8 >= 0 && c8 <= c16 && c16 <= c32 && c32 <= n,
+              "%s: inconsistent row counts of the pattern", name);
   h->nnz = gnnz;
   h->truncated = (int64_t)hs.truncated;
   h->longest = hs.longest;
   RLH_HIP(hipMalloc((void **)&w.gi, (size_t)gnnz * 4));
   RLH_HIP(hipMalloc(&w.gv, (size_t)gnnz * es));
-  RLH_HIP(hipMalloc((void **)&w.rows_short, (size_t)std::max<int64_t>(n_short, 1) * 4));
-  RLH_HIP(hipMalloc((void **)&w.rows_long, (size_t)std::max<int64_t>(n_long, 1) * 4));
-  hipLaunchKernelGGL(fsai_fill, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, ix32, w.start, w.gp, w.sp, w.gi, w.rows_short,
-                     w.rows_long);
-  // ---- the rows
-  const int64_t most = (int64_t)ctx().num_cu * kSetupBlocksPerCu;
-  if (n_short)
-    hipLaunchKernelGGL((fsai_setup<T, kShort>), dim3(blocks_for(n_short, kBlock / kShort, most)), blk, 0, st, n_short, w.rows_short,
-                       ip64, ix32, va, w.start, w.gp, (T *)w.gv, w.status);
-  if (n_long)
-    hipLaunchKernelGGL((fsai_setup<T, kMaxRow>), dim3(blocks_for(n_long, 1, most)), dim3(64), 0, st, n_long, w.rows_long, ip64, ix32,
-                       va, w.start, w.gp, (T *)w.gv, w.status);
+  RLH_HIP(hipMalloc((void **)&w.rows, (size_t)n * 4));
+  const Bins bins{w.sa, w.sb, c8, c16, c32, w.rows};
+  if (levels == 1)
+    hipLaunchKernelGGL(fsai_fill, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, ix32, w.start, w.gp, w.gi, bins);
+  else
+    hipLaunchKernelGGL(fsai_pattern_fill, dim3(blocks_for(n, kBlock / 64, most)), blk, 0, st, n, max_row, levels, ip64, ix32, w.gp,
+                       w.gi, bins);
+  // ---- the rows, bin by bin
+  launch_setup<T, kShort>(c8, w.rows, ip64, ix32, va, w.gp, w.gi, (T *)w.gv, w.status);
+  launch_setup<T, 16>(c16 - c8, w.rows + c8, ip64, ix32, va, w.gp, w.gi, (T *)w.gv, w.status);
+  launch_setup<T, 32>(c32 - c16, w.rows + c16, ip64, ix32, va, w.gp, w.gi, (T *)w.gv, w.status);
+  launch_setup<T, kMaxRow>(n - c32, w.rows + c32, ip64, ix32, va, w.gp, w.gi, (T *)w.gv, w.status);
   RLH_HIP(hipGetLastError());
   RLH_HIP(hipMemcpyAsync(&hs, w.status, sizeof hs, hipMemcpyDeviceToHost, st));
   RLH_HIP(hipStreamSynchronize(st));
@@ -412,44 +570,47 @@ int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T 
 }
 
 template <typename P, typename I>
-int fsai_build_any(rlh_fsai *h, const char *name, const void *ip, const void *ix, const void *va, int max_row) {
+int fsai_build_any(rlh_fsai *h, const char *name, const void *ip, const void *ix, const void *va, int max_row, int four) {
   switch (h->dtype) {
-    case RLH_S: return fsai_build<float, P, I>(h, name, (const P *)ip, (const I *)ix, (const float *)va, max_row);
-    case RLH_D: return fsai_build<double, P, I>(h, name, (const P *)ip, (const I *)ix, (const double *)va, max_row);
-    case RLH_C: return fsai_build<c32, P, I>(h, name, (const P *)ip, (const I *)ix, (const c32 *)va, max_row);
-    case RLH_Z: return fsai_build<c64, P, I>(h, name, (const P *)ip, (const I *)ix, (const c64 *)va, max_row);
+    case RLH_S: return fsai_build<float, P, I>(h, name, (const P *)ip, (const I *)ix, (const float *)va, max_row, four);
+    case RLH_D: return fsai_build<double, P, I>(h, name, (const P *)ip, (const I *)ix, (const double *)va, max_row, four);
+    case RLH_C: return fsai_build<c32, P, I>(h, name, (const P *)ip, (const I *)ix, (const c32 *)va, max_row, four);
+    case RLH_Z: return fsai_build<c64, P, I>(h, name, (const P *)ip, (const I *)ix, (const c64 *)va, max_row, four);
   }
   return 1;
 }
 
-int check_create_args(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, const void *indptr, int max_row) {
+int check_create_args(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, const void *indptr, int max_row, int levels) {
   RLH_REQUIRE(ph != nullptr, "%s: null handle pointer", name);
   *ph = nullptr;
   RLH_REQUIRE(dtype_valid(dtype), "%s: unknown dtype %d", name, dtype);
   RLH_REQUIRE(n >= 0 && n < INT32_MAX, "%s: the size must lie in [0, 2^31 - 1)", name);
   RLH_REQUIRE(max_row >= 1 && max_row <= kMaxRow, "%s: max_row must lie in [1, %d], got %d", name, kMaxRow, max_row);
+  RLH_REQUIRE(levels >= 1 && levels <= kMaxLevels, "%s: levels must lie in [1, %d], got %d", name, kMaxLevels, levels);
   RLH_REQUIRE(indptr, "%s: null indptr", name);
   return 0;
 }
 
-}  // namespace
-}  // namespace rlh
+// RLH_FSAI_BINS=0: the two bins of 8 and 64 lanes per row; read by every create call
+int four_bins() {
+  const char *e = getenv("RLH_FSAI_BINS");
+  return (e && e[0] == '0' && e[1] == 0) ? 0 : 1;
+}
 
-using namespace rlh;
-
-extern "C" int rlh_fsai_create_device(rlh_fsai_t *ph, int dtype, int64_t n, int index_bits, const void *d_indptr,
-                                      const void *d_indices, const void *d_values, int max_row) {
-  const char *name = "rlh_fsai_create_device";
+int create_device(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, int index_bits, const void *d_indptr,
+                  const void *d_indices, const void *d_values, int max_row, int levels) {
   if (int rc = require_ready()) return rc;
-  if (int rc = check_create_args(name, ph, dtype, n, d_indptr, max_row)) return rc;
+  if (int rc = check_create_args(name, ph, dtype, n, d_indptr, max_row, levels)) return rc;
   RLH_REQUIRE(index_bits == 32 || index_bits == 64, "%s: index_bits must be 32 or 64, got %d", name, index_bits);
   rlh_fsai *h = new rlh_fsai();
   h->dtype = dtype;
   h->n = n;
+  h->levels = levels;
+  const int four = four_bins();
   int rc = 0;
   if (n > 0)
-    rc = index_bits == 32 ? fsai_build_any<int32_t, int32_t>(h, name, d_indptr, d_indices, d_values, max_row)
-                          : fsai_build_any<int64_t, int64_t>(h, name, d_indptr, d_indices, d_values, max_row);
+    rc = index_bits == 32 ? fsai_build_any<int32_t, int32_t>(h, name, d_indptr, d_indices, d_values, max_row, four)
+                          : fsai_build_any<int64_t, int64_t>(h, name, d_indptr, d_indices, d_values, max_row, four);
   if (rc) {
     rlh_fsai_destroy(h);
     return rc;
@@ -458,11 +619,10 @@ extern "C" int rlh_fsai_create_device(rlh_fsai_t *ph, int dtype, int64_t n, int 
   return 0;
 }
 
-extern "C" int rlh_fsai_create(rlh_fsai_t *ph, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
-                               const void *values, int max_row) {
-  const char *name = "rlh_fsai_create";
+int create_host(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
+                const void *values, int max_row, int levels) {
   if (int rc = require_ready()) return rc;
-  if (int rc = check_create_args(name, ph, dtype, n, indptr, max_row)) return rc;
+  if (int rc = check_create_args(name, ph, dtype, n, indptr, max_row, levels)) return rc;
   // what decides how much is uploaded is checked here; everything else by the kernels, as for device arrays
   RLH_REQUIRE(indptr[0] == 0, "%s: indptr[0] must be 0", name);
   for (int64_t r = 0; r < n; ++r) RLH_REQUIRE(indptr[r + 1] >= indptr[r], "%s: indptr decreases at row %lld", name, (long long)r);
@@ -471,6 +631,8 @@ extern "C" int rlh_fsai_create(rlh_fsai_t *ph, int dtype, int64_t n, const int64
   rlh_fsai *h = new rlh_fsai();
   h->dtype = dtype;
   h->n = n;
+  h->levels = levels;
+  const int four = four_bins();
   int rc = 0;
   if (n > 0) {
     int64_t *d_ip = nullptr;
@@ -482,7 +644,7 @@ extern "C" int rlh_fsai_create(rlh_fsai_t *ph, int dtype, int64_t n, const int64
     if (e == hipSuccess) e = hipMemcpy(d_ip, indptr, (size_t)(n + 1) * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess && nnz) e = hipMemcpy(d_ix, indices, (size_t)nnz * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess && nnz) e = hipMemcpy(d_va, values, (size_t)(nnz * es), hipMemcpyHostToDevice);
-    if (e == hipSuccess) rc = fsai_build_any<int64_t, int32_t>(h, name, d_ip, d_ix, d_va, max_row);
+    if (e == hipSuccess) rc = fsai_build_any<int64_t, int32_t>(h, name, d_ip, d_ix, d_va, max_row, four);
     (void)hipFree(d_ip);
     (void)hipFree(d_ix);
     (void)hipFree(d_va);
@@ -496,6 +658,37 @@ extern "C" int rlh_fsai_create(rlh_fsai_t *ph, int dtype, int64_t n, const int64
     return rc;
   }
   *ph = h;
+  return 0;
+}
+
+}  // namespace
+}  // namespace rlh
+
+using namespace rlh;
+
+extern "C" int rlh_fsai_create_device(rlh_fsai_t *ph, int dtype, int64_t n, int index_bits, const void *d_indptr,
+                                      const void *d_indices, const void *d_values, int max_row) {
+  return create_device("rlh_fsai_create_device", ph, dtype, n, index_bits, d_indptr, d_indices, d_values, max_row, 1);
+}
+
+extern "C" int rlh_fsai_create_levels_device(rlh_fsai_t *ph, int dtype, int64_t n, int index_bits, const void *d_indptr,
+                                             const void *d_indices, const void *d_values, int max_row, int levels) {
+  return create_device("rlh_fsai_create_levels_device", ph, dtype, n, index_bits, d_indptr, d_indices, d_values, max_row, levels);
+}
+
+extern "C" int rlh_fsai_create(rlh_fsai_t *ph, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
+                               const void *values, int max_row) {
+  return create_host("rlh_fsai_create", ph, dtype, n, indptr, indices, values, max_row, 1);
+}
+
+extern "C" int rlh_fsai_create_levels(rlh_fsai_t *ph, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
+                                      const void *values, int max_row, int levels) {
+  return create_host("rlh_fsai_create_levels", ph, dtype, n, indptr, indices, values, max_row, levels);
+}
+
+extern "C" int rlh_fsai_levels(rlh_fsai_t h, int *levels) {
+  RLH_REQUIRE(h && levels, "rlh_fsai_levels: null handle or output");
+  *levels = h->levels;
   return 0;
 }
 

@@ -3,6 +3,9 @@
 
   (i)  the config-3 FE surrogate (raleigh_amd/synthetic.py)      (ii) lap3d 64^3      -- the sizes of tools/ilu_bench.py
 
+  levels       --levels 1,2,3: one ApproximateInverse per level of fill (the pattern of that power of the lower triangle),
+               each reported with its longest row, entries per row and truncated rows, next to IncompleteLU and no
+               preconditioner
   set-up       ApproximateInverse from a torch.sparse_csr tensor on the GPU: the device time the library reports
                (events around the whole build) and the host wall time; IncompleteLU.factorize on the same matrix
                (host wall time: ILUT on the host, then the set-up of the two triangular solves)
@@ -11,9 +14,11 @@
   solve        partial_hevp(which=10, tol=1e-6) with T = ApproximateInverse, IncompleteLU, True: iterations and seconds
 
 Every timing is repeated --repeats times and reported as fastest .. slowest; "A beats B" means A's slowest repeat is
-faster than B's fastest.  Nothing here is a threshold.
+faster than B's fastest, anything else is "no winner".  Nothing here is a threshold.  --setup-only stops after the
+set-up lines (for comparing two builds of the library on one machine).
 
-    python tools/approx_inverse_bench.py [--out profiles/r10_approx_inverse.txt] [--m 16] [--calls 20] [--repeats 5]
+    python tools/approx_inverse_bench.py [--out profiles/r11_approx_inverse_levels.txt] [--levels 1,2,3] [--m 16]
+                                         [--calls 20] [--repeats 5] [--setup-only]
 """
 import argparse
 import ctypes
@@ -36,13 +41,16 @@ def resource_lines():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'r10_approx_inverse.txt'))
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'r11_approx_inverse_levels.txt'))
+    ap.add_argument('--levels', default='1,2,3', help='levels of fill of ApproximateInverse, comma separated')
+    ap.add_argument('--setup-only', action='store_true', help='set-up timings only')
     ap.add_argument('--m', type=int, default=16)
     ap.add_argument('--calls', type=int, default=20)
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--lap', type=int, default=64)
     ap.add_argument('--no-resources', action='store_true', help='skip the compiler\'s resource lines (needs hipcc)')
     args = ap.parse_args()
+    levels = [int(v) for v in args.levels.split(',')]
     import torch
     import scipy.sparse as sp
     from raleigh_amd import _lib
@@ -87,16 +95,27 @@ def main():
         torch.cuda.synchronize()
         say('== %s: n = %d, nnz = %d (%.1f per row)' % (title, n, A.nnz, A.nnz / n))
         # ---- set-up
-        dev_s, wall_s, ilu_s = [], [], []
-        T = None
-        for _ in range(args.repeats):
+        names = ['ApproximateInverse(levels=%d)' % lv for lv in levels]
+        Ts, walls = {}, {}
+        for lv, name in zip(levels, names):
+            dev_s, wall_s = [], []
             T = None
-            t0 = time.perf_counter()
-            T = ApproximateInverse(t)
-            _lib.check(L.rlh_sync())
-            wall_s.append(time.perf_counter() - t0)
-            dev_s.append(T.setup_seconds)
-        ilu = None
+            for _ in range(args.repeats):
+                T = None
+                t0 = time.perf_counter()
+                T = ApproximateInverse(t) if lv == 1 else ApproximateInverse(t, levels=lv)
+                _lib.check(L.rlh_sync())
+                wall_s.append(time.perf_counter() - t0)
+                dev_s.append(T.setup_seconds)
+            Ts[name], walls[name] = T, wall_s
+            say('   set-up  %-29s device %s s, host wall %s s; nnz(G) = %d (%.1f per row, fill %.2f, longest row %d, '
+                '%d rows cut), %.1f MB held' % (name, span(dev_s, fmt='%.4f'), span(wall_s, fmt='%.4f'), T.nnz, T.nnz / n, T.fill,
+                                                T.longest_row, T.truncated_rows, T.device_bytes() / 1e6))
+        if args.setup_only:
+            say()
+            del T, Ts, t
+            continue
+        ilu, ilu_s = None, []
         for _ in range(args.repeats):
             ilu = None
             t0 = time.perf_counter()
@@ -104,16 +123,15 @@ def main():
             ilu.factorize()
             _lib.check(L.rlh_sync())
             ilu_s.append(time.perf_counter() - t0)
-        say('   set-up  ApproximateInverse(tensor)   device %s s, host wall %s s; nnz(G) = %d (fill %.2f, longest row %d, '
-            '%d rows cut), %.1f MB held' % (span(dev_s, fmt='%.4f'), span(wall_s, fmt='%.4f'), T.nnz, T.fill, T.longest_row,
-                                            T.truncated_rows, T.device_bytes() / 1e6))
         say('   set-up  IncompleteLU.factorize        host wall %s s; fill %.2f, levels %s'
             % (span(ilu_s, fmt='%.4f'), ilu.fill, ilu.levels))
-        say('           ' + beats('ApproximateInverse', 'IncompleteLU', wall_s, ilu_s))
+        for name in names:
+            say('           ' + beats(name, 'IncompleteLU', walls[name], ilu_s))
         # ---- application
         B, X = Vectors(n, m), Vectors(n, m)
         B.fill_random()
-        ops = [('ApproximateInverse', T, T.algorithmic_bytes(m)), ('IncompleteLU', ilu, ilu.chain().algorithmic_bytes(m))]
+        ops = [(name, Ts[name], Ts[name].algorithmic_bytes(m)) for name in names]
+        ops.append(('IncompleteLU', ilu, ilu.chain().algorithmic_bytes(m)))
         for _, op, _ in ops:
             for _ in range(3):
                 op.apply(B, X)
@@ -128,12 +146,13 @@ def main():
                 _lib.check(L.rlh_timer_stop(ctypes.byref(ms)))
                 times[name].append(ms.value / args.calls)
         for name, op, nb in ops:
-            say('   apply   %-20s %s ms per call; %.1f MB algorithmic -> %.0f GB/s at the fastest'
+            say('   apply   %-29s %s ms per call; %.1f MB algorithmic -> %.0f GB/s at the fastest'
                 % (name, span(times[name], fmt='%.4f'), nb / 1e6, nb / min(times[name]) / 1e6))
-        say('           ' + beats('ApproximateInverse', 'IncompleteLU', times['ApproximateInverse'], times['IncompleteLU']))
+        for name in names:
+            say('           ' + beats(name, 'IncompleteLU', times[name], times['IncompleteLU']))
         # ---- solve
         solves = {}
-        for name, prec in (('ApproximateInverse', T), ('IncompleteLU', ilu), ('True (none)', True)):
+        for name, prec in [(name, Ts[name]) for name in names] + [('IncompleteLU', ilu), ('True (none)', True)]:
             ts, its, status = [], None, None
             for _ in range(args.repeats):
                 np.random.seed(1)
@@ -146,13 +165,20 @@ def main():
                 ts.append(time.perf_counter() - t0)
                 its = partial_hevp.last['iterations'] if status is not None and status >= 0 else -1
             solves[name] = ts
-            say('   solve   T = %-20s %s s, %d iterations, status %d, smallest eigenvalue %.10g'
+            say('   solve   T = %-29s %s s, %d iterations, status %d, smallest eigenvalue %.10g'
                 % (name, span(ts, fmt='%.4f'), its, status, lmd[0] if lmd is not None and len(lmd) else float('nan')))
-        say('           ' + beats('ApproximateInverse', 'IncompleteLU', solves['ApproximateInverse'], solves['IncompleteLU']))
-        say('           ' + beats('ApproximateInverse', 'no preconditioner', solves['ApproximateInverse'], solves['True (none)']))
+        for name in names:
+            say('           ' + beats(name, 'IncompleteLU', solves[name], solves['IncompleteLU']))
+            say('           ' + beats(name, 'no preconditioner', solves[name], solves['True (none)']))
+        for name in names[1:]:
+            say('           ' + beats(name, names[0], solves[name], solves[names[0]]))
+        # set-up and solve together: what a user who has the matrix on the GPU pays once
+        for name in names[1:]:
+            both = lambda k: [a + b for a, b in zip(sorted(walls[k]), sorted(solves[k]))]
+            say('           set-up + solve: ' + beats(name, names[0], both(name), both(names[0])))
         say()
-        del T, ilu, t
-    if not args.no_resources:
+        del T, Ts, ilu, t
+    if not args.no_resources and not args.setup_only:
         for ln in resource_lines():
             say(ln)
     out_file.close()
