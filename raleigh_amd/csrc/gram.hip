@@ -451,7 +451,6 @@ struct ZGramArgs {
   double *partials;                          // [64 x 128 entries][gridDim.x]
 };
 
-template <int DBG>
 __global__ __launch_bounds__(1024) void gram_z_dma_kernel(ZGramArgs a) {
   extern __shared__ __align__(16) char zlds[];
   typedef double acc_t __attribute__((ext_vector_type(4)));
@@ -477,10 +476,8 @@ __global__ __launch_bounds__(1024) void gram_z_dma_kernel(ZGramArgs a) {
     int64_t row = chunk * kZgRows + lrow;
     if (row > a.n - 1) row = a.n - 1;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if constexpr ((DBG & 1) != 0) break;
+    for (int i = 0; i < 4; ++i)
       dma16(gcol[i] + row, buf * (unsigned)kZgBuf + (unsigned)(wave * 4 + i) * (unsigned)kZgSlot);
-    }
   };
   // ---- multiply plan
   const int grp = wave >> 3, u = wave & 7, yp = u >> 2, xj = u & 3;
@@ -512,7 +509,6 @@ __global__ __launch_bounds__(1024) void gram_z_dma_kernel(ZGramArgs a) {
     const char *base = zlds + buf * (unsigned)kZgBuf;
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
-      if constexpr ((DBG & 2) != 0) break;
       const unsigned ro = (unsigned)ks * 32u;
       const double fa0 = *reinterpret_cast<const double *>(base + ya0 + ro + k8);
       const double fa1 = *reinterpret_cast<const double *>(base + ya1 + ro + k8);
@@ -572,23 +568,13 @@ static int gram_z_dma_launch(int64_t n, int64_t mx, const void *X, int64_t ldx, 
   int64_t nb = c.num_cu;
   if (nb > a.nchunks) nb = a.nchunks;
   RLH_REQUIRE((size_t)nb * 64 * 128 * sizeof(double) <= kWorkspaceBytes, "rlh_gram: reduction workspace");
-#define RLH_ZG(D_)                                                                                                  \
-  do {                                                                                                              \
-    static bool attr = false;                                                                                       \
-    if (!attr) {                                                                                                    \
-      RLH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gram_z_dma_kernel<D_>),                           \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kZgBuf));                         \
-      attr = true;                                                                                                  \
-    }                                                                                                               \
-    hipLaunchKernelGGL(gram_z_dma_kernel<D_>, dim3((unsigned)nb), dim3(1024), 2 * kZgBuf, c.stream, a);             \
-  } while (0)
-  switch (getenv("RLH_GRAM_ZDBG") ? atoi(getenv("RLH_GRAM_ZDBG")) : 0) {   // (timing-only builds: 1 no DMA, 2 no multiply)
-    case 1: RLH_ZG(1); break;
-    case 2: RLH_ZG(2); break;
-    case 3: RLH_ZG(3); break;
-    default: RLH_ZG(0); break;
+  static bool attr = false;
+  if (!attr) {
+    RLH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gram_z_dma_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kZgBuf));
+    attr = true;
   }
-#undef RLH_ZG
+  hipLaunchKernelGGL(gram_z_dma_kernel, dim3((unsigned)nb), dim3(1024), 2 * kZgBuf, c.stream, a);
   RLH_HIP(hipGetLastError());
   const int total = (int)(my * mx);
   hipLaunchKernelGGL(gram_z_finalize, dim3((total + 3) / 4), dim3(256), 0, c.stream, (const double *)c.work, (int)nb, (int)my,

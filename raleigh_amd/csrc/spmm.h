@@ -36,75 +36,161 @@ struct WideSched {         // launch order built for one (resident workgroups, p
   int64_t len;
 };
 
+namespace rlh {
+
+// n bytes of `src` in a new device allocation of max(bytes, at_least) bytes
+template <typename P>
+static inline int upload(P *&dst, const void *src, size_t bytes, size_t at_least = 0) {
+  RLH_HIP(hipMalloc((void **)&dst, std::max(bytes, at_least)));
+  RLH_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+  return 0;
+}
+
+// Launch order of a windowed layout's blocks.  Workgroup w of the persistent grid processes
+// sched[w], sched[w + grid], ...; workgroups w and w + 8 share an XCD and its L2 under the
+// observed round-robin placement, so the positions {r * grid + 8 i + x, i < per_xcd} are blocks that
+// XCD x works on at the same time.  A block's windows are mostly the own rows of other blocks
+// (the z planes of a 3-D stencil are the rows of the blocks n_y n_x / rows-per-block further on): the
+// schedule makes such blocks concurrent on one XCD, so that the window one of them stages is an
+// L2 hit left by the block that owns those rows, instead of a second and third trip over the fabric
+// (speed only: any order gives the same result).
+// position r * grid + 8 i + x  <-  member i of group g = 8 r + x of the ordered block list
+static inline void well_layout(const std::vector<int32_t> &order, int slots, std::vector<int32_t> &sched, int &grid) {
+  const int xcds = 8;
+  int per_xcd = slots / xcds;
+  if (per_xcd < 1) per_xcd = 1;
+  const int64_t nb = (int64_t)order.size();
+  if (nb <= (int64_t)xcds * per_xcd) {
+    grid = (int)nb;
+    sched = order;
+    return;
+  }
+  grid = xcds * per_xcd;
+  const int64_t ngroups = (nb + per_xcd - 1) / per_xcd;
+  const int64_t rounds = (ngroups + xcds - 1) / xcds;
+  sched.assign((size_t)(rounds * grid), -1);
+  for (int64_t k = 0; k < nb; ++k) {
+    const int64_t g = k / per_xcd, i = k % per_xcd;
+    sched[(size_t)((g / xcds) * grid + i * xcds + g % xcds)] = order[(size_t)k];
+  }
+}
+
+// The launch order of one windowed layout's units (the 1024-row blocks, or the stacks): the schedule of the whole operator
+// and, built on first use for a given own / halo boundary n_own, the two schedules of rlh_spmm_part (overlap of the halo
+// exchange with the interior rows) -- the units that reference only own columns, and the rest; each keeps the grouped
+// order of the full schedule.
+struct LaunchOrder {
+  int32_t *sched = nullptr;              // device: unit processed at launch position p (-1: none)
+  int64_t len = 0;
+  int grid = 0;                          // workgroups the schedule was laid out for
+  std::vector<int32_t> order, maxcol;    // host: the grouped order of the units; largest column each references
+  int64_t split_at = -1;                 // n_own the part schedules were built for (-1: none)
+  int32_t *part_sched[2] = {nullptr, nullptr};
+  int64_t part_len[2] = {0, 0};
+  int part_grid[2] = {0, 0};
+
+  // lays `order_` out for one workgroup per CU and uploads the schedule
+  int set(std::vector<int32_t> &&order_, std::vector<int32_t> &&maxcol_) {
+    order = std::move(order_);
+    maxcol = std::move(maxcol_);
+    return place(order, sched, len, grid);
+  }
+  int split(int64_t n_own) {
+    if (split_at == n_own) return 0;
+    release_parts();
+    std::vector<int32_t> part[2];
+    for (int32_t u : order) part[maxcol[(size_t)u] < n_own ? 0 : 1].push_back(u);
+    for (int k = 0; k < 2; ++k)
+      if (!part[k].empty())
+        if (int rc = place(part[k], part_sched[k], part_len[k], part_grid[k])) return rc;
+    split_at = n_own;
+    return 0;
+  }
+  // part 0: all units; 1 / 2: those without / with halo columns (after split); *grid_ == 0: nothing to launch
+  void pick(int part, const int32_t **sched_, int64_t *len_, int *grid_) const {
+    *sched_ = part == 0 ? sched : part_sched[part - 1];
+    *len_ = part == 0 ? len : part_len[part - 1];
+    *grid_ = part == 0 ? grid : part_grid[part - 1];
+  }
+  void release() {
+    if (sched) (void)hipFree(sched);
+    sched = nullptr;
+    len = 0;
+    grid = 0;
+    release_parts();
+  }
+
+ private:
+  static int place(const std::vector<int32_t> &units, int32_t *&d_sched, int64_t &d_len, int &d_grid) {
+    std::vector<int32_t> host;
+    well_layout(units, ctx().num_cu, host, d_grid);
+    d_len = (int64_t)host.size();
+    return upload(d_sched, host.data(), host.size() * sizeof(int32_t));
+  }
+  void release_parts() {
+    for (int k = 0; k < 2; ++k) {
+      if (part_sched[k]) (void)hipFree(part_sched[k]);
+      part_sched[k] = nullptr;
+      part_len[k] = 0;
+      part_grid[k] = 0;
+    }
+    split_at = -1;
+  }
+};
+
+}  // namespace rlh
+
 struct rlh_csr {
-  int dtype;
-  int64_t n_rows, n_cols, nnz;
-  int64_t n_slices;
-  int64_t padded;          // stored entries incl. padding
-  int64_t *slice_ptr;      // device, n_slices + 1 (entry offsets)
-  int32_t *cols;           // device, padded
-  void *vals;              // device, padded
-  int64_t device_bytes;
+  int dtype = 0;
+  int64_t n_rows = 0, n_cols = 0, nnz = 0;
+  int64_t n_slices = 0;
+  int64_t padded = 0;                // stored entries incl. padding
+  int64_t *slice_ptr = nullptr;      // device, n_slices + 1 (entry offsets)
+  int32_t *cols = nullptr;           // device, padded
+  void *vals = nullptr;              // device, padded
+  int64_t device_bytes = 0;
   // 1024-row windowed layout (rows of at most 8 entries, real types)
-  int64_t well_blocks;     // 0: not built
-  int well_wmax;           // register slots per row the kernel is instantiated for
-  WellMeta *well_meta;     // device, well_blocks
-  int32_t *well_gsrc;      // device: first column of every 64-entry staging group
-  uint16_t *well_idx;      // device: position of the entry's column in the staged image
-  void *well_vals;         // device
-  double well_ratio;       // staged elements per stored entry slot (diagnostic)
-  int32_t *well_sched;     // device: block processed at launch position p (-1: none)
-  int64_t well_sched_len;
-  int well_grid;           // workgroups the schedule was laid out for
-  // split of the blocks by "references a column >= n_own" (overlap of the halo exchange with the
-  // interior rows, rlh_spmm_part): host-side order / largest referenced column per block, and the
-  // two launch orders built on first use for a given n_own
-  std::vector<int32_t> well_order, well_maxcol;
-  int64_t well_split_at;   // n_own the split was built for (-1: none)
-  int32_t *well_sched_part[2];
-  int64_t well_sched_part_len[2];
-  int well_grid_part[2];
-  int well_inbounds;       // every staging group lies inside [0, n_cols)
-  int well_aligned;        // every staging group starts on a multiple of 8 columns
+  int64_t well_blocks = 0;           // 0: not built
+  int well_wmax = 0;                 // register slots per row the kernel is instantiated for
+  WellMeta *well_meta = nullptr;     // device, well_blocks
+  int32_t *well_gsrc = nullptr;      // device: first column of every 64-entry staging group
+  uint16_t *well_idx = nullptr;      // device: position of the entry's column in the staged image
+  void *well_vals = nullptr;         // device
+  double well_ratio = 0.0;           // staged elements per stored entry slot (diagnostic)
+  rlh::LaunchOrder well_launch;      // of the blocks
+  int well_inbounds = 0;             // every staging group lies inside [0, n_cols)
+  int well_aligned = 0;              // every staging group starts on a multiple of 8 columns
   // the same layout over STACKS of row blocks (spmm.hip, "Stacked blocks"): a workgroup takes kStkR 1024-row blocks whose
   // windows overlap (for a 3-D stencil two blocks one grid plane apart) and stages the union of their windows once
-  int64_t stk_blocks;      // stacks; 0: not built
-  WellMeta *stk_meta;      // device, per stack (eoff counts slots: member r's 8 slots start at eoff + 8 r)
-  int32_t *stk_member;     // device, kStkR pairs per stack: (first row, rows) of the stack's row blocks ((0, 0): none)
-  int32_t *stk_gsrc;       // device
-  uint16_t *stk_idx;       // device
-  void *stk_vals;          // device
+  int64_t stk_blocks = 0;            // stacks; 0: not built
+  WellMeta *stk_meta = nullptr;      // device, per stack (eoff counts slots: member r's 8 slots start at eoff + 8 r)
+  int32_t *stk_member = nullptr;     // device, kStkR pairs per stack: (first row, rows) of the stack's row blocks ((0, 0): none)
+  int32_t *stk_gsrc = nullptr;       // device
+  uint16_t *stk_idx = nullptr;       // device
+  void *stk_vals = nullptr;          // device
   // value dictionary of the stacks (constant-coefficient stencils repeat a few dozen rows of values: 27 for the 7-point
   // Laplacian): per row the index of its 8-slot value tuple, and the table of distinct tuples -- 4 bytes per row
   // instead of 8 values; nullptr when the rows have more than kStkMaxPatterns distinct tuples
-  int32_t *stk_pat;        // device, [stack][member][row of the block]: value pattern | position pattern << 16
-  uint16_t *stk_dtab;      // device, [stack][member][kStkMaxDeltas][8]: positions minus the row's index in its block, per
-                           // position pattern of that member (a stencil's interior rows all share one); nullptr: none
-  void *stk_table;         // device, [pattern][8 values]
-  int64_t stk_npat;
-  int32_t *stk_sched;      // device
-  int64_t stk_sched_len;
-  int stk_grid;
-  int stk_gmax;           // largest number of staging groups of a stack
-  // the stacks without / with halo columns (rlh_spmm_part), as well_split keeps them for the blocks
-  std::vector<int32_t> stk_order, stk_maxcol;
-  int64_t stk_split_at;
-  int32_t *stk_sched_part[2];
-  int64_t stk_sched_part_len[2];
-  int stk_grid_part[2];
-  int stk_self;            // slot 7 of every row of the stacks holds the position of the row's own column (fused Chebyshev step)
-  int stk_aligned;         // every staging group of the stacks starts on a multiple of 8 columns
-  int stk_overhang;        // columns (< 8) the last staging group reaches past n_cols: the callers' leading dimensions must cover them
-  double stk_staged;       // staged elements per row and vector (diagnostic; the unstacked layout's: well_staged)
-  double well_staged;
+  int32_t *stk_pat = nullptr;        // device, [stack][member][row of the block]: value pattern | position pattern << 16
+  uint16_t *stk_dtab = nullptr;      // device, [stack][member][kStkMaxDeltas][8]: positions minus the row's index in its block, per
+                                     // position pattern of that member (a stencil's interior rows all share one); nullptr: none
+  void *stk_table = nullptr;         // device, [pattern][8 values]
+  int64_t stk_npat = 0;
+  rlh::LaunchOrder stk_launch;       // of the stacks
+  int stk_gmax = 0;                  // largest number of staging groups of a stack
+  int stk_self = 0;                  // slot 7 of every row of the stacks holds the position of the row's own column (fused Chebyshev step)
+  int stk_aligned = 0;               // every staging group of the stacks starts on a multiple of 8 columns
+  int stk_overhang = 0;              // columns (< 8) the last staging group reaches past n_cols: the callers' leading dimensions must cover them
+  double stk_staged = 0.0;           // staged elements per row and vector (diagnostic; the unstacked layout's: well_staged)
+  double well_staged = 0.0;
   // 256-row interleaved layout (any row length, any type)
-  int64_t wide_blocks;     // 0: not built
-  WideMeta *wide_meta;     // device
-  int32_t *wide_gsrc;      // device
-  void *wide_idx;          // device: 16-byte pieces of 8 positions, [chunk][row]
-  void *wide_vals;         // device: 16-byte pieces of values, [chunk][piece][row]
-  int wide_gmax;           // largest number of staging groups of a block
-  int wide_k;              // rows per thread of the interleaved layout: 2 where consecutive rows share their column pattern (FE nodes)
+  int64_t wide_blocks = 0;           // 0: not built
+  WideMeta *wide_meta = nullptr;     // device
+  int32_t *wide_gsrc = nullptr;      // device
+  void *wide_idx = nullptr;          // device: 16-byte pieces of 8 positions, [chunk][row]
+  void *wide_vals = nullptr;         // device: 16-byte pieces of values, [chunk][piece][row]
+  int wide_gmax = 0;                 // largest number of staging groups of a block
+  int wide_k = 1;                    // rows per thread of the interleaved layout: 2 where consecutive rows share their column pattern (FE nodes)
   std::vector<int32_t> wide_order, wide_maxcol;
   std::vector<WideSched> wide_scheds;
 };
@@ -294,35 +380,6 @@ static void parallel_blocks(int64_t nblocks, F fn) {
   for (unsigned t = 1; t < nt; ++t) pool.emplace_back(worker);
   worker();
   for (auto &t : pool) t.join();
-}
-
-// Launch order of a windowed layout's blocks.  Workgroup w of the persistent grid processes
-// sched[w], sched[w + grid], ...; workgroups w and w + 8 share an XCD and its L2 under the
-// observed round-robin placement, so the positions {r * grid + 8 i + x, i < per_xcd} are blocks that
-// XCD x works on at the same time.  A block's windows are mostly the own rows of other blocks
-// (the z planes of a 3-D stencil are the rows of the blocks n_y n_x / rows-per-block further on): the
-// schedule makes such blocks concurrent on one XCD, so that the window one of them stages is an
-// L2 hit left by the block that owns those rows, instead of a second and third trip over the fabric
-// (speed only: any order gives the same result).
-// position r * grid + 8 i + x  <-  member i of group g = 8 r + x of the ordered block list
-static inline void well_layout(const std::vector<int32_t> &order, int slots, std::vector<int32_t> &sched, int &grid) {
-  const int xcds = 8;
-  int per_xcd = slots / xcds;
-  if (per_xcd < 1) per_xcd = 1;
-  const int64_t nb = (int64_t)order.size();
-  if (nb <= (int64_t)xcds * per_xcd) {
-    grid = (int)nb;
-    sched = order;
-    return;
-  }
-  grid = xcds * per_xcd;
-  const int64_t ngroups = (nb + per_xcd - 1) / per_xcd;
-  const int64_t rounds = (ngroups + xcds - 1) / xcds;
-  sched.assign((size_t)(rounds * grid), -1);
-  for (int64_t k = 0; k < nb; ++k) {
-    const int64_t g = k / per_xcd, i = k % per_xcd;
-    sched[(size_t)((g / xcds) * grid + i * xcds + g % xcds)] = order[(size_t)k];
-  }
 }
 
 // Launch groups on the block-overlap graph.  A group is the `per_xcd` units one XCD works on at the same time: what it

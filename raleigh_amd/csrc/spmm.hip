@@ -684,10 +684,9 @@ __global__ __launch_bounds__(1024) void well_stack_kernel(const WellMeta *__rest
 // of this vector out of its slot and the R stores.  The compiler does not count asm loads, so every wait on the DMAs is
 // written here, from the number of DMAs this wave has issued after them (LDS-DMAs complete in order among themselves);
 // a stack with a ragged member (the last row block of the matrix) waits for vmcnt(0) instead.
-// Timing-only builds (DBG, profiles/r03_spmm_stack.txt) put the floor of this access pattern -- DMAs, stores and the
-// entries, no LDS reads -- at 1.09 of the kernel's 1.15-1.20 ms on lap3d 215^3 fp64; a version whose ring ran on across
-// the stack boundaries, with the next stack's entries prefetched into a second register set, measured the same and is
-// not kept.
+// The floor of this access pattern -- DMAs, stores and the entries, no LDS reads -- was measured at 1.09 of the kernel's
+// 1.15-1.20 ms on lap3d 215^3 fp64 (profiles/r03_spmm_stack.txt, section 5); a version whose ring ran on across the stack
+// boundaries, with the next stack's entries prefetched into a second register set, measured the same and is not kept.
 template <int N> __device__ __forceinline__ void wait_vm_le() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 
 // wait until at most n vector-memory operations of this wave are outstanding (s_waitcnt takes an immediate)
@@ -725,15 +724,13 @@ __device__ __forceinline__ void stk_store(c64 *p, c64 v) {
   __builtin_nontemporal_store(f64x2{v.re, v.im}, reinterpret_cast<f64x2 *>(p));
 }
 
-// (DBG: timing-only builds for tools/stack_bench.py -- 1: no DMA, 2: no LDS reads / arithmetic, 4: no stores: wrong
-// results; 8: plain instead of non-temporal stores)
 // CHEB (16-byte elements): the fused Chebyshev step  P = cy y + cp P + cb (B - A y)  on the same ring -- X is y (staged),
 // Y is P (read and written in place), y[row] comes out of the staged image (slot 7 of every row holds its own column's
 // position: stk_self).  P and B are ordinary loads, and ordinary loads and LDS-DMAs do not retire in order with each other
 // (see the waits below), so this variant never counts: every wait is for everything.  With the two slots of a 16-byte ring
 // that costs nothing in depth -- the DMA of vector j + 1 and the operands of vector j are in flight together while the
 // products of vector j are formed, one wait, then the update and its stores.
-template <typename T, int R, int LD, int DBG = 0, bool CHEB = false>
+template <typename T, int R, int LD, bool CHEB = false>
 __global__ __launch_bounds__(1024) void well_stack_dma_kernel(const WellMeta *__restrict__ meta,
                                                               const int32_t *__restrict__ member,
                                                               const int32_t *__restrict__ gsrc,
@@ -812,7 +809,7 @@ __global__ __launch_bounds__(1024) void well_stack_dma_kernel(const WellMeta *__
       const T *hsrc = H ? H + (int64_t)j * ldh - n_own : src;   // halo row of column c: hsrc[c] (pieces never lie across n_own)
 #pragma unroll
       for (int i = 0; i < LD; ++i) {
-        if (i >= mine || (DBG & 1)) break;
+        if (i >= mine) break;
         const T *g = (scol[i] < n_own ? src : hsrc) + scol[i];
         unsigned dst = slot + (unsigned)(wave + nw * i) * 1024u, keep;
         asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
@@ -830,16 +827,11 @@ __global__ __launch_bounds__(1024) void well_stack_dma_kernel(const WellMeta *__
         for (int t = 0; t < WMAX; t += 2) {
           unsigned w = ixb[r][t / 2];
           asm volatile("" : "+v"(w));              // (unpacked per vector: hoisted out of the loop the offsets take 16 registers)
-          if constexpr ((DBG & 2) != 0) acc = (t == (j & 6)) ? v[r][t] : acc;
-          else {
-            fma_acc(acc, v[r][t], *reinterpret_cast<const T *>(ldsb + ((w & 0xffffu) * (unsigned)sizeof(T) + boff)));
-            fma_acc(acc, v[r][t + 1], *reinterpret_cast<const T *>(ldsb + ((w >> 16) * (unsigned)sizeof(T) + boff)));
-          }
+          fma_acc(acc, v[r][t], *reinterpret_cast<const T *>(ldsb + ((w & 0xffffu) * (unsigned)sizeof(T) + boff)));
+          fma_acc(acc, v[r][t + 1], *reinterpret_cast<const T *>(ldsb + ((w >> 16) * (unsigned)sizeof(T) + boff)));
         }
         // (non-temporal stores: 1.107 against 1.140 ms with plain ones, variants taking turns in one process)
-        if constexpr ((DBG & 4) != 0) { if (ixb[r][0] == 0xfffffffeu) Y[(int64_t)row[r] + (int64_t)j * ldy] = acc; }
-        else if constexpr ((DBG & 8) != 0) { if (whole || row[r] >= 0) Y[(int64_t)row[r] + (int64_t)j * ldy] = acc; }
-        else if (whole || row[r] >= 0) stk_store(Y + (int64_t)row[r] + (int64_t)j * ldy, acc);
+        if (whole || row[r] >= 0) stk_store(Y + (int64_t)row[r] + (int64_t)j * ldy, acc);
       }
     };
     // every wave is done with the previous stack's slots (its last vectors were read after the last barrier)
@@ -896,11 +888,11 @@ __global__ __launch_bounds__(1024) void well_stack_dma_kernel(const WellMeta *__
       // but they are NOT counted as allowed: LDS-DMAs and ordinary vector-memory operations do not complete in order with
       // each other (seen with loads in the bfloat16 kernel below), and a store that has completed early would let an
       // unfinished DMA through the count; if they are still outstanding this waits for one more vector than necessary
-      // (RLH_SPMM_STACK_DBG & 16 counts them as before: the same time to within the noise).
+      // (counting them as allowed measured the same time to within the noise: profiles/r03_spmm_stack.txt).
       const int later = m - 1 - j < D - 1 ? m - 1 - j : D - 1;
       // (a short member -- the last block of the matrix, or the plane-aligned blocks -- changes nothing here: the count
       // rests on the DMAs alone, whatever stores a wave does or does not issue)
-      wait_vm_outstanding(((DBG & 1) ? 0 : later * mine) + ((DBG & 16) && whole ? (j < D ? j : D) * nmem : 0));
+      wait_vm_outstanding(later * mine);
       __builtin_amdgcn_s_barrier();
       if (j + D < m) issue(j + D);
       compute(j);
@@ -1089,9 +1081,10 @@ static int launch_well_we(const rlh_csr *h, int part, int64_t m, const T *X, int
                           int64_t ldh, T *Y, int64_t ldy, const ChebArgs<T> *cheb) {
   Context &c = ctx();
   // launch order: all blocks, or the blocks without / with halo columns (rlh_spmm_part)
-  const int32_t *sched = part == 0 ? h->well_sched : h->well_sched_part[part - 1];
-  const int64_t sched_len = part == 0 ? h->well_sched_len : h->well_sched_part_len[part - 1];
-  const int64_t nb = part == 0 ? h->well_grid : h->well_grid_part[part - 1];   // one workgroup per CU, persistent
+  const int32_t *sched;
+  int64_t sched_len;
+  int nb;                                               // one workgroup per CU, persistent
+  h->well_launch.pick(part, &sched, &sched_len, &nb);
   if (nb == 0) return 0;
   const int cps_cap = env_int("RLH_SPMM_CPS", 8);       // vectors per step (tunable)
   if (cheb)
@@ -1143,8 +1136,9 @@ constexpr int kBfImageBytes = 16 * 1024;           // ng <= 128 groups of 64 two
 constexpr int kBfRingBytes = 64 * 1024;
 constexpr int kBfOperandBytes = 6 * 1024;          // per wave: [member][p, b, y] x 64 lanes x 16 bytes (its first 2 KB double as the tile)
 
-// (DBG: timing-only builds -- 1: no y DMAs, 2: no row products, 4: no operand DMAs / no update: wrong results)
-template <int R, int VPS, int DBG = 0>
+// (where the step's time goes -- y DMAs, row products, operand DMAs and update taken out in turn -- is measured in
+// profiles/r03_spmm_stack.txt, section 10)
+template <int R, int VPS>
 __global__ __launch_bounds__(1024) void well_stack_cheb_bf16_kernel(const WellMeta *__restrict__ meta,
                                                                     const int32_t *__restrict__ member,
                                                                     const int32_t *__restrict__ gsrc,
@@ -1214,7 +1208,7 @@ __global__ __launch_bounds__(1024) void well_stack_cheb_bf16_kernel(const WellMe
     }
     asm volatile("" : "+v"(scol));
     auto issue = [&](int j, unsigned par) {        // the images of vectors j, j + 1 (clamped) into slot `par`
-      if (!mine || (DBG & 1)) return;
+      if (!mine) return;
 #pragma unroll
       for (int u = 0; u < VPS; ++u) {
         const int jv = j + u < m ? j + u : m - 1;
@@ -1235,7 +1229,6 @@ __global__ __launch_bounds__(1024) void well_stack_cheb_bf16_kernel(const WellMe
         if (r >= nmem) break;
         const int64_t r8 = row0[r] + rg * 8;
         const int64_t rc = r8 + 8 <= n_rows ? r8 : 0;
-        if constexpr ((DBG & 4) != 0) continue;
         dma16(P + (int64_t)jc * ldp + rc, opbase + (unsigned)(r * 3 + 0) * 1024u);
         dma16(B + (int64_t)jc * ldb + rc, opbase + (unsigned)(r * 3 + 1) * 1024u);
         dma16(Yk + (int64_t)jc * ldy + rc, opbase + (unsigned)(r * 3 + 2) * 1024u);
@@ -1258,7 +1251,7 @@ __global__ __launch_bounds__(1024) void well_stack_cheb_bf16_kernel(const WellMe
           // (a wave that moves no image has nothing to wait for here -- and must not: a wait would make it, and through
           // the barrier every wave, sit out the acknowledgement of its last stores)
           if (!whole) wait_vm_le<0>();
-          else if (mine) wait_vm_outstanding(jj == 0 && !(DBG & 4) ? 3 * nmem : 0);
+          else if (mine) wait_vm_outstanding(jj == 0 ? 3 * nmem : 0);
           __builtin_amdgcn_s_barrier();
           const int jn = jj + VPS < cnt ? j + VPS : j0 + 8;          // first vector of the next step
           if (jn < m) issue(jn, par ^ 1u);
@@ -1270,8 +1263,6 @@ __global__ __launch_bounds__(1024) void well_stack_cheb_bf16_kernel(const WellMe
             for (int r = 0; r < R; ++r) {
               if (r >= nmem) break;
               float a = 0.f;
-              if constexpr ((DBG & 2) != 0) a = v[r][(jj + u) & 7];
-              else
 #pragma unroll
               for (int t = 0; t < WMAX; t += 2) {
                 unsigned w = ixb[r][t / 2];
@@ -1294,7 +1285,6 @@ __global__ __launch_bounds__(1024) void well_stack_cheb_bf16_kernel(const WellMe
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         if (r >= nmem) break;
-        if constexpr ((DBG & 4) != 0) { if (acc[r][0] == 1.2345e30f) P[0] = 0; continue; }
         union { rlh_u32x4e u; unsigned short e[8]; } pu, bu, yu, ou;
         pu.u = *reinterpret_cast<const rlh_u32x4e *>(ldsb + opbase + (unsigned)(r * 3 + 0) * 1024u + (unsigned)lane * 16u);
         bu.u = *reinterpret_cast<const rlh_u32x4e *>(ldsb + opbase + (unsigned)(r * 3 + 1) * 1024u + (unsigned)lane * 16u);
@@ -1328,74 +1318,57 @@ __global__ __launch_bounds__(1024) void well_stack_cheb_bf16_kernel(const WellMe
       // no counted wait ever has to sit out their acknowledgement
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       if (j0 + 8 < m) operands(j0 + 8);
-      if constexpr ((DBG & 4) == 0) {
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-          if (r >= nmem) break;
-          const int64_t r8 = row0[r] + rg * 8;
-          if ((whole || r8 + 8 <= n_rows) && act) *reinterpret_cast<rlh_u32x4e *>(P + (int64_t)jv * ldp + r8) = outs[r];
-        }
+      for (int r = 0; r < R; ++r) {
+        if (r >= nmem) break;
+        const int64_t r8 = row0[r] + rg * 8;
+        if ((whole || r8 + 8 <= n_rows) && act) *reinterpret_cast<rlh_u32x4e *>(P + (int64_t)jv * ldp + r8) = outs[r];
       }
     }
   }
+}
+
+// one launch of the LDS-DMA stack kernel (CHEB: its fused Chebyshev step)
+template <typename T, bool CHEB>
+static int launch_stack_dma(const rlh_csr *h, const int32_t *pat, const int32_t *sched, int64_t sched_len, int grid, int64_t m,
+                            const T *X, int64_t ldx, int64_t n_own, const T *H, int64_t ldh, T *Y, int64_t ldy,
+                            const ChebArgs<T> &cheb) {
+  constexpr int LD = 5;                                  // 16-byte pieces per issuing wave and vector (<= 80 pieces)
+  static bool attr_dma = false;
+  if (!attr_dma) {
+    RLH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&well_stack_dma_kernel<T, kStkR, LD, CHEB>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, kStkLdsBytes));
+    attr_dma = true;
+  }
+  hipLaunchKernelGGL((well_stack_dma_kernel<T, kStkR, LD, CHEB>), dim3((unsigned)grid), dim3(1024), kStkLdsBytes,
+                     ctx().stream, h->stk_meta, h->stk_member, h->stk_gsrc, h->stk_idx,
+                     pat ? (const T *)h->stk_table : (const T *)h->stk_vals, pat, pat ? h->stk_dtab : nullptr, h->n_rows,
+                     sched, sched_len, X, ldx, n_own, H, ldh, Y, ldy, (int)m, cheb);
+  RLH_HIP(hipGetLastError());
+  return 0;
 }
 
 template <typename T>
 static int launch_stack(const rlh_csr *h, int part, int64_t m, const T *X, int64_t ldx, int64_t n_own, const T *H,
                         int64_t ldh, T *Y, int64_t ldy, bool dma, const ChebArgs<T> *cheb = nullptr) {
   Context &c = ctx();
-  const int32_t *sched = part == 0 ? h->stk_sched : h->stk_sched_part[part - 1];
-  const int64_t sched_len = part == 0 ? h->stk_sched_len : h->stk_sched_part_len[part - 1];
-  const int grid = part == 0 ? h->stk_grid : h->stk_grid_part[part - 1];
+  const int32_t *sched;
+  int64_t sched_len;
+  int grid;
+  h->stk_launch.pick(part, &sched, &sched_len, &grid);
   if (grid == 0) return 0;
   constexpr bool cplx = std::is_same<T, c32>::value || std::is_same<T, c64>::value;
   if (dma) {
     constexpr int EPL = 16 / (int)sizeof(T);
     const int32_t *pat = sizeof(T) < 16 && env_int("RLH_SPMM_STACK_PAT", 1) != 0 ? h->stk_pat : nullptr;   // the value dictionary, where the handle has one
-    const int ld = 5;                                                  // 16-byte pieces per issuing wave and vector (<= 80 pieces)
-#define RLH_STK_DMA(LD_, ...)                                                                                           \
-    do {                                                                                                                \
-      static bool attr_dma = false;                                                                                     \
-      if (!attr_dma) {                                                                                                  \
-        RLH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&well_stack_dma_kernel<T, kStkR, LD_ __VA_ARGS__>),  \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, kStkLdsBytes));                         \
-        attr_dma = true;                                                                                                \
-      }                                                                                                                 \
-      hipLaunchKernelGGL((well_stack_dma_kernel<T, kStkR, LD_ __VA_ARGS__>), dim3((unsigned)grid), dim3(1024),          \
-                         kStkLdsBytes, c.stream, h->stk_meta, h->stk_member, h->stk_gsrc, h->stk_idx,                   \
-                         pat ? (const T *)h->stk_table : (const T *)h->stk_vals, pat, pat ? h->stk_dtab : nullptr,      \
-                         h->n_rows, sched, sched_len, X, ldx, n_own, H, ldh, Y, ldy, (int)m,                            \
-                         cheb ? *cheb : ChebArgs<T>{});                                                                 \
-    } while (0)
-    const int dbg = env_int("RLH_SPMM_STACK_DBG", 0);
     RLH_REQUIRE(h->stk_gmax <= 80 * EPL, "rlh_spmm: a stack of %d staging groups", h->stk_gmax);   // (a slot holds 40 or 80 pieces)
     if (cheb) {
-      if constexpr (sizeof(T) == 16) {
-        RLH_STK_DMA(5, , 0, true);
-        RLH_HIP(hipGetLastError());
-        return 0;
-      } else {
+      if constexpr (sizeof(T) == 16)
+        return launch_stack_dma<T, true>(h, pat, sched, sched_len, grid, m, X, ldx, n_own, H, ldh, Y, ldy, *cheb);
+      else
         RLH_REQUIRE(false, "rlh_spmm_cheb: the stacked fused step exists for 16-byte elements only");
-      }
     }
-    if (dbg && std::is_same<T, double>::value) {
-      if constexpr (std::is_same<T, double>::value) {
-        switch (dbg) {
-          case 1: RLH_STK_DMA(5, , 1); break;
-          case 2: RLH_STK_DMA(5, , 2); break;
-          case 3: RLH_STK_DMA(5, , 3); break;
-          case 4: RLH_STK_DMA(5, , 4); break;
-          case 5: RLH_STK_DMA(5, , 5); break;
-          case 6: RLH_STK_DMA(5, , 6); break;
-          case 7: RLH_STK_DMA(5, , 7); break;
-          case 8: RLH_STK_DMA(5, , 8); break;
-          default: RLH_STK_DMA(5, , 16); break;
-        }
-      }
-    } else RLH_STK_DMA(5);
-#undef RLH_STK_DMA
-    RLH_HIP(hipGetLastError());
-    return 0;
+    return launch_stack_dma<T, false>(h, pat, sched, sched_len, grid, m, X, ldx, n_own, H, ldh, Y, ldy, ChebArgs<T>{});
   }
   RLH_REQUIRE(part == 0 && H == nullptr, "rlh_spmm: the register-staged stack kernel takes the whole operator only");
   if constexpr (!cplx) {
@@ -1406,9 +1379,9 @@ static int launch_stack(const rlh_csr *h, int part, int64_t m, const T *X, int64
       attr = true;
     }
     const int cps_cap = env_int("RLH_SPMM_CPS", 8);
-    hipLaunchKernelGGL((well_stack_kernel<T, kStkR>), dim3((unsigned)h->stk_grid), dim3(1024), 2 * kStkBufBytes, c.stream,
-                       h->stk_meta, h->stk_member, h->stk_gsrc, h->stk_idx, (const T *)h->stk_vals, h->n_rows, h->stk_sched,
-                       h->stk_sched_len, X, ldx, Y, ldy, (int)m, cps_cap < 1 ? 1 : cps_cap);
+    hipLaunchKernelGGL((well_stack_kernel<T, kStkR>), dim3((unsigned)grid), dim3(1024), 2 * kStkBufBytes, c.stream,
+                       h->stk_meta, h->stk_member, h->stk_gsrc, h->stk_idx, (const T *)h->stk_vals, h->n_rows, sched,
+                       sched_len, X, ldx, Y, ldy, (int)m, cps_cap < 1 ? 1 : cps_cap);
     RLH_HIP(hipGetLastError());
   }
   return 0;
@@ -1420,9 +1393,6 @@ static int launch_well(const rlh_csr *h, int part, int64_t m, const T *X, int64_
   // (rows of more than 8 entries and the complex types use the interleaved layout, spmm_wide.inc)
   return launch_well_w<T, 8>(h, part, m, X, ldx, n_own, H, ldh, Y, ldy, cheb);
 }
-
-static int well_split(rlh_csr *h, int64_t n_own);
-static int stack_split(rlh_csr *h, int64_t n_own);
 
 // Y = A X on the stacked layout where the handle has one and the call fits it: the whole operator on own columns with
 // either kernel; with a halo block, or on the interior / boundary part of the rows (rlh_spmm_part), the LDS-DMA kernel,
@@ -1462,7 +1432,7 @@ static int stack_dispatch(rlh_csr *h, int part, int64_t m, const T *X, int64_t l
       return 0;
     }
     if (part != 0)
-      if (int rc = stack_split(h, n_own)) return rc;
+      if (int rc = h->stk_launch.split(n_own)) return rc;
   }
   if (cheb && !dma) return 0;
   *done = true;
@@ -1513,7 +1483,7 @@ static int spmm_impl(rlh_csr *h, int part, int64_t m, const void *X_, int64_t ld
   if constexpr (!DType<DT>::cplx) {
     if (h->well_blocks > 0) {
       if (part != 0)
-        if (int rc = well_split(h, n_own)) return rc;
+        if (int rc = h->well_launch.split(n_own)) return rc;
       return launch_well<T>(h, part, m, X, ldx, n_own, H, ldh, Y, ldy, cheb);
     }
   }
@@ -1586,68 +1556,19 @@ static int csr_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices, 
   }
   h->n_slices = ns;
   h->padded = padded;
-  RLH_HIP(hipMalloc((void **)&h->slice_ptr, (size_t)(ns + 1) * sizeof(int64_t)));
-  RLH_HIP(hipMemcpy(h->slice_ptr, sp.data(), (size_t)(ns + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+  if (int rc = upload(h->slice_ptr, sp.data(), (size_t)(ns + 1) * sizeof(int64_t))) return rc;
   if (padded > 0) {
-    RLH_HIP(hipMalloc((void **)&h->cols, (size_t)padded * sizeof(int32_t)));
-    RLH_HIP(hipMalloc((void **)&h->vals, (size_t)padded * sizeof(T)));
-    RLH_HIP(hipMemcpy(h->cols, cols.data(), (size_t)padded * sizeof(int32_t), hipMemcpyHostToDevice));
-    RLH_HIP(hipMemcpy(h->vals, vals.data(), (size_t)padded * sizeof(T), hipMemcpyHostToDevice));
+    if (int rc = upload(h->cols, cols.data(), (size_t)padded * sizeof(int32_t))) return rc;
+    if (int rc = upload(h->vals, vals.data(), (size_t)padded * sizeof(T))) return rc;
   }
   h->device_bytes = (ns + 1) * 8 + padded * (4 + (int64_t)sizeof(T));
   return 0;
 }
 
 
-// The two launch orders of rlh_spmm_part for the own / halo boundary n_own: blocks that reference
-// only own columns, and the rest (each keeps the grouped order of the full schedule).
-static int well_split(rlh_csr *h, int64_t n_own) {
-  if (h->well_split_at == n_own) return 0;
-  for (int k = 0; k < 2; ++k) {
-    if (h->well_sched_part[k]) (void)hipFree(h->well_sched_part[k]);
-    h->well_sched_part[k] = nullptr;
-    h->well_sched_part_len[k] = 0;
-    h->well_grid_part[k] = 0;
-  }
-  std::vector<int32_t> part[2];
-  for (int32_t b : h->well_order) part[h->well_maxcol[(size_t)b] < n_own ? 0 : 1].push_back(b);
-  for (int k = 0; k < 2; ++k) {
-    if (part[k].empty()) continue;
-    std::vector<int32_t> sched;
-    well_layout(part[k], ctx().num_cu, sched, h->well_grid_part[k]);
-    h->well_sched_part_len[k] = (int64_t)sched.size();
-    RLH_HIP(hipMalloc((void **)&h->well_sched_part[k], sched.size() * sizeof(int32_t)));
-    RLH_HIP(hipMemcpy(h->well_sched_part[k], sched.data(), sched.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  }
-  h->well_split_at = n_own;
-  return 0;
-}
-
 template <int DT>
 static int stack_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices, const void *values_,
                        const std::vector<std::vector<Win>> &wins, int64_t staged_unstacked);
-
-static int stack_split(rlh_csr *h, int64_t n_own) {       // (well_split for the stacks)
-  if (h->stk_split_at == n_own) return 0;
-  for (int k = 0; k < 2; ++k) {
-    if (h->stk_sched_part[k]) (void)hipFree(h->stk_sched_part[k]);
-    h->stk_sched_part[k] = nullptr;
-    h->stk_sched_part_len[k] = 0;
-    h->stk_grid_part[k] = 0;
-  }
-  std::vector<int32_t> part[2];
-  for (int32_t sb : h->stk_order) part[h->stk_maxcol[(size_t)sb] < n_own ? 0 : 1].push_back(sb);
-  for (int k = 0; k < 2; ++k) {
-    if (part[k].empty()) continue;
-    std::vector<int32_t> sched;
-    well_layout(part[k], ctx().num_cu, sched, h->stk_grid_part[k]);
-    h->stk_sched_part_len[k] = (int64_t)sched.size();
-    RLH_HIP(hipMalloc((void **)&h->stk_sched_part[k], sched.size() * sizeof(int32_t)));
-    RLH_HIP(hipMemcpy(h->stk_sched_part[k], sched.data(), sched.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  }
-  h->stk_split_at = n_own;
-  return 0;
-}
 
 // Host side of the 1024-row windowed layout.  Returns 0 with h->well_blocks == 0 when the matrix
 // does not qualify (a row longer than 8 entries, a block whose windows do not fit the LDS buffer,
@@ -1745,26 +1666,18 @@ static int well_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices,
     if ((int64_t)gsrc[g] + 64 > h->n_cols) h->well_inbounds = 0;
     if (gsrc[g] & 7) h->well_aligned = 0;
   }
-  std::vector<int32_t> sched;
-  well_schedule(wins, nblocks, n, kWellRows, ctx().num_cu, h->well_order);
-  well_layout(h->well_order, ctx().num_cu, sched, h->well_grid);
+  std::vector<int32_t> order, maxcol((size_t)nblocks);
+  well_schedule(wins, nblocks, n, kWellRows, ctx().num_cu, order);
+  for (int64_t b = 0; b < nblocks; ++b) maxcol[(size_t)b] = wins[b].back().start + wins[b].back().len - 1;
   clk.lap("well: schedule");
-  h->well_maxcol.resize((size_t)nblocks);
-  for (int64_t b = 0; b < nblocks; ++b) h->well_maxcol[(size_t)b] = wins[b].back().start + wins[b].back().len - 1;
-  h->well_sched_len = (int64_t)sched.size();
-  RLH_HIP(hipMalloc((void **)&h->well_sched, sched.size() * sizeof(int32_t)));
-  RLH_HIP(hipMemcpy(h->well_sched, sched.data(), sched.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  RLH_HIP(hipMalloc((void **)&h->well_meta, (size_t)nblocks * sizeof(WellMeta)));
-  RLH_HIP(hipMemcpy(h->well_meta, meta.data(), (size_t)nblocks * sizeof(WellMeta), hipMemcpyHostToDevice));
-  RLH_HIP(hipMalloc((void **)&h->well_gsrc, (size_t)std::max<int64_t>(goff, 1) * sizeof(int32_t)));
-  RLH_HIP(hipMemcpy(h->well_gsrc, gsrc.data(), (size_t)goff * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (int rc = h->well_launch.set(std::move(order), std::move(maxcol))) return rc;
+  if (int rc = upload(h->well_meta, meta.data(), (size_t)nblocks * sizeof(WellMeta))) return rc;
+  if (int rc = upload(h->well_gsrc, gsrc.data(), (size_t)goff * sizeof(int32_t), sizeof(int32_t))) return rc;
   const size_t ne = (size_t)(eoff + epad) * kWellRows;
-  RLH_HIP(hipMalloc((void **)&h->well_idx, std::max<size_t>(ne, 1) * sizeof(uint16_t)));
-  RLH_HIP(hipMalloc((void **)&h->well_vals, std::max<size_t>(ne, 1) * sizeof(T)));
-  RLH_HIP(hipMemcpy(h->well_idx, idx.data(), ne * sizeof(uint16_t), hipMemcpyHostToDevice));
-  RLH_HIP(hipMemcpy(h->well_vals, vals.data(), ne * sizeof(T), hipMemcpyHostToDevice));
+  if (int rc = upload(h->well_idx, idx.data(), ne * sizeof(uint16_t), sizeof(uint16_t))) return rc;
+  if (int rc = upload(h->well_vals, vals.data(), ne * sizeof(T), sizeof(T))) return rc;
   h->padded = eoff * kWellRows;
-  h->device_bytes = nblocks * (int64_t)sizeof(WellMeta) + (int64_t)sched.size() * 4 + goff * 4 + (int64_t)ne * (2 + (int64_t)sizeof(T));
+  h->device_bytes = nblocks * (int64_t)sizeof(WellMeta) + h->well_launch.len * 4 + goff * 4 + (int64_t)ne * (2 + (int64_t)sizeof(T));
   h->well_blocks = nblocks;
   h->well_staged = (double)staged / (double)n;
   clk.lap("well: upload");
@@ -2037,10 +1950,8 @@ static int stack_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices
   h->stk_aligned = 1;
   for (int64_t g = 0; g < goff; ++g)
     if (gsrc[(size_t)g] & 7) h->stk_aligned = 0;
-  h->stk_maxcol.resize((size_t)nst);
-  for (int64_t sb = 0; sb < nst; ++sb) h->stk_maxcol[(size_t)sb] = swins[(size_t)sb].back().start + swins[(size_t)sb].back().len - 1;
-  std::vector<int32_t> &order = h->stk_order;
-  std::vector<int32_t> sched;
+  std::vector<int32_t> order, maxcol((size_t)nst);
+  for (int64_t sb = 0; sb < nst; ++sb) maxcol[(size_t)sb] = swins[(size_t)sb].back().start + swins[(size_t)sb].back().len - 1;
   std::vector<int32_t> granule_owner((size_t)((n + kWellRows - 1) / kWellRows), -1);      // the stack that owns row 1024 c
   {
     int64_t blk = 0;
@@ -2050,13 +1961,9 @@ static int stack_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices
     }
   }
   well_schedule(swins, nst, n, kWellRows, ctx().num_cu, order, &granule_owner);
-  well_layout(order, ctx().num_cu, sched, h->stk_grid);
   clk.lap("stack: schedule");
-  h->stk_sched_len = (int64_t)sched.size();
-  RLH_HIP(hipMalloc((void **)&h->stk_sched, sched.size() * sizeof(int32_t)));
-  RLH_HIP(hipMemcpy(h->stk_sched, sched.data(), sched.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  RLH_HIP(hipMalloc((void **)&h->stk_meta, (size_t)nst * sizeof(WellMeta)));
-  RLH_HIP(hipMemcpy(h->stk_meta, meta.data(), (size_t)nst * sizeof(WellMeta), hipMemcpyHostToDevice));
+  if (int rc = h->stk_launch.set(std::move(order), std::move(maxcol))) return rc;
+  if (int rc = upload(h->stk_meta, meta.data(), (size_t)nst * sizeof(WellMeta))) return rc;
   {
     std::vector<int32_t> ranges(members.size() * 2, 0);                   // (first row, rows) of every member; (0, 0): none
     for (size_t k = 0; k < members.size(); ++k)
@@ -2064,11 +1971,9 @@ static int stack_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices
         ranges[2 * k] = (int32_t)brow[(size_t)members[k]];
         ranges[2 * k + 1] = (int32_t)(brow[(size_t)members[k] + 1] - brow[(size_t)members[k]]);
       }
-    RLH_HIP(hipMalloc((void **)&h->stk_member, ranges.size() * sizeof(int32_t)));
-    RLH_HIP(hipMemcpy(h->stk_member, ranges.data(), ranges.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (int rc = upload(h->stk_member, ranges.data(), ranges.size() * sizeof(int32_t))) return rc;
   }
-  RLH_HIP(hipMalloc((void **)&h->stk_gsrc, (size_t)std::max<int64_t>(goff, 1) * sizeof(int32_t)));
-  RLH_HIP(hipMemcpy(h->stk_gsrc, gsrc.data(), (size_t)goff * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (int rc = upload(h->stk_gsrc, gsrc.data(), (size_t)goff * sizeof(int32_t), sizeof(int32_t))) return rc;
   // value dictionary: the distinct 8-slot value tuples of the rows (byte-wise), given up beyond kStkMaxPatterns
   {
     std::vector<int32_t> pat((size_t)nst * R * kWellRows, 0);
@@ -2139,23 +2044,18 @@ static int stack_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices
     h->stk_npat = 0;
     if (ok && !table.empty()) {
       if (dok) {
-        RLH_HIP(hipMalloc((void **)&h->stk_dtab, dtab.size() * sizeof(uint16_t)));
-        RLH_HIP(hipMemcpy(h->stk_dtab, dtab.data(), dtab.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        if (int rc = upload(h->stk_dtab, dtab.data(), dtab.size() * sizeof(uint16_t))) return rc;
         h->device_bytes += (int64_t)dtab.size() * 2;
       }
       h->stk_npat = (int64_t)table.size() / 8;
-      RLH_HIP(hipMalloc((void **)&h->stk_pat, pat.size() * sizeof(int32_t)));
-      RLH_HIP(hipMemcpy(h->stk_pat, pat.data(), pat.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-      RLH_HIP(hipMalloc((void **)&h->stk_table, table.size() * sizeof(T)));
-      RLH_HIP(hipMemcpy(h->stk_table, table.data(), table.size() * sizeof(T), hipMemcpyHostToDevice));
+      if (int rc = upload(h->stk_pat, pat.data(), pat.size() * sizeof(int32_t))) return rc;
+      if (int rc = upload(h->stk_table, table.data(), table.size() * sizeof(T))) return rc;
       h->device_bytes += (int64_t)pat.size() * 4 + (int64_t)table.size() * (int64_t)sizeof(T);
     }
   }
-  RLH_HIP(hipMalloc((void **)&h->stk_idx, ne * sizeof(uint16_t)));
-  RLH_HIP(hipMalloc((void **)&h->stk_vals, ne * sizeof(T)));
-  RLH_HIP(hipMemcpy(h->stk_idx, idx.data(), ne * sizeof(uint16_t), hipMemcpyHostToDevice));
-  RLH_HIP(hipMemcpy(h->stk_vals, vals.data(), ne * sizeof(T), hipMemcpyHostToDevice));
-  h->device_bytes += nst * (int64_t)sizeof(WellMeta) + (int64_t)sched.size() * 4 + goff * 4 + (int64_t)members.size() * 8 +
+  if (int rc = upload(h->stk_idx, idx.data(), ne * sizeof(uint16_t))) return rc;
+  if (int rc = upload(h->stk_vals, vals.data(), ne * sizeof(T))) return rc;
+  h->device_bytes += nst * (int64_t)sizeof(WellMeta) + h->stk_launch.len * 4 + goff * 4 + (int64_t)members.size() * 8 +
                      (int64_t)ne * (2 + (int64_t)sizeof(T));
   h->stk_blocks = nst;
   clk.lap("stack: upload");
@@ -2298,19 +2198,6 @@ int rlh_csr_create(rlh_csr_t *out, int dtype, int64_t n_rows, int64_t n_cols, co
   clk.lap("argument checks");
   rlh_csr *h = new rlh_csr();
   h->dtype = dtype; h->n_rows = n_rows; h->n_cols = n_cols; h->nnz = nnz;
-  h->slice_ptr = nullptr; h->cols = nullptr; h->vals = nullptr;
-  h->well_blocks = 0; h->well_meta = nullptr; h->well_gsrc = nullptr; h->well_idx = nullptr; h->well_vals = nullptr;
-  h->well_ratio = 0.0; h->well_sched = nullptr; h->well_sched_len = 0; h->well_grid = 0; h->well_inbounds = 0; h->well_aligned = 0;
-  h->stk_self = 0;
-  h->stk_blocks = 0; h->stk_meta = nullptr; h->stk_member = nullptr; h->stk_gsrc = nullptr; h->stk_idx = nullptr;
-  h->stk_split_at = -1; h->stk_sched_part[0] = h->stk_sched_part[1] = nullptr; h->stk_sched_part_len[0] = h->stk_sched_part_len[1] = 0;
-  h->stk_grid_part[0] = h->stk_grid_part[1] = 0; h->stk_aligned = 0; h->stk_gmax = 0; h->stk_overhang = 0;
-  h->stk_pat = nullptr; h->stk_table = nullptr; h->stk_npat = 0; h->stk_dtab = nullptr;
-  h->stk_vals = nullptr; h->stk_sched = nullptr; h->stk_sched_len = 0; h->stk_grid = 0; h->stk_staged = 0.0; h->well_staged = 0.0;
-  h->well_split_at = -1; h->well_sched_part[0] = h->well_sched_part[1] = nullptr;
-  h->well_sched_part_len[0] = h->well_sched_part_len[1] = 0; h->well_grid_part[0] = h->well_grid_part[1] = 0;
-  h->wide_blocks = 0; h->wide_meta = nullptr; h->wide_gsrc = nullptr; h->wide_idx = nullptr; h->wide_vals = nullptr;
-  h->wide_gmax = 0; h->wide_k = 1; h->n_slices = 0; h->padded = 0; h->device_bytes = 0; h->well_wmax = 0;
   // Layout (RLH_SPMM_FORMAT=sell|well|wide overrides the choice and the locality test; read per
   // handle so tests can cover all three): rows of at most 8 entries of a real type -> the 1024-row
   // windowed layout; otherwise, or when that one does not qualify -> the 256-row interleaved
@@ -2371,7 +2258,6 @@ int rlh_csr_destroy(rlh_csr_t h) {
     if (h->well_gsrc) (void)hipFree(h->well_gsrc);
     if (h->well_idx) (void)hipFree(h->well_idx);
     if (h->well_vals) (void)hipFree(h->well_vals);
-    if (h->well_sched) (void)hipFree(h->well_sched);
     if (h->stk_meta) (void)hipFree(h->stk_meta);
     if (h->stk_member) (void)hipFree(h->stk_member);
     if (h->stk_gsrc) (void)hipFree(h->stk_gsrc);
@@ -2380,11 +2266,8 @@ int rlh_csr_destroy(rlh_csr_t h) {
     if (h->stk_pat) (void)hipFree(h->stk_pat);
     if (h->stk_table) (void)hipFree(h->stk_table);
     if (h->stk_dtab) (void)hipFree(h->stk_dtab);
-    if (h->stk_sched) (void)hipFree(h->stk_sched);
-    for (int k = 0; k < 2; ++k)
-      if (h->stk_sched_part[k]) (void)hipFree(h->stk_sched_part[k]);
-    for (int k = 0; k < 2; ++k)
-      if (h->well_sched_part[k]) (void)hipFree(h->well_sched_part[k]);
+    h->well_launch.release();
+    h->stk_launch.release();
     wide_destroy(h);
   }
   delete h;
@@ -2409,6 +2292,33 @@ static inline bool bf16_layout_ok(const rlh_csr *h) {
 }
 static inline bool bf16_halo_ok(const rlh_csr *h, int64_t n_own, int64_t ldh) {
   return h->well_aligned && n_own % 8 == 0 && ldh % 8 == 0;
+}
+// the bfloat16 Chebyshev step on the stacks, VPS vectors per step (the caller has checked that the stacks take the call)
+template <int VPS>
+static int launch_stack_cheb_bf16(rlh_csr *h, int part, int64_t m, const unsigned short *Y, int64_t ldy, int64_t n_own,
+                                  const unsigned short *H, int64_t ldh, unsigned short *P, int64_t ldp,
+                                  const unsigned short *B, int64_t ldb, float cy, float cp, float cb) {
+  if (part != 0)
+    if (int rc = h->stk_launch.split(n_own)) return rc;
+  const int32_t *sched;
+  int64_t sched_len;
+  int grid;
+  h->stk_launch.pick(part, &sched, &sched_len, &grid);
+  if (grid == 0) return 0;
+  constexpr int lds = kBfRingBytes + 16 * kBfOperandBytes;
+  const int32_t *pat = env_int("RLH_SPMM_STACK_PAT", 1) != 0 ? h->stk_pat : nullptr;
+  static bool attr = false;
+  if (!attr) {
+    RLH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&well_stack_cheb_bf16_kernel<kStkR, VPS>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    attr = true;
+  }
+  hipLaunchKernelGGL((well_stack_cheb_bf16_kernel<kStkR, VPS>), dim3((unsigned)grid), dim3(1024), lds, ctx().stream,
+                     h->stk_meta, h->stk_member, h->stk_gsrc, h->stk_idx,
+                     pat ? (const float *)h->stk_table : (const float *)h->stk_vals, pat, pat ? h->stk_dtab : nullptr,
+                     h->n_rows, sched, sched_len, Y, ldy, n_own, H, ldh, P, ldp, B, ldb, (int)m, cy, cp, cb);
+  RLH_HIP(hipGetLastError());
+  return 0;
 }
 extern "C" {
 
@@ -2517,50 +2427,16 @@ int rlh_spmm_cheb_bf16_part(rlh_csr_t h, int part, int64_t m, const void *Y16, i
       env_int("RLH_SPMM_STACK_BF16", 1) != 0 &&
       (h->stk_overhang == 0 || (H16 != nullptr && n_own != h->n_cols ? ldh >= h->n_cols - n_own + h->stk_overhang
                                                                       : ldy >= h->n_cols + h->stk_overhang))) {
-    if (part != 0)
-      if (int rc = stack_split(h, n_own)) return rc;
-    const int32_t *ssched = part == 0 ? h->stk_sched : h->stk_sched_part[part - 1];
-    const int64_t ssched_len = part == 0 ? h->stk_sched_len : h->stk_sched_part_len[part - 1];
-    const int sgrid = part == 0 ? h->stk_grid : h->stk_grid_part[part - 1];
-    if (sgrid == 0) return 0;
-    constexpr int lds = kBfRingBytes + 16 * kBfOperandBytes;
-    const int32_t *bpat = env_int("RLH_SPMM_STACK_PAT", 1) != 0 ? h->stk_pat : nullptr;
-#define RLH_BF_STACK(VPS_, ...)                                                                                       \
-    do {                                                                                                              \
-      static bool attr = false;                                                                                       \
-      if (!attr) {                                                                                                    \
-        RLH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&well_stack_cheb_bf16_kernel<kStkR, VPS_ __VA_ARGS__>), \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));                                \
-        attr = true;                                                                                                  \
-      }                                                                                                               \
-      hipLaunchKernelGGL((well_stack_cheb_bf16_kernel<kStkR, VPS_ __VA_ARGS__>), dim3((unsigned)sgrid), dim3(1024), lds, c.stream, \
-                         h->stk_meta, h->stk_member, h->stk_gsrc, h->stk_idx,                                         \
-                         bpat ? (const float *)h->stk_table : (const float *)h->stk_vals, bpat,                       \
-                         bpat ? h->stk_dtab : nullptr, h->n_rows,                                                     \
-                         ssched, ssched_len, Y, ldy, n_own, H, ldh, P, ldp, B, ldb, (int)m, (float)cy, (float)cp,     \
-                         (float)cb);                                                                                  \
-    } while (0)
-    switch (env_int("RLH_SPMM_BF16_DBG", 0)) {
-      case 1: RLH_BF_STACK(2, , 1); break;
-      case 2: RLH_BF_STACK(2, , 2); break;
-      case 3: RLH_BF_STACK(2, , 3); break;
-      case 4: RLH_BF_STACK(2, , 4); break;
-      case 5: RLH_BF_STACK(2, , 5); break;
-      case 6: RLH_BF_STACK(2, , 6); break;
-      case 7: RLH_BF_STACK(2, , 7); break;
-      default:
-        if (env_int("RLH_SPMM_BF16_VPS", 2) >= 2) RLH_BF_STACK(2);
-        else RLH_BF_STACK(1);
-    }
-#undef RLH_BF_STACK
-    RLH_HIP(hipGetLastError());
-    return 0;
+    if (env_int("RLH_SPMM_BF16_VPS", 2) >= 2)
+      return launch_stack_cheb_bf16<2>(h, part, m, Y, ldy, n_own, H, ldh, P, ldp, B, ldb, (float)cy, (float)cp, (float)cb);
+    return launch_stack_cheb_bf16<1>(h, part, m, Y, ldy, n_own, H, ldh, P, ldp, B, ldb, (float)cy, (float)cp, (float)cb);
   }
   if (part != 0)
-    if (int rc = well_split(h, n_own)) return rc;
-  const int32_t *sched = part == 0 ? h->well_sched : h->well_sched_part[part - 1];
-  const int64_t sched_len = part == 0 ? h->well_sched_len : h->well_sched_part_len[part - 1];
-  const int64_t nb = part == 0 ? h->well_grid : h->well_grid_part[part - 1];
+    if (int rc = h->well_launch.split(n_own)) return rc;
+  const int32_t *sched;
+  int64_t sched_len;
+  int nb;
+  h->well_launch.pick(part, &sched, &sched_len, &nb);
   if (nb == 0) return 0;
 #define RLH_BF_LAUNCH(W)                                                                                          \
   hipLaunchKernelGGL((well_cheb_bf16_kernel<W>), dim3((unsigned)nb), dim3(1024), 0, c.stream, h->well_meta,       \

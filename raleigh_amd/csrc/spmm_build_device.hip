@@ -537,9 +537,8 @@ extern "C" int rlh_csr_create_device(rlh_csr_t *out, int dtype, int64_t n_rows, 
   RLH_REQUIRE(!(fmt && !strcmp(fmt, "well")),
               "rlh_csr_create_device: RLH_SPMM_FORMAT=well: the 1024-row windowed layout is not built on the device "
               "(interleaved or sliced ELL only; rlh_csr_create builds it from host arrays)");
-  rlh_csr *h = new rlh_csr();                 // (every member zero / empty)
+  rlh_csr *h = new rlh_csr();                 // (every member at its "nothing built" default)
   h->dtype = dtype; h->n_rows = n_rows; h->n_cols = n_cols;
-  h->wide_k = 1; h->well_split_at = -1; h->stk_split_at = -1;
   int rc = 1;
 #define RLH_CSR_BUILD(T)                                                                                              \
   rc = index_bits == 32 ? csr_create_device_impl<T, int32_t>(h, (const int32_t *)d_indptr, (const int32_t *)d_indices,  \

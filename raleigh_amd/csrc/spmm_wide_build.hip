@@ -127,14 +127,10 @@ int wide_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices, const 
   h->wide_maxcol.resize((size_t)nblocks);
   for (int64_t b = 0; b < nblocks; ++b) h->wide_maxcol[(size_t)b] = wins[b].back().start + wins[b].back().len - 1;
   h->wide_gmax = gmax;
-  RLH_HIP(hipMalloc((void **)&h->wide_meta, (size_t)nblocks * sizeof(WideMeta)));
-  RLH_HIP(hipMemcpy(h->wide_meta, meta.data(), (size_t)nblocks * sizeof(WideMeta), hipMemcpyHostToDevice));
-  RLH_HIP(hipMalloc((void **)&h->wide_gsrc, (size_t)std::max<int64_t>(goff, 1) * sizeof(int32_t)));
-  RLH_HIP(hipMemcpy(h->wide_gsrc, gsrc.data(), (size_t)goff * sizeof(int32_t), hipMemcpyHostToDevice));
-  RLH_HIP(hipMalloc((void **)&h->wide_idx, idx.size()));
-  RLH_HIP(hipMemcpy(h->wide_idx, idx.data(), idx.size(), hipMemcpyHostToDevice));
-  RLH_HIP(hipMalloc((void **)&h->wide_vals, vals.size()));
-  RLH_HIP(hipMemcpy(h->wide_vals, vals.data(), vals.size(), hipMemcpyHostToDevice));
+  if (int rc = upload(h->wide_meta, meta.data(), (size_t)nblocks * sizeof(WideMeta))) return rc;
+  if (int rc = upload(h->wide_gsrc, gsrc.data(), (size_t)goff * sizeof(int32_t), sizeof(int32_t))) return rc;
+  if (int rc = upload(h->wide_idx, idx.data(), idx.size())) return rc;
+  if (int rc = upload(h->wide_vals, vals.data(), vals.size())) return rc;
   h->padded = eoff * 8 * kWideRows;
   h->device_bytes = nblocks * (int64_t)sizeof(WideMeta) + goff * 4 + (int64_t)idx.size() + (int64_t)vals.size();
   h->wide_blocks = nblocks;
@@ -170,8 +166,7 @@ int wide_sched(rlh_csr *h, int slots, int part, int64_t n_own, const int32_t **s
   if (!list.empty()) {
     well_layout(list, slots, sch, s.grid);
     s.len = (int64_t)sch.size();
-    RLH_HIP(hipMalloc((void **)&s.sched, sch.size() * sizeof(int32_t)));
-    RLH_HIP(hipMemcpy(s.sched, sch.data(), sch.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (int rc = upload(s.sched, sch.data(), sch.size() * sizeof(int32_t))) return rc;
   }
   if (h->wide_scheds.size() >= 16) {             // a bounded cache: drop the oldest
     if (h->wide_scheds.front().sched) {

@@ -49,9 +49,6 @@ RLH_GRAM_WG_PER_CU=1), chunk (2 * 8 CU + 1) + 1 for the grid-stride loops of MOD
 route() below restates the dispatch conditions of gram_impl; it only names the kernel family that a case reaches (for
 the error / bound table that every test prints) and the panel side inside which gram_finalize mirrors a self-Gram (the
 one place where exact Hermitian symmetry is guaranteed and therefore asserted).  It never changes a check.
-
-Deliberately outside the suite: the RLH_GRAM_ZDBG = 1 / 2 / 3 builds of gram_z_dma_kernel.  They leave out the DMA or
-the multiply to time the rest and do not compute a Gram matrix.
 """
 
 import ctypes

@@ -38,7 +38,7 @@ def cu():
 
 
 def set_leg(monkeypatch, leg):
-    for name in ('STREAM', 'QUAD', 'NT', 'PIPE', 'ROWS', 'ZDMA', 'WG_PER_CU', 'ZDBG'):
+    for name in ('STREAM', 'QUAD', 'NT', 'PIPE', 'ROWS', 'ZDMA', 'WG_PER_CU'):
         monkeypatch.delenv('RLH_GRAM_' + name, raising=False)
     for name, value in PER_CALL[leg].items():
         monkeypatch.setenv(name, value)

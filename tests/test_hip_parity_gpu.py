@@ -1130,6 +1130,77 @@ def test_spmm_interior_boundary_parts(spmm_format, key):
     assert cases.rel(P.data(), 1.2 * x[:, r0:r1] - 0.2 * p0 + 0.4 * (b0 - ref)) < tol
 
 
+@pytest.mark.parametrize('stack', ['0', '2'])
+def test_spmm_part_resplit_on_one_handle(monkeypatch, stack):
+    """rlh_spmm_part on ONE handle with two own / halo boundaries in turn (3 072, 3 328, 3 072 again): the launch orders
+    of the two parts are rebuilt for every new n_own and the old ones freed.  Three 1024-row blocks, rows i - 1024,
+    i - 1, i, i + 1, i + 1024 inside the 3 072 own columns (so blocks 0 and 1 are each other's partners: forced stacks
+    are {0, 1} and {2}), plus one column of [3 072, 3 328) in every row of block 1 and one of [3 328, 3 584) in every
+    row of block 2.  Every time: part 1 is handed a NaN halo block and writes exactly the units (blocks, or stacks)
+    whose members reference no column >= n_own (at 3 072 block 0 alone, with stacks none: block 0 shares its stack
+    with block 1; at 3 328 blocks 0 and 1 either way), parts 1 + 2 give the product, and the third round repeats the
+    first bit for bit."""
+    from raleigh_amd import _lib
+    from raleigh_amd.algebra.hip import Vectors, CsrOperator
+    monkeypatch.setenv('RLH_SPMM_FORMAT', 'well')
+    monkeypatch.setenv('RLH_SPMM_STACK', stack)
+    n, ncols, m = 3072, 3584, 5
+    rng = np.random.default_rng(21)
+    i = np.arange(n)
+    rows, cols = [], []
+    for d in (-1024, -1, 0, 1, 1024):
+        ok = (i + d >= 0) & (i + d < n)
+        rows.append(i[ok])
+        cols.append(i[ok] + d)
+    for b, c0 in ((1, 3072), (2, 3328)):
+        r = np.arange(1024 * b, 1024 * (b + 1))
+        rows.append(r)
+        cols.append(c0 + (7 * r) % 256)
+    rows, cols = np.concatenate(rows), np.concatenate(cols)
+    A = sp.csr_matrix((rng.standard_normal(len(rows)), (rows, cols)), shape=(n, ncols))
+    A.sort_indices()
+    assert np.diff(A.indptr).max() <= 7
+    maxcol = [A[1024 * b:1024 * (b + 1)].indices.max() for b in range(3)]
+    assert maxcol[0] < 3072 <= maxcol[1] < 3328 <= maxcol[2]
+    op = CsrOperator(A, n_own=n)
+    units = [(0,), (1,), (2,)] if stack == '0' else [(0, 1), (2,)]
+    assert op.layout()[0] == 'well' and op.stacks()[0] == (0 if stack == '0' else len(units))
+    x = rng.standard_normal((m, ncols))
+    ref = (A @ x.T).T
+    L = _lib.lib()
+
+    def two_parts(n_own):
+        X, Hgood = Vectors(np.ascontiguousarray(x[:, :n_own])), Vectors(np.ascontiguousarray(x[:, n_own:]))
+        Hbad = Vectors(np.full((m, ncols - n_own), np.nan))
+        Y = Vectors(n, m)
+        Y.fill(np.full((m, n), 777.0))
+        _lib.check(L.rlh_spmm_part(op._h, 1, m, X.data_ptr(), X.ld(), n_own, Hbad.data_ptr(), Hbad.ld(), Y.data_ptr(), Y.ld()))
+        y1 = Y.data()
+        _lib.check(L.rlh_spmm_part(op._h, 2, m, X.data_ptr(), X.ld(), n_own, Hgood.data_ptr(), Hgood.ld(), Y.data_ptr(), Y.ld()))
+        y12 = Y.data()
+        want = np.zeros(n, dtype=bool)                    # rows of the units without halo columns
+        for u in units:
+            if all(maxcol[b] < n_own for b in u):
+                for b in u:
+                    want[1024 * b:1024 * (b + 1)] = True
+        done = y1[0] != 777
+        print('stack %s, n_own %d: part 1 wrote %d rows (expected %d), parts 1 + 2 relative error %.3e'
+              % (stack, n_own, done.sum(), want.sum(), cases.rel(y12, ref)))
+        assert np.array_equal(done, want)
+        assert np.all(y1[:, ~done] == 777) and np.all(np.isfinite(y1))
+        if done.any():
+            assert cases.rel(y1[:, done], ref[:, done]) < 1e-13
+        assert cases.rel(y12, ref) < 1e-13
+        return y1, y12, done
+
+    a1, a12, adone = two_parts(3072)
+    assert np.array_equal(adone[:1024], np.full(1024, stack == '0')) and not adone[1024:].any()
+    b1, b12, bdone = two_parts(3328)
+    assert bdone[:2048].all() and not bdone[2048:].any()
+    c1, c12, cdone = two_parts(3072)
+    assert np.array_equal(c1, a1) and np.array_equal(c12, a12)
+
+
 @pytest.mark.parametrize('key', KEYS)
 @pytest.mark.parametrize('shape', [(7, 5, 9, 4), (16, 16, 16, 16), (3, 20, 10, 27), (32, 32, 40, 24), (30, 34, 17, 33),
                                    (64, 64, 32, 32), (64, 64, 64, 64), (60, 64, 64, 50)])

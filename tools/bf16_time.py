@@ -1,5 +1,5 @@
 """Times the bfloat16 Chebyshev step on lap3d side^3 with m vectors (HIP events, variants taking turns):
-python tools/bf16_time.py 215 16 [--dbg]"""
+python tools/bf16_time.py 215 16"""
 import ctypes, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -26,10 +26,7 @@ for s in range(3):
     blk.pack(V, 1.0)
     blocks.append(blk)
 y, p, b = blocks
-variants = [('1024-row blocks', {'RLH_SPMM_STACK_BF16': '0', 'RLH_SPMM_BF16_DBG': '0'}), ('stacks', {'RLH_SPMM_STACK_BF16': '1', 'RLH_SPMM_BF16_DBG': '0'})]
-if '--dbg' in sys.argv:
-    what = {1: 'no y DMAs', 2: 'no row products', 3: 'no y DMAs, no row products', 4: 'no operands / update', 5: 'row products only', 6: 'y DMAs only', 7: 'entries, waits, barriers only'}
-    variants += [('stacks, ' + what[d], {'RLH_SPMM_STACK_BF16': '1', 'RLH_SPMM_BF16_DBG': str(d)}) for d in range(1, 8)]
+variants = [('1024-row blocks', {'RLH_SPMM_STACK_BF16': '0'}), ('stacks', {'RLH_SPMM_STACK_BF16': '1'})]
 ms = ctypes.c_float()
 times = {k: [] for k, _ in variants}
 for rep in range(12):

@@ -24,7 +24,6 @@ def main():
     ap.add_argument('--m', type=int, default=32)
     ap.add_argument('--dtype', default='d')
     ap.add_argument('--reps', type=int, default=10)
-    ap.add_argument('--dbg', action='store_true', help='time the timing-only builds of the LDS-DMA kernel (fp64, lap3d 215)')
     ap.add_argument('--check', action='store_true', help='compare with scipy on the host (small sizes)')
     args = ap.parse_args()
     from raleigh_amd import _lib
@@ -71,27 +70,13 @@ def main():
     ms = ctypes.c_float()
     nbytes = A.nnz * (es + 4) + (n + 1) * 4 + 2 * n * m * es
 
-    def timed(reps=args.reps):
-        op.apply(X, Y)
-        _lib.check(L.rlh_sync())
-        ts = []
-        for _ in range(reps):
-            _lib.check(L.rlh_timer_start())
-            op.apply(X, Y)
-            _lib.check(L.rlh_timer_stop(ctypes.byref(ms)))
-            ts.append(ms.value)
-        return float(np.median(ts)), float(np.min(ts))
-
     results = {}
     variants = [('blocks', {'RLH_SPMM_STACK': '0'})]
     if stacks and args.dtype in 'cz':
         variants += [('stacks, LDS-DMA', {'RLH_SPMM_STACK': '1'})]
     elif stacks:
         variants += [('stacks, register staging', {'RLH_SPMM_STACK': '1', 'RLH_SPMM_STACK_DMA': '0'}),
-                     ('stacks, LDS-DMA', {'RLH_SPMM_STACK': '1', 'RLH_SPMM_STACK_DMA': '2', 'RLH_SPMM_STACK_DBG': '0'})]
-        if args.dbg:
-            variants += [('stacks, LDS-DMA, plain stores', {'RLH_SPMM_STACK': '1', 'RLH_SPMM_STACK_DMA': '2', 'RLH_SPMM_STACK_DBG': '8'}),
-                         ('stacks, LDS-DMA, stores counted', {'RLH_SPMM_STACK': '1', 'RLH_SPMM_STACK_DMA': '2', 'RLH_SPMM_STACK_DBG': '16'})]
+                     ('stacks, LDS-DMA', {'RLH_SPMM_STACK': '1', 'RLH_SPMM_STACK_DMA': '2'})]
     # the variants take turns (one call each per round): the first calls of a process run up to 8 % slower than the
     # later ones, which a variant-after-variant comparison books to whoever goes first
     times = {name: [] for name, _ in variants}
@@ -105,18 +90,9 @@ def main():
                 times[name].append(ms.value)
             if rep == 0:
                 results[name] = Y.data().copy() if n * m <= 40_000_000 else Y.data()[:, ::max(1, n // 200_000)].copy()
-    os.environ['RLH_SPMM_STACK_DBG'] = '0'
     for name, _ in variants:
         med, mn = float(np.median(times[name])), float(np.min(times[name]))
         print('%-28s %8.4f ms (min %8.4f)  %8.1f GB/s  %5.1f%% of 8 TB/s' % (name, med, mn, nbytes / med / 1e6, nbytes / med / 1e6 / 80), flush=True)
-    if args.dbg and stacks:
-        what = {1: 'no DMA', 2: 'no LDS reads', 3: 'no DMA, no LDS reads', 4: 'no stores', 5: 'no DMA, no stores',
-                6: 'no LDS reads, no stores', 7: 'nothing but the entries, waits and barriers'}
-        for d in range(1, 8):
-            os.environ['RLH_SPMM_STACK_DBG'] = str(d)
-            med, mn = timed()
-            print('  timing-only build %d (%s): %8.4f ms (min %8.4f)' % (d, what[d], med, mn), flush=True)
-        os.environ['RLH_SPMM_STACK_DBG'] = '0'
     base = results['blocks']
     for name, y in results.items():
         if name != 'blocks' and y.shape == base.shape:

@@ -1,4 +1,4 @@
-"""Time of the complex128 64 x 64 two-operand Gram at config 5's size: python tools/zgram_bench.py [N] (RLH_GRAM_ZDMA, RLH_GRAM_ZDBG)"""
+"""Time of the complex128 64 x 64 two-operand Gram at config 5's size: python tools/zgram_bench.py [N] (RLH_GRAM_ZDMA)"""
 import os, sys, time, ctypes
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -19,4 +19,4 @@ ts = []
 for _ in range(20):
     _lib.check(L.rlh_timer_start()); f(); _lib.check(L.rlh_timer_stop(ctypes.byref(ms))); ts.append(ms.value)
 t = float(np.median(ts))
-print('ZDMA=%s ZDBG=%s: %.3f ms  %.1f TF  %.2f TB/s' % (os.environ.get('RLH_GRAM_ZDMA', '1'), os.environ.get('RLH_GRAM_ZDBG', '0'), t, 8.0 * n * m * m / t / 1e9, 2 * n * m * 16 / t / 1e9))
+print('ZDMA=%s: %.3f ms  %.1f TF  %.2f TB/s' % (os.environ.get('RLH_GRAM_ZDMA', '1'), t, 8.0 * n * m * m / t / 1e9, 2 * n * m * 16 / t / 1e9))
