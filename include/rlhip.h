@@ -507,6 +507,25 @@ int rlh_fsai_create_levels(rlh_fsai_t *h, int dtype, int64_t n, const int64_t *i
                            const void *values, int max_row, int levels);
 /* the levels a handle was built with */
 int rlh_fsai_levels(rlh_fsai_t h, int *levels);
+/* The _adaptive forms start from the level pattern above and carry out `steps` (1 .. 63) enrichment steps per row, each
+ * adding up to `step_size` (1 .. 16) columns chosen by value.  One step on the pattern P of row i: with S y = e_last,
+ * S = A[P, P], g = y^H (double / complex double), the candidates are the columns j < i outside P that some row p of P
+ * stores (explicit zeros count; a_pj below the diagonal is conj of the stored (j, p)), r_j = sum_p g_p a_pj over p
+ * ascending and score_j = |r_j|^2 / a_jj: the decrease of the Kaporin functional g A g^H from adding j alone.  The
+ * candidates of the largest finite positive scores are taken, at most step_size and at most max_row - |P|, equal
+ * scores the larger column first; a row stops when it holds max_row columns or a step takes nothing.  G is then
+ * computed on the final pattern as by the forms above: bit for bit the plain build of A with explicit zeros on that
+ * pattern and its mirror image, the same in every run, for both index widths and both settings of RLH_FSAI_BINS.
+ * truncated_rows (rlh_fsai_info) counts the rows max_row held back: the level pattern was cut, the row was full before
+ * one of its steps began, or a step took fewer columns than min(step_size, candidates of positive score) for lack of
+ * room.  A local block that is not positive definite, at any step, fails the build and names the row. */
+int rlh_fsai_create_adaptive_device(rlh_fsai_t *h, int dtype, int64_t n, int index_bits, const void *d_indptr,
+                                    const void *d_indices, const void *d_values, int max_row, int levels, int steps,
+                                    int step_size);
+int rlh_fsai_create_adaptive(rlh_fsai_t *h, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
+                             const void *values, int max_row, int levels, int steps, int step_size);
+/* the enrichment a handle was built with (0, 0: none) */
+int rlh_fsai_adaptive(rlh_fsai_t h, int *steps, int *step_size);
 /* Y = G^H (G X) for column-major DEVICE blocks of m vectors (leading dimensions >= n; Y may be X): two sparse
  * products (the kernels of rlh_spd_apply, bit-identical from call to call) through an n x m workspace of the handle,
  * which grows when a wider block than before arrives (that call synchronises the stream once); otherwise

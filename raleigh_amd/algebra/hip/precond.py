@@ -213,9 +213,17 @@ class ApproximateInverse:
     The patterns are nested, so without truncation a higher level never has a larger Kaporin number; it costs more
     entries per row (on a 7-point stencil 4, 10 and 20 at levels 1, 2 and 3) and a longer set-up.  Rows keep the
     `max_row` largest columns of their pattern; `truncated_rows` counts those whose full pattern has more.
-    ``levels=1`` is the build described above, bit for bit."""
+    ``levels=1`` is the build described above, bit for bit.
 
-    def __init__(self, matrix, max_row=64, levels=1):
+    steps (0 .. 63) and step_size (1 .. 16) make the pattern adaptive: after the level pattern every row goes through
+    `steps` enrichment steps, each adding the (at most `step_size`) columns j < i outside its pattern P, stored in some
+    row of P, that lower the Kaporin functional g A g^H of the row most: those of the largest |sum_p g_p a_pj|^2 / a_jj,
+    g the row solved on P.  The choice is by value, made on the device, and invariant under diagonal scaling; a row
+    stops at `max_row` columns or when no candidate lowers the functional.  `truncated_rows` then counts the rows that
+    `max_row` held back: cut level patterns, rows full before one of their steps, steps that had to leave candidates
+    for lack of room.  ``steps=0`` (the default) is the build without enrichment through the entry points it always had."""
+
+    def __init__(self, matrix, max_row=64, levels=1, steps=0, step_size=1):
         from . import device_data
         L = self._L = _lib.lib()                          # (the handle belongs to THIS library object)
         self._h = None
@@ -225,8 +233,16 @@ class ApproximateInverse:
         levels = int(levels)
         if not 1 <= levels <= 8:
             raise ValueError('levels must lie in [1, 8], got %d' % levels)
-        self.levels = levels
-        more = () if levels == 1 else (levels,)             # (level 1 goes through the entry points it always had)
+        steps, step_size = int(steps), int(step_size)
+        if not 0 <= steps <= 63:
+            raise ValueError('steps must lie in [0, 63], got %d' % steps)
+        if not 1 <= step_size <= 16:
+            raise ValueError('step_size must lie in [1, 16], got %d' % step_size)
+        self.levels, self.steps, self.step_size = levels, steps, step_size
+        if steps:
+            more, kind = (levels, steps, step_size), '_adaptive'
+        else:                                               # (level 1 goes through the entry points it always had)
+            more, kind = (() if levels == 1 else (levels,)), ('' if levels == 1 else '_levels')
         h = ctypes.c_void_p()
         if device_data.is_tensor(matrix):
             from .sparse import operator_tensor
@@ -243,7 +259,7 @@ class ApproximateInverse:
                     torch.cuda.current_stream(val.device).synchronize()
                 self._n = int(t.shape[0])
                 self._nnz_a = int(val.numel())
-                name = 'rlh_fsai_create_levels_device' if more else 'rlh_fsai_create_device'
+                name = 'rlh_fsai_create%s_device' % kind
                 self._create(getattr(L, name), name, h, _lib.DTYPE_CODE[self._dtype], self._n,
                              32 if crow.element_size() == 4 else 64, ctypes.c_void_p(crow.data_ptr()),
                              ctypes.c_void_p(col.data_ptr()), ctypes.c_void_p(val.data_ptr()), max_row, *more)
@@ -260,7 +276,7 @@ class ApproximateInverse:
         indptr = np.ascontiguousarray(a.indptr, dtype=np.int64)
         indices = np.ascontiguousarray(a.indices, dtype=np.int32)
         values = np.ascontiguousarray(a.data)
-        name = 'rlh_fsai_create_levels' if more else 'rlh_fsai_create'
+        name = 'rlh_fsai_create' + kind
         self._create(getattr(L, name), name, h, _lib.DTYPE_CODE[self._dtype], self._n, _lib.host_ptr(indptr),
                      _lib.host_ptr(indices), _lib.host_ptr(values), max_row, *more)
         self._finish(h)

@@ -19,6 +19,13 @@
 //                   steps on: a descending selection without a sort, at most max_row + 1 steps per level.  Capping
 //                   to the max_row largest after every level gives the capped final pattern: what a dropped column
 //                   j reaches is <= j, below every kept column, and the kept ones are in the next union themselves.
+//   enrichment      (the _adaptive entry points only) fsai_enrich<T, LANES>: `steps` times per row, solve on the pattern
+//                   and take the (at most step_size) columns below i, stored in a member's row, that lower the row's
+//                   Kaporin functional most.  The rows are binned by their capacity min(max_row, k + steps *
+//                   step_size) with the keys and scans of the set-up's bins, one lane group per row from the first
+//                   solve to the last selection; pattern and packed triangle in the LDS (the set-up's 40 KB), g in
+//                   the lanes' registers.  The patterns go to a slab at the scanned capacities and are compacted
+//                   (fsai_fill again) with new counts, keys and scans; from there on the build is the one below.
 //   set-up          fsai_setup<T, LANES>: LANES = 8, 16, 32 or 64 lanes per row for k <= LANES (RLH_FSAI_BINS=0: 8
 //                   and 64 only), 256 threads per workgroup (128 for 32 lanes in complex, 64 for 64 lanes).  The
 //                   packed upper triangle of S (then R) lies in the LDS: at most 40 KB per workgroup, so four
@@ -50,6 +57,7 @@ struct FsaiStatus : BuildStatus {
   long long row, col;                          // row and column of the entry a partner error points at
   unsigned long long truncated;                // rows cut to max_row
   int longest;                                 // longest row of G
+  unsigned long long limited;                  // adaptive build: rows max_row held back (those cut are among them)
 };
 
 __device__ __forceinline__ bool failed(const BuildStatus *st) { return *(const volatile unsigned long long *)&st->err != kNoError; }
@@ -94,10 +102,11 @@ struct Bins {
   int32_t *rows;                 // the rows of bin 8, then 16, 32 and 64, each in ascending order
 };
 
-__device__ __forceinline__ void put_row(const Bins &b, int64_t i, int64_t k) {
+// (the row's own keys are the steps of the scans at i)
+__device__ __forceinline__ void put_row(const Bins &b, int64_t i) {
   const int64_t a = b.sa[i], p8 = a & 0xffffffff, p16 = a >> 32, p32 = b.sb[i];
   int64_t at;
-  if (k <= kShort) at = p8;
+  if (p8 + 1 == (b.sa[i + 1] & 0xffffffff)) at = p8;
   else if (p16 + 1 == (b.sa[i + 1] >> 32)) at = b.c8 + (p16 - p8);
   else if (p32 + 1 == b.sb[i + 1]) at = b.c16 + (p32 - p16);
   else at = b.c32 + (i - p32);
@@ -105,8 +114,10 @@ __device__ __forceinline__ void put_row(const Bins &b, int64_t i, int64_t k) {
 }
 
 // per row: the diagonal is stored, every entry below it has its partner; at level 1 (tally) the kept entries (the
-// last min(lower, max_row) up to the diagonal), where they begin in A's row, and the keys of the row's bin
-__global__ __launch_bounds__(kBlock) void fsai_count(int64_t n, int max_row, int tally, int four, const int64_t *__restrict__ ip,
+// last min(lower, max_row) up to the diagonal), where they begin in A's row, and the keys of the row's bin (that of
+// its capacity min(max_row, k + grow); grow = 0 unless the pattern is enriched)
+__global__ __launch_bounds__(kBlock) void fsai_count(int64_t n, int max_row, int tally, int four, int grow,
+                                                     const int64_t *__restrict__ ip,
                                                      const int32_t *__restrict__ ix, int64_t *__restrict__ cnt,
                                                      int64_t *__restrict__ keya, int64_t *__restrict__ keyb,
                                                      int64_t *__restrict__ start, FsaiStatus *st) {
@@ -134,7 +145,7 @@ __global__ __launch_bounds__(kBlock) void fsai_count(int64_t n, int max_row, int
     }
     if (tally) {
       cnt[i] = k;
-      bin_keys(k, four, &keya[i], &keyb[i]);
+      bin_keys(k + grow < max_row ? k + grow : max_row, four, &keya[i], &keyb[i]);
     }
   }
 }
@@ -159,7 +170,7 @@ __global__ __launch_bounds__(kBlock) void fsai_fill(int64_t n, const int32_t *__
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
     const int64_t g0 = gp[i], k = gp[i + 1] - g0, a0 = start[i];
     for (int64_t t = 0; t < k; ++t) gi[g0 + t] = ix[a0 + t];
-    put_row(bins, i, k);
+    put_row(bins, i);
   }
 }
 
@@ -223,7 +234,7 @@ __device__ __forceinline__ int row_pattern(int64_t i, int max_row, int levels, c
 }
 
 // levels > 1: the kept entries per row and the keys of its bin (one wave per row)
-__global__ __launch_bounds__(kBlock) void fsai_pattern_count(int64_t n, int max_row, int levels, int four,
+__global__ __launch_bounds__(kBlock) void fsai_pattern_count(int64_t n, int max_row, int levels, int four, int grow,
                                                              const int64_t *__restrict__ ip, const int32_t *__restrict__ ix,
                                                              int64_t *__restrict__ cnt, int64_t *__restrict__ ka,
                                                              int64_t *__restrict__ kb, FsaiStatus *st) {
@@ -236,7 +247,7 @@ __global__ __launch_bounds__(kBlock) void fsai_pattern_count(int64_t n, int max_
     const int k = row_pattern(i, max_row, levels, ip, ix, cur[wave], lane, &over);
     if (lane == 0) {
       cnt[i] = k;
-      bin_keys(k, four, &ka[i], &kb[i]);
+      bin_keys(k + grow < max_row ? k + grow : max_row, four, &ka[i], &kb[i]);
       if (over) atomicAdd(&st->truncated, 1ull);
       atomicMax(&st->longest, k);
     }
@@ -256,7 +267,7 @@ __global__ __launch_bounds__(kBlock) void fsai_pattern_fill(int64_t n, int max_r
     int k = row_pattern(i, max_row, levels, ip, ix, cur[wave], lane, &over);
     if ((int64_t)k > gp[i + 1] - g0) k = (int)(gp[i + 1] - g0);      // (equal: the walk is the counting kernel's)
     if (lane < k) gi[g0 + lane] = cur[wave][lane];
-    if (lane == 0) put_row(bins, i, k);
+    if (lane == 0) put_row(bins, i);
   }
 }
 
@@ -301,6 +312,55 @@ template <typename T, int LANES> constexpr int setup_threads() {
   return LANES == 64 ? 64 : (LANES == 32 && sizeof(typename Wide<T>::type) == 16) ? 128 : kBlock;
 }
 
+// The local system of one row by its lane group (the set-up and every enrichment step): the columns of the pattern
+// ascend in pcol[0 .. k), the rows they name begin and end at pbeg / pend, all three in the LDS and visible to the
+// group.  S = A[P, P] is gathered into the packed triangle R, factorised S = R^H R and R u = e_k is solved: lane q
+// returns u_q (row q of G is conj(u)).  false: S is not positive definite (the same answer in every lane).
+template <typename T, int LANES>
+__device__ __forceinline__ bool local_solve(int k, int lane, const int32_t *pcol, const int64_t *pbeg, const int64_t *pend,
+                                            typename Wide<T>::type *R, const int32_t *__restrict__ ix,
+                                            const T *__restrict__ va, typename Wide<T>::type *out) {
+  using D = typename Wide<T>::type;
+  // S[p, q], p <= q: the stored entry (P[p], P[q]) -- on or above the diagonal -- or 0
+  const int pairs = k * (k + 1) / 2;
+  for (int e = lane; e < pairs; e += LANES) {
+    int q = (int)((sqrtf(8.f * (float)e + 1.f) - 1.f) * 0.5f);
+    while (q * (q + 1) / 2 > e) --q;
+    while ((q + 1) * (q + 2) / 2 <= e) ++q;
+    const int p = e - q * (q + 1) / 2;
+    const int64_t c = pcol[q], hi = pend[p];
+    const int64_t f = lower_bound_col(ix, pbeg[p], hi, c);
+    R[e] = (f < hi && (int64_t)ix[f] == c) ? widen(va[f]) : from_real(0.0, D());
+  }
+  wave_sync();
+  // S = R^H R row by row: lane q holds column q; R[p, q] = (S[p, q] - sum_{t < p} conj(R[t, p]) R[t, q]) / R[p, p]
+  double last = 1.0;
+  for (int p = 0; p < k; ++p) {
+    D acc = from_real(0.0, D());
+    const bool mine = lane >= p && lane < k;
+    if (mine) {
+      acc = R[tri_at(p, lane)];
+      for (int t = 0; t < p; ++t) fma_conj_acc(acc, R[tri_at(t, p)], neg_of(R[tri_at(t, lane)]));
+    }
+    const double d = __shfl(real_of(acc), p, LANES);
+    if (!(d > 0.0) || !(d < INFINITY)) return false;                     // (the same decision in every lane of the group)
+    last = d;
+    const double r = sqrt(d);
+    if (mine) R[tri_at(p, lane)] = lane == p ? from_real(r, D()) : div_real(acc, r);
+    wave_sync();
+  }
+  // R u = e_k from the last column back; lane p carries the right-hand side of row p
+  D rhs = from_real(0.0, D()), u = from_real(0.0, D());
+  for (int q = k - 1; q >= 0; --q) {
+    const D cand = q == k - 1 ? from_real(inv_sqrt(last), D()) : div_real(rhs, real_of(R[tri_at(q, q)]));
+    const D uq = shfl_of(cand, q, LANES);
+    if (lane == q) u = uq;
+    if (lane < q) fma_acc(rhs, R[tri_at(lane, q)], neg_of(uq));
+  }
+  *out = u;
+  return true;
+}
+
 template <typename T, int LANES>
 __global__ __launch_bounds__((setup_threads<T, LANES>())) void fsai_setup(int64_t nlist, const int32_t *__restrict__ list,
                                                                         const int64_t *__restrict__ ip,
@@ -314,7 +374,6 @@ __global__ __launch_bounds__((setup_threads<T, LANES>())) void fsai_setup(int64_
   __shared__ int32_t pcol[kGroups][LANES];
   __shared__ int64_t pbeg[kGroups][LANES], pend[kGroups][LANES];
   const int grp = threadIdx.x / LANES, lane = threadIdx.x % LANES;
-  D *R = tri[grp];
   for (int64_t s = (int64_t)blockIdx.x * kGroups + grp; s < nlist; s += (int64_t)gridDim.x * kGroups) {
     const int64_t i = list[s];
     const int64_t g0 = gp[i];
@@ -327,48 +386,163 @@ __global__ __launch_bounds__((setup_threads<T, LANES>())) void fsai_setup(int64_
       pend[grp][lane] = ip[c + 1];
     }
     wave_sync();
-    // S[p, q], p <= q: the stored entry (P[p], P[q]) -- on or above the diagonal -- or 0
-    const int pairs = k * (k + 1) / 2;
-    for (int e = lane; e < pairs; e += LANES) {
-      int q = (int)((sqrtf(8.f * (float)e + 1.f) - 1.f) * 0.5f);
-      while (q * (q + 1) / 2 > e) --q;
-      while ((q + 1) * (q + 2) / 2 <= e) ++q;
-      const int p = e - q * (q + 1) / 2;
-      const int64_t c = pcol[grp][q], hi = pend[grp][p];
-      const int64_t f = lower_bound_col(ix, pbeg[grp][p], hi, c);
-      R[e] = (f < hi && (int64_t)ix[f] == c) ? widen(va[f]) : from_real(0.0, D());
-    }
-    wave_sync();
-    // S = R^H R row by row: lane q holds column q; R[p, q] = (S[p, q] - sum_{t < p} conj(R[t, p]) R[t, q]) / R[p, p]
-    bool bad = false;
-    double last = 1.0;
-    for (int p = 0; p < k; ++p) {
-      D acc = from_real(0.0, D());
-      const bool mine = lane >= p && lane < k;
-      if (mine) {
-        acc = R[tri_at(p, lane)];
-        for (int t = 0; t < p; ++t) fma_conj_acc(acc, R[tri_at(t, p)], neg_of(R[tri_at(t, lane)]));
-      }
-      const double d = __shfl(real_of(acc), p, LANES);
-      if (!(d > 0.0) || !(d < INFINITY)) { bad = true; break; }          // (the same decision in every lane of the group)
-      last = d;
-      const double r = sqrt(d);
-      if (mine) R[tri_at(p, lane)] = lane == p ? from_real(r, D()) : div_real(acc, r);
-      wave_sync();
-    }
-    if (bad) {
+    D u;
+    if (!local_solve<T, LANES>(k, lane, pcol[grp], pbeg[grp], pend[grp], tri[grp], ix, va, &u)) {
       if (lane == 0) build_error(st, kErrNotPd, i);
       continue;
     }
-    // R u = e_k from the last column back; lane p carries the right-hand side of row p
-    D rhs = from_real(0.0, D()), u = from_real(0.0, D());
-    for (int q = k - 1; q >= 0; --q) {
-      const D cand = q == k - 1 ? from_real(inv_sqrt(last), D()) : div_real(rhs, real_of(R[tri_at(q, q)]));
-      const D uq = shfl_of(cand, q, LANES);
-      if (lane == q) u = uq;
-      if (lane < q) fma_acc(rhs, R[tri_at(lane, q)], neg_of(uq));
-    }
     if (lane < k) narrow(dev_conj(u), &gv[g0 + lane]);
+  }
+}
+
+// ---------------------------------------------------------------- adaptive patterns: enrichment by Kaporin gradient
+template <int LANES> __device__ __forceinline__ int group_max(int v) {
+  for (int o = LANES / 2; o; o >>= 1) {
+    const int w = __shfl_xor(v, o, 64);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+
+// The sum over the lanes of a group, the same bits in every lane.  Partners at distance 1, 2, 4, ..: a row of k
+// members leaves exact zeros in the lanes from k on, so the rounded partial sums -- and the result -- are those of
+// every group width that holds the row: the sum does not depend on the row's bin.
+template <int LANES> __device__ __forceinline__ double group_sum(double v) {
+  for (int o = 1; o < LANES; o <<= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+template <int LANES> __device__ __forceinline__ c64 group_sum(c64 v) { return c64{group_sum<LANES>(v.re), group_sum<LANES>(v.im)}; }
+
+__device__ __forceinline__ double abs2_of(double a) { return a * a; }
+__device__ __forceinline__ double abs2_of(c64 a) { return fma(a.re, a.re, a.im * a.im); }
+
+// `steps` enrichment steps on the level pattern of every row of one bin (LANES lanes per row: the row's capacity
+// min(max_row, k0 + steps * step_size) is at most LANES).  One step on the pattern P (ascending in the LDS, i its last
+// member): solve S y = e_last (local_solve: g = conj(u) is a positive multiple of y^H, lane q keeps g_q in a register);
+// then lane q walks the stored entries of row P[q] downwards from column i - 1, the group's maximum of the columns the
+// lanes show is the next candidate j (descending, each once; members of P are passed over), the lanes that show it
+// contribute g_p a_pj -- a_pj read at (p, j) for j > p, as conj of (j, p) for j < p: never below the diagonal -- and
+// r_j is their group_sum.  score_j = |r_j|^2 / a_jj; lane t holds the t-th best (score, column) so far, a new one goes
+// behind those that are not smaller (they have larger columns).  The taken columns are appended and the pattern is
+// sorted by ranks.  The final pattern goes to slab[sp[i] ..), its length and the keys of its bin to cnt, ka, kb.
+// Every decision is the group's (the same in each of its lanes); st->limited counts rows max_row held back.
+template <typename T, int LANES>
+__global__ __launch_bounds__((setup_threads<T, LANES>())) void fsai_enrich(
+    int64_t nlist, const int32_t *__restrict__ list, int max_row, int steps, int step_size, int four,
+    const int64_t *__restrict__ ip, const int32_t *__restrict__ ix, const T *__restrict__ va, const int64_t *__restrict__ gp0,
+    const int32_t *__restrict__ gi0, const int64_t *__restrict__ sp, int32_t *__restrict__ slab, int64_t *__restrict__ cnt,
+    int64_t *__restrict__ ka, int64_t *__restrict__ kb, FsaiStatus *st) {
+  using D = typename Wide<T>::type;
+  constexpr int kThreads = setup_threads<T, LANES>(), kGroups = kThreads / LANES, kTri = LANES * (LANES + 1) / 2;
+  __shared__ D tri[kGroups][kTri];
+  __shared__ int32_t pcol[kGroups][LANES];
+  __shared__ int64_t pbeg[kGroups][LANES], pend[kGroups][LANES];
+  static_assert(sizeof(D) * kGroups * kTri + 20 * kThreads <= 40 * 1024, "the LDS of a workgroup");
+  const int grp = threadIdx.x / LANES, lane = threadIdx.x % LANES;
+  const int base = (threadIdx.x & 63) - lane;          // the group's first lane within its wave
+  constexpr unsigned long long kGroupMask = LANES == 64 ? ~0ull : ((1ull << (LANES & 63)) - 1);
+  int32_t *P = pcol[grp];
+  for (int64_t s = (int64_t)blockIdx.x * kGroups + grp; s < nlist; s += (int64_t)gridDim.x * kGroups) {
+    const int64_t i = list[s];
+    const int64_t g0 = gp0[i], s0 = sp[i];
+    int k = (int)(gp0[i + 1] - g0);                    // 1 <= k <= capacity <= LANES
+    const int room = (int)(sp[i + 1] - s0);            // the row's capacity
+    wave_sync();                                       // (the row before this one is done with the LDS)
+    if (lane < k) P[lane] = gi0[g0 + lane];
+    bool limited = false, bad = false;
+    for (int step = 0; step < steps; ++step) {
+      if (k >= max_row) { limited = true; break; }     // full before this step begins
+      if (k >= room) break;                            // (k < max_row: capacity left for every step; never taken)
+      wave_sync();
+      if (lane < k) {
+        const int32_t c = P[lane];
+        pbeg[grp][lane] = ip[c];
+        pend[grp][lane] = ip[c + 1];
+      }
+      wave_sync();
+      D u;
+      if (!local_solve<T, LANES>(k, lane, P, pbeg[grp], pend[grp], tri[grp], ix, va, &u)) { bad = true; break; }
+      const D g = dev_conj(u);
+      const int take = min(step_size, room - k);                    // = min(step_size, max_row - k); 1 <= take < LANES
+      int64_t beg = 0, pos = -1, own = -1;
+      if (lane < k) {
+        own = P[lane];
+        beg = pbeg[grp][lane];
+        pos = lower_bound_col(ix, beg, pend[grp][lane], i) - 1;     // the last stored column below i
+      }
+      int cand = pos >= beg ? ix[pos] : -1;
+      int member = k - 1, held = 0, positive = 0, my_col = -1;
+      double my_score = 0.0;
+      for (;;) {
+        const int j = group_max<LANES>(cand);          // the largest column not yet seen: the same in every lane
+        if (j < 0) break;
+        while (member >= 0 && P[member] > j) --member;
+        const bool show = cand == j;
+        if (member < 0 || P[member] != j) {
+          const int64_t jb = ip[j], je = ip[j + 1];
+          D term = from_real(0.0, D());
+          if (show) {
+            D a = from_real(0.0, D());
+            if ((int64_t)j > own) {
+              a = widen(va[pos]);
+            } else {                                   // the partner (j, own) above the diagonal (fsai_count saw it)
+              const int64_t f = lower_bound_col(ix, jb, je, own);
+              if (f < je && (int64_t)ix[f] == own) a = dev_conj(widen(va[f]));
+            }
+            fma_acc(term, g, a);
+          }
+          const D r = group_sum<LANES>(term);
+          const int64_t fd = lower_bound_col(ix, jb, je, j);
+          const double ajj = (fd < je && ix[fd] == j) ? real_of(widen(va[fd])) : 0.0;
+          const double score = abs2_of(r) / ajj;
+          if (score > 0.0 && score < INFINITY) {
+            ++positive;
+            const unsigned long long ahead = __ballot(lane < held && my_score >= score);
+            const int at = __popcll((ahead >> base) & kGroupMask);
+            if (at < take) {
+              const double up_score = __shfl_up(my_score, 1, LANES);
+              const int up_col = __shfl_up(my_col, 1, LANES);
+              if (lane == at) {
+                my_score = score;
+                my_col = j;
+              } else if (lane > at) {
+                my_score = up_score;
+                my_col = up_col;
+              }
+              if (held < take) ++held;
+            }
+          }
+        }
+        if (show) {
+          --pos;
+          cand = pos >= beg ? ix[pos] : -1;
+        }
+      }
+      if (max_row - k < min(step_size, positive)) limited = true;    // fewer taken than offered, for lack of room
+      if (!held) break;                                // nothing to take: the row stops
+      // the taken columns behind the pattern, then every member to its rank
+      wave_sync();
+      if (lane < held) P[k + lane] = my_col;
+      wave_sync();
+      k += held;
+      int32_t v = 0;
+      int rank = 0;
+      if (lane < k) {
+        v = P[lane];
+        for (int t = 0; t < k; ++t) rank += P[t] < v ? 1 : 0;
+      }
+      wave_sync();
+      if (lane < k) P[rank] = v;
+    }
+    wave_sync();
+    if (lane < k) slab[s0 + lane] = P[lane];
+    if (lane == 0) {
+      cnt[i] = k;
+      bin_keys(k, four, &ka[i], &kb[i]);
+      if (limited) atomicAdd(&st->limited, 1ull);
+      atomicMax(&st->longest, k);
+      if (bad) build_error(st, kErrNotPd, i);
+    }
   }
 }
 
@@ -377,12 +551,15 @@ struct FsaiScratch {                // released when the build returns, however 
   int64_t *indptr = nullptr, *cnt = nullptr, *ka = nullptr, *kb = nullptr, *start = nullptr, *gp = nullptr, *sa = nullptr,
           *sb = nullptr, *bsum = nullptr;
   int32_t *cols = nullptr, *gi = nullptr, *gp32 = nullptr, *rows = nullptr;
+  int64_t *cap = nullptr, *sp = nullptr;       // adaptive build: the rows' capacities, their scan,
+  int32_t *slab = nullptr, *level = nullptr;   // the enriched patterns at sp[i] and the level patterns they grew from
   void *gv = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   ~FsaiScratch() {
     (void)hipFree(status); (void)hipFree(indptr); (void)hipFree(cnt); (void)hipFree(ka); (void)hipFree(kb); (void)hipFree(start);
     (void)hipFree(gp); (void)hipFree(sa); (void)hipFree(sb); (void)hipFree(bsum); (void)hipFree(cols); (void)hipFree(gi);
-    (void)hipFree(gp32); (void)hipFree(rows); (void)hipFree(gv);
+    (void)hipFree(gp32); (void)hipFree(rows); (void)hipFree(gv); (void)hipFree(cap); (void)hipFree(sp); (void)hipFree(slab);
+    (void)hipFree(level);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
   }
@@ -394,7 +571,7 @@ struct FsaiScratch {                // released when the build returns, however 
 struct rlh_fsai {
   int dtype = 0;
   int64_t n = 0, nnz = 0, truncated = 0;
-  int longest = 0, levels = 1;
+  int longest = 0, levels = 1, steps = 0, step_size = 0;
   double setup_seconds = 0;
   rlh_spd_t spd = nullptr;          // G and G^H with their partitions
   char *work = nullptr;             // the n x m block between the two products
@@ -425,12 +602,32 @@ void launch_setup(int64_t count, const int32_t *list, const int64_t *ip, const i
                      list, ip, ix, va, gp, gi, gv, status);
 }
 
+// per row the capacity min(max_row, k + grow) of an enriched pattern
+__global__ __launch_bounds__(kBlock) void fsai_capacity(int64_t n, int max_row, int grow, const int64_t *__restrict__ cnt,
+                                                        int64_t *__restrict__ cap) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
+    cap[i] = cnt[i] + grow < max_row ? cnt[i] + grow : max_row;
+}
+
+// one enrichment kernel over the rows of one bin (of capacities)
+template <typename T, int LANES>
+void launch_enrich(int64_t count, const int32_t *list, int max_row, int steps, int step_size, int four, const int64_t *ip,
+                   const int32_t *ix, const T *va, const int64_t *gp0, const int32_t *gi0, const int64_t *sp, int32_t *slab,
+                   int64_t *cnt, int64_t *ka, int64_t *kb, FsaiStatus *status) {
+  if (!count) return;
+  constexpr int kThreads = setup_threads<T, LANES>();
+  const int64_t most = (int64_t)ctx().num_cu * kSetupBlocksPerCu;
+  hipLaunchKernelGGL((fsai_enrich<T, LANES>), dim3(blocks_for(count, kThreads / LANES, most)), dim3(kThreads), 0, ctx().stream, count,
+                     list, max_row, steps, step_size, four, ip, ix, va, gp0, gi0, sp, slab, cnt, ka, kb, status);
+}
+
 // `name`: the entry point the messages speak for.  ip, ix, va: device arrays, n >= 1.  four: bins of 8, 16, 32 and 64
 // lanes per row (else 8 and 64).
 template <typename T, typename P, typename I>
 int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T *va, int max_row, int four) {
   const int64_t es = sizeof(T), n = h->n;
-  const int levels = h->levels;
+  const int levels = h->levels, steps = h->steps, step_size = h->step_size, grow = steps * step_size;
   hipStream_t st = ctx().stream;
   const dim3 blk(kBlock);
   FsaiScratch w;
@@ -504,12 +701,12 @@ int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T 
   RLH_HIP(hipMalloc((void **)&w.sa, (size_t)(n + 1) * 8));
   RLH_HIP(hipMalloc((void **)&w.sb, (size_t)(n + 1) * 8));
   RLH_HIP(hipMalloc((void **)&w.bsum, (size_t)(nb + 1) * 8));
-  hipLaunchKernelGGL(fsai_count, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, max_row, levels == 1 ? 1 : 0, four, ip64, ix32,
-                     w.cnt, w.ka, w.kb, w.start, w.status);
+  hipLaunchKernelGGL(fsai_count, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, max_row, levels == 1 ? 1 : 0, four, grow, ip64,
+                     ix32, w.cnt, w.ka, w.kb, w.start, w.status);
   hipLaunchKernelGGL(fsai_resolve_error, dim3(1), dim3(1), 0, st, n, ip64, ix32, w.status);
   if (levels > 1)
-    hipLaunchKernelGGL(fsai_pattern_count, dim3(blocks_for(n, kBlock / 64, most)), blk, 0, st, n, max_row, levels, four, ip64, ix32,
-                       w.cnt, w.ka, w.kb, w.status);
+    hipLaunchKernelGGL(fsai_pattern_count, dim3(blocks_for(n, kBlock / 64, most)), blk, 0, st, n, max_row, levels, four, grow, ip64,
+                       ix32, w.cnt, w.ka, w.kb, w.status);
   if (int rc = exclusive_scan(n, w.cnt, w.bsum, w.gp)) return rc;
   if (int rc = exclusive_scan(n, w.ka, w.bsum, w.sa)) return rc;
   if (int rc = exclusive_scan(n, w.kb, w.bsum, w.sb)) return rc;
@@ -520,21 +717,62 @@ int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T 
   RLH_HIP(hipMemcpyAsync(&tot[2], w.sb + n, 8, hipMemcpyDeviceToHost, st));
   RLH_HIP(hipStreamSynchronize(st));
   if (hs.err != kNoError) return report(hs);
-  const int64_t gnnz = tot[0], c8 = tot[1] & 0xffffffff, c16 = tot[1] >> 32, c32 = tot[2];
+  int64_t gnnz = tot[0], c8 = tot[1] & 0xffffffff, c16 = tot[1] >> 32, c32 = tot[2];
   RLH_REQUIRE(gnnz >= n && gnnz <= n * (int64_t)max_row && c8 >= 0 && c8 <= c16 && c16 <= c32 && c32 <= n,
               "%s: inconsistent row counts of the pattern", name);
-  h->nnz = gnnz;
-  h->truncated = (int64_t)hs.truncated;
-  h->longest = hs.longest;
   RLH_HIP(hipMalloc((void **)&w.gi, (size_t)gnnz * 4));
-  RLH_HIP(hipMalloc(&w.gv, (size_t)gnnz * es));
   RLH_HIP(hipMalloc((void **)&w.rows, (size_t)n * 4));
-  const Bins bins{w.sa, w.sb, c8, c16, c32, w.rows};
+  Bins bins{w.sa, w.sb, c8, c16, c32, w.rows};
   if (levels == 1)
     hipLaunchKernelGGL(fsai_fill, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, ix32, w.start, w.gp, w.gi, bins);
   else
     hipLaunchKernelGGL(fsai_pattern_fill, dim3(blocks_for(n, kBlock / 64, most)), blk, 0, st, n, max_row, levels, ip64, ix32, w.gp,
                        w.gi, bins);
+  if (steps > 0) {
+    // ---- enrichment: so far the bins are those of the capacities and w.gi holds the level patterns.  The enriched
+    // patterns go to a slab at the scanned capacities; counts, keys and scans are then made again for the final rows.
+    RLH_HIP(hipMalloc((void **)&w.cap, (size_t)n * 8));
+    RLH_HIP(hipMalloc((void **)&w.sp, (size_t)(n + 1) * 8));
+    hipLaunchKernelGGL(fsai_capacity, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, max_row, grow, w.cnt, w.cap);
+    if (int rc = exclusive_scan(n, w.cap, w.bsum, w.sp)) return rc;
+    int64_t room = 0;
+    RLH_HIP(hipMemcpyAsync(&room, w.sp + n, 8, hipMemcpyDeviceToHost, st));
+    RLH_HIP(hipStreamSynchronize(st));
+    RLH_REQUIRE(room >= gnnz && room <= n * (int64_t)max_row, "%s: inconsistent row counts of the pattern", name);
+    RLH_HIP(hipMalloc((void **)&w.slab, (size_t)room * 4));
+    launch_enrich<T, kShort>(c8, w.rows, max_row, steps, step_size, four, ip64, ix32, va, w.gp, w.gi, w.sp, w.slab, w.cnt, w.ka,
+                             w.kb, w.status);
+    launch_enrich<T, 16>(c16 - c8, w.rows + c8, max_row, steps, step_size, four, ip64, ix32, va, w.gp, w.gi, w.sp, w.slab, w.cnt,
+                         w.ka, w.kb, w.status);
+    launch_enrich<T, 32>(c32 - c16, w.rows + c16, max_row, steps, step_size, four, ip64, ix32, va, w.gp, w.gi, w.sp, w.slab, w.cnt,
+                         w.ka, w.kb, w.status);
+    launch_enrich<T, kMaxRow>(n - c32, w.rows + c32, max_row, steps, step_size, four, ip64, ix32, va, w.gp, w.gi, w.sp, w.slab,
+                              w.cnt, w.ka, w.kb, w.status);
+    RLH_HIP(hipGetLastError());
+    if (int rc = exclusive_scan(n, w.cnt, w.bsum, w.gp)) return rc;      // (the kernels above are done with w.gp)
+    if (int rc = exclusive_scan(n, w.ka, w.bsum, w.sa)) return rc;
+    if (int rc = exclusive_scan(n, w.kb, w.bsum, w.sb)) return rc;
+    RLH_HIP(hipMemcpyAsync(&hs, w.status, sizeof hs, hipMemcpyDeviceToHost, st));
+    RLH_HIP(hipMemcpyAsync(&tot[0], w.gp + n, 8, hipMemcpyDeviceToHost, st));
+    RLH_HIP(hipMemcpyAsync(&tot[1], w.sa + n, 8, hipMemcpyDeviceToHost, st));
+    RLH_HIP(hipMemcpyAsync(&tot[2], w.sb + n, 8, hipMemcpyDeviceToHost, st));
+    RLH_HIP(hipStreamSynchronize(st));
+    if (hs.err != kNoError) return report(hs);
+    const int64_t before = gnnz;
+    gnnz = tot[0], c8 = tot[1] & 0xffffffff, c16 = tot[1] >> 32, c32 = tot[2];
+    RLH_REQUIRE(gnnz >= before && gnnz <= room && c8 >= 0 && c8 <= c16 && c16 <= c32 && c32 <= n,
+                "%s: inconsistent row counts of the pattern", name);
+    hs.truncated = hs.limited;
+    w.level = w.gi;
+    w.gi = nullptr;
+    RLH_HIP(hipMalloc((void **)&w.gi, (size_t)gnnz * 4));
+    bins = Bins{w.sa, w.sb, c8, c16, c32, w.rows};
+    hipLaunchKernelGGL(fsai_fill, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, w.slab, w.sp, w.gp, w.gi, bins);
+  }
+  h->nnz = gnnz;
+  h->truncated = (int64_t)hs.truncated;
+  h->longest = hs.longest;
+  RLH_HIP(hipMalloc(&w.gv, (size_t)gnnz * es));
   // ---- the rows, bin by bin
   launch_setup<T, kShort>(c8, w.rows, ip64, ix32, va, w.gp, w.gi, (T *)w.gv, w.status);
   launch_setup<T, 16>(c16 - c8, w.rows + c8, ip64, ix32, va, w.gp, w.gi, (T *)w.gv, w.status);
@@ -580,13 +818,22 @@ int fsai_build_any(rlh_fsai *h, const char *name, const void *ip, const void *ix
   return 1;
 }
 
-int check_create_args(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, const void *indptr, int max_row, int levels) {
+constexpr int kMaxSteps = 63, kMaxStepSize = 16;
+
+// steps = 0: a build without enrichment (the entry points that have no such argument)
+int check_create_args(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, const void *indptr, int max_row, int levels,
+                      bool adaptive, int steps, int step_size) {
   RLH_REQUIRE(ph != nullptr, "%s: null handle pointer", name);
   *ph = nullptr;
   RLH_REQUIRE(dtype_valid(dtype), "%s: unknown dtype %d", name, dtype);
   RLH_REQUIRE(n >= 0 && n < INT32_MAX, "%s: the size must lie in [0, 2^31 - 1)", name);
   RLH_REQUIRE(max_row >= 1 && max_row <= kMaxRow, "%s: max_row must lie in [1, %d], got %d", name, kMaxRow, max_row);
   RLH_REQUIRE(levels >= 1 && levels <= kMaxLevels, "%s: levels must lie in [1, %d], got %d", name, kMaxLevels, levels);
+  if (adaptive) {
+    RLH_REQUIRE(steps >= 1 && steps <= kMaxSteps, "%s: steps must lie in [1, %d], got %d", name, kMaxSteps, steps);
+    RLH_REQUIRE(step_size >= 1 && step_size <= kMaxStepSize, "%s: step_size must lie in [1, %d], got %d", name, kMaxStepSize,
+                step_size);
+  }
   RLH_REQUIRE(indptr, "%s: null indptr", name);
   return 0;
 }
@@ -598,14 +845,19 @@ int four_bins() {
 }
 
 int create_device(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, int index_bits, const void *d_indptr,
-                  const void *d_indices, const void *d_values, int max_row, int levels) {
+                  const void *d_indices, const void *d_values, int max_row, int levels, bool adaptive = false, int steps = 0,
+                  int step_size = 0) {
   if (int rc = require_ready()) return rc;
-  if (int rc = check_create_args(name, ph, dtype, n, d_indptr, max_row, levels)) return rc;
+  if (int rc = check_create_args(name, ph, dtype, n, d_indptr, max_row, levels, adaptive, steps, step_size)) return rc;
   RLH_REQUIRE(index_bits == 32 || index_bits == 64, "%s: index_bits must be 32 or 64, got %d", name, index_bits);
   rlh_fsai *h = new rlh_fsai();
   h->dtype = dtype;
   h->n = n;
   h->levels = levels;
+  if (adaptive) {
+    h->steps = steps;
+    h->step_size = step_size;
+  }
   const int four = four_bins();
   int rc = 0;
   if (n > 0)
@@ -620,9 +872,9 @@ int create_device(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, int in
 }
 
 int create_host(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
-                const void *values, int max_row, int levels) {
+                const void *values, int max_row, int levels, bool adaptive = false, int steps = 0, int step_size = 0) {
   if (int rc = require_ready()) return rc;
-  if (int rc = check_create_args(name, ph, dtype, n, indptr, max_row, levels)) return rc;
+  if (int rc = check_create_args(name, ph, dtype, n, indptr, max_row, levels, adaptive, steps, step_size)) return rc;
   // what decides how much is uploaded is checked here; everything else by the kernels, as for device arrays
   RLH_REQUIRE(indptr[0] == 0, "%s: indptr[0] must be 0", name);
   for (int64_t r = 0; r < n; ++r) RLH_REQUIRE(indptr[r + 1] >= indptr[r], "%s: indptr decreases at row %lld", name, (long long)r);
@@ -632,6 +884,10 @@ int create_host(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, const in
   h->dtype = dtype;
   h->n = n;
   h->levels = levels;
+  if (adaptive) {
+    h->steps = steps;
+    h->step_size = step_size;
+  }
   const int four = four_bins();
   int rc = 0;
   if (n > 0) {
@@ -684,6 +940,25 @@ extern "C" int rlh_fsai_create(rlh_fsai_t *ph, int dtype, int64_t n, const int64
 extern "C" int rlh_fsai_create_levels(rlh_fsai_t *ph, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
                                       const void *values, int max_row, int levels) {
   return create_host("rlh_fsai_create_levels", ph, dtype, n, indptr, indices, values, max_row, levels);
+}
+
+extern "C" int rlh_fsai_create_adaptive_device(rlh_fsai_t *ph, int dtype, int64_t n, int index_bits, const void *d_indptr,
+                                               const void *d_indices, const void *d_values, int max_row, int levels, int steps,
+                                               int step_size) {
+  return create_device("rlh_fsai_create_adaptive_device", ph, dtype, n, index_bits, d_indptr, d_indices, d_values, max_row, levels,
+                       true, steps, step_size);
+}
+
+extern "C" int rlh_fsai_create_adaptive(rlh_fsai_t *ph, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
+                                        const void *values, int max_row, int levels, int steps, int step_size) {
+  return create_host("rlh_fsai_create_adaptive", ph, dtype, n, indptr, indices, values, max_row, levels, true, steps, step_size);
+}
+
+extern "C" int rlh_fsai_adaptive(rlh_fsai_t h, int *steps, int *step_size) {
+  RLH_REQUIRE(h && steps && step_size, "rlh_fsai_adaptive: null handle or output");
+  *steps = h->steps;
+  *step_size = h->step_size;
+  return 0;
 }
 
 extern "C" int rlh_fsai_levels(rlh_fsai_t h, int *levels) {

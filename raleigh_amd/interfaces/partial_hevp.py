@@ -41,7 +41,9 @@ def partial_hevp(A, B=None, T=None, buckling=False, sigma=0, which=6, tol=1e-4, 
     operator of the error estimate is still built on the device.  Of the preconditioners, `ApproximateInverse`
     (algebra/hip/precond.py) takes the same tensor and is set up by kernels on the GPU (``levels=2`` or ``3`` puts it
     on the pattern of that power of the lower triangle: fewer iterations on stencil-like operators, whose rows store
-    only a few entries, for a longer set-up), as `ChebyshevPreconditioner`
+    only a few entries, for a longer set-up; ``steps=`` and ``step_size=`` then let every row take, step by step,
+    the further columns that lower its Kaporin functional most: a pattern chosen by value on the GPU, for matrices
+    whose level patterns ``max_row`` cuts), as `ChebyshevPreconditioner`
     is from the operator; an IncompleteLU preconditioner is a host factorisation and is set up from a SciPy matrix
     only.  A CPU tensor is taken as the SciPy matrix of its arrays (ndarrays come back).
 

@@ -6,6 +6,10 @@
   levels       --levels 1,2,3: one ApproximateInverse per level of fill (the pattern of that power of the lower triangle),
                each reported with its longest row, entries per row and truncated rows, next to IncompleteLU and no
                preconditioner
+  adaptive     --adaptive LEVELS:STEPS:SIZE[,...]: one ApproximateInverse(levels=LEVELS, steps=STEPS, step_size=SIZE) each
+               (the level pattern enriched on the GPU by Kaporin gradient), in the same run next to the --levels builds and
+               measured the same way; the share of its set-up that the enrichment takes is what the set-up costs beyond
+               that of the level pattern alone (device time, fastest against fastest)
   set-up       ApproximateInverse from a torch.sparse_csr tensor on the GPU: the device time the library reports
                (events around the whole build) and the host wall time; IncompleteLU.factorize on the same matrix
                (host wall time: ILUT on the host, then the set-up of the two triangular solves)
@@ -17,8 +21,8 @@ Every timing is repeated --repeats times and reported as fastest .. slowest; "A 
 faster than B's fastest, anything else is "no winner".  Nothing here is a threshold.  --setup-only stops after the
 set-up lines (for comparing two builds of the library on one machine).
 
-    python tools/approx_inverse_bench.py [--out profiles/r11_approx_inverse_levels.txt] [--levels 1,2,3] [--m 16]
-                                         [--calls 20] [--repeats 5] [--setup-only]
+    python tools/approx_inverse_bench.py [--out profiles/r11_approx_inverse_levels.txt] [--levels 1,2,3]
+                                         [--adaptive 1:4:4,1:4:8,2:2:4] [--m 16] [--calls 20] [--repeats 5] [--setup-only]
 """
 import argparse
 import ctypes
@@ -43,6 +47,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'r11_approx_inverse_levels.txt'))
     ap.add_argument('--levels', default='1,2,3', help='levels of fill of ApproximateInverse, comma separated')
+    ap.add_argument('--adaptive', default='', help='adaptive patterns as LEVELS:STEPS:SIZE, comma separated')
     ap.add_argument('--setup-only', action='store_true', help='set-up timings only')
     ap.add_argument('--m', type=int, default=16)
     ap.add_argument('--calls', type=int, default=20)
@@ -51,6 +56,8 @@ def main():
     ap.add_argument('--no-resources', action='store_true', help='skip the compiler\'s resource lines (needs hipcc)')
     args = ap.parse_args()
     levels = [int(v) for v in args.levels.split(',')]
+    adaptive = [tuple(int(v) for v in spec.split(':')) for spec in args.adaptive.split(',') if spec]
+    assert all(len(spec) == 3 for spec in adaptive), '--adaptive takes LEVELS:STEPS:SIZE'
     import torch
     import scipy.sparse as sp
     from raleigh_amd import _lib
@@ -95,22 +102,31 @@ def main():
         torch.cuda.synchronize()
         say('== %s: n = %d, nnz = %d (%.1f per row)' % (title, n, A.nnz, A.nnz / n))
         # ---- set-up
-        names = ['ApproximateInverse(levels=%d)' % lv for lv in levels]
-        Ts, walls = {}, {}
-        for lv, name in zip(levels, names):
+        level_names = ['ApproximateInverse(levels=%d)' % lv for lv in levels]
+        adaptive_names = ['ApproximateInverse(%d:%d:%d)' % spec for spec in adaptive]
+        names = level_names + adaptive_names
+        kwargs = [dict(levels=lv) if lv != 1 else {} for lv in levels]
+        kwargs += [dict(levels=lv, steps=steps, step_size=size) for lv, steps, size in adaptive]
+        Ts, walls, devs = {}, {}, {}
+        for kw, name in zip(kwargs, names):
             dev_s, wall_s = [], []
             T = None
             for _ in range(args.repeats):
                 T = None
                 t0 = time.perf_counter()
-                T = ApproximateInverse(t) if lv == 1 else ApproximateInverse(t, levels=lv)
+                T = ApproximateInverse(t, **kw)
                 _lib.check(L.rlh_sync())
                 wall_s.append(time.perf_counter() - t0)
                 dev_s.append(T.setup_seconds)
-            Ts[name], walls[name] = T, wall_s
+            Ts[name], walls[name], devs[name] = T, wall_s, dev_s
             say('   set-up  %-29s device %s s, host wall %s s; nnz(G) = %d (%.1f per row, fill %.2f, longest row %d, '
                 '%d rows cut), %.1f MB held' % (name, span(dev_s, fmt='%.4f'), span(wall_s, fmt='%.4f'), T.nnz, T.nnz / n, T.fill,
                                                 T.longest_row, T.truncated_rows, T.device_bytes() / 1e6))
+        for (lv, steps, size), name in zip(adaptive, adaptive_names):
+            if lv in levels:
+                plain = min(devs[level_names[levels.index(lv)]])
+                say('           enrichment (%d steps of %d): %.0f %% of the set-up of %s (device, fastest %.4f s against %.4f s '
+                    'for the level pattern alone)' % (steps, size, 100 * (1 - plain / min(devs[name])), name, min(devs[name]), plain))
         if args.setup_only:
             say()
             del T, Ts, t
@@ -170,12 +186,18 @@ def main():
         for name in names:
             say('           ' + beats(name, 'IncompleteLU', solves[name], solves['IncompleteLU']))
             say('           ' + beats(name, 'no preconditioner', solves[name], solves['True (none)']))
-        for name in names[1:]:
+        for name in level_names[1:]:
             say('           ' + beats(name, names[0], solves[name], solves[names[0]]))
+        for name in adaptive_names:
+            for other in level_names:
+                say('           ' + beats(name, other, solves[name], solves[other]))
         # set-up and solve together: what a user who has the matrix on the GPU pays once
-        for name in names[1:]:
-            both = lambda k: [a + b for a, b in zip(sorted(walls[k]), sorted(solves[k]))]
+        both = lambda k: [a + b for a, b in zip(sorted(walls[k]), sorted(solves[k]))]
+        for name in level_names[1:]:
             say('           set-up + solve: ' + beats(name, names[0], both(name), both(names[0])))
+        for name in adaptive_names:
+            for other in level_names:
+                say('           set-up + solve: ' + beats(name, other, both(name), both(other)))
         say()
         del T, Ts, ilu, t
     if not args.no_resources and not args.setup_only:
