@@ -243,42 +243,44 @@ class ApproximateInverse:
             more, kind = (levels, steps, step_size), '_adaptive'
         else:                                               # (level 1 goes through the entry points it always had)
             more, kind = (() if levels == 1 else (levels,)), ('' if levels == 1 else '_levels')
-        h = ctypes.c_void_p()
+        t = None
         if device_data.is_tensor(matrix):
             from .sparse import operator_tensor
             t = operator_tensor(matrix)
-            if device_data._on_device(t):
-                import torch
-                self._dtype = device_data.numpy_type(t)
-                crow, col, val = t.crow_indices(), t.col_indices(), t.values()
-                if col.dtype != crow.dtype:                 # (torch takes mixed index types: both as the wider one)
-                    crow, col = crow.to(torch.int64), col.to(torch.int64)
-                crow, col = crow.contiguous(), col.contiguous()
-                val = val.detach().resolve_conj().resolve_neg().contiguous()
-                if val.is_cuda:                             # the conversions may have launched work on torch's stream
-                    torch.cuda.current_stream(val.device).synchronize()
-                self._n = int(t.shape[0])
-                self._nnz_a = int(val.numel())
-                name = 'rlh_fsai_create%s_device' % kind
-                self._create(getattr(L, name), name, h, _lib.DTYPE_CODE[self._dtype], self._n,
-                             32 if crow.element_size() == 4 else 64, ctypes.c_void_p(crow.data_ptr()),
-                             ctypes.c_void_p(col.data_ptr()), ctypes.c_void_p(val.data_ptr()), max_row, *more)
-                self._finish(h)
-                return
-            matrix = device_data.to_host(t)
-        from .sparse_data import canonical_csr
-        a = canonical_csr(matrix)
-        if a.shape[0] != a.shape[1]:
-            raise ValueError('a square matrix is needed, got %d x %d' % a.shape)
-        self._dtype = a.dtype.type
-        self._n = int(a.shape[0])
-        self._nnz_a = int(a.nnz)
-        indptr = np.ascontiguousarray(a.indptr, dtype=np.int64)
-        indices = np.ascontiguousarray(a.indices, dtype=np.int32)
-        values = np.ascontiguousarray(a.data)
-        name = 'rlh_fsai_create' + kind
-        self._create(getattr(L, name), name, h, _lib.DTYPE_CODE[self._dtype], self._n, _lib.host_ptr(indptr),
-                     _lib.host_ptr(indices), _lib.host_ptr(values), max_row, *more)
+            if not device_data._on_device(t):
+                matrix, t = device_data.to_host(t), None
+        # the entry point and its arguments between the handle and max_row (the arrays they point at live to the call)
+        if t is not None:
+            import torch
+            self._dtype = device_data.numpy_type(t)
+            crow, col, val = t.crow_indices(), t.col_indices(), t.values()
+            if col.dtype != crow.dtype:                     # (torch takes mixed index types: both as the wider one)
+                crow, col = crow.to(torch.int64), col.to(torch.int64)
+            crow, col = crow.contiguous(), col.contiguous()
+            val = val.detach().resolve_conj().resolve_neg().contiguous()
+            if val.is_cuda:                                 # the conversions may have launched work on torch's stream
+                torch.cuda.current_stream(val.device).synchronize()
+            self._n = int(t.shape[0])
+            self._nnz_a = int(val.numel())
+            name = 'rlh_fsai_create%s_device' % kind
+            args = (_lib.DTYPE_CODE[self._dtype], self._n, 32 if crow.element_size() == 4 else 64,
+                    ctypes.c_void_p(crow.data_ptr()), ctypes.c_void_p(col.data_ptr()), ctypes.c_void_p(val.data_ptr()))
+        else:
+            from .sparse_data import canonical_csr
+            a = canonical_csr(matrix)
+            if a.shape[0] != a.shape[1]:
+                raise ValueError('a square matrix is needed, got %d x %d' % a.shape)
+            self._dtype = a.dtype.type
+            self._n = int(a.shape[0])
+            self._nnz_a = int(a.nnz)
+            indptr = np.ascontiguousarray(a.indptr, dtype=np.int64)
+            indices = np.ascontiguousarray(a.indices, dtype=np.int32)
+            values = np.ascontiguousarray(a.data)
+            name = 'rlh_fsai_create' + kind
+            args = (_lib.DTYPE_CODE[self._dtype], self._n, _lib.host_ptr(indptr), _lib.host_ptr(indices),
+                    _lib.host_ptr(values))
+        h = ctypes.c_void_p()
+        self._create(getattr(L, name), name, h, *args, max_row, *more)
         self._finish(h)
 
     @staticmethod

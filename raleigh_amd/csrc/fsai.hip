@@ -38,11 +38,18 @@
 // scheduling, G is the same bits in every run.  Lanes of a group exchange data through the LDS and shuffles only
 // within their own wave, at points every lane of the group reaches together (the trip counts are the group's k).
 // What a kernel finds wrong goes to the status record (code and the smallest position), never to a trap.
+//
+// The host side follows the kernels.  An entry point makes an FsaiPlan (what the build is asked to do); create_host and
+// create_device check it and run fsai_build inside make_handle.  fsai_build is the one build path: FsaiScratch owns every
+// device array it allocates, pattern_totals is the scan-fetch-wait-check sequence after the level pattern and again after
+// enrichment, and for_each_bin with launch_bin launches the enrichment and the set-up kernels bin by bin.
 #include "device_build.h"
 #include "spmm_data.h"
 
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
+#include <vector>
 
 namespace rlh {
 namespace {
@@ -181,8 +188,9 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_wave_barrier();
 }
 
-__device__ __forceinline__ int wave_max(int v) {
-  for (int o = 32; o; o >>= 1) {
+// the largest value among the LANES lanes of a group (64: the wave), the same in each of them
+template <int LANES> __device__ __forceinline__ int group_max(int v) {
+  for (int o = LANES / 2; o; o >>= 1) {
     const int w = __shfl_xor(v, o, 64);
     v = w > v ? w : v;
   }
@@ -212,7 +220,7 @@ __device__ __forceinline__ int row_pattern(int64_t i, int max_row, int levels, c
     }
     int cand = pos >= beg ? ix[pos] : -1, mine = -1, kn = 0;
     for (;;) {
-      const int m = wave_max(cand);                  // the largest column not yet taken: the same in every lane
+      const int m = group_max<64>(cand);                  // the largest column not yet taken: the same in every lane
       if (m < 0) break;
       if (kn == max_row) {
         *over = true;
@@ -396,13 +404,6 @@ __global__ __launch_bounds__((setup_threads<T, LANES>())) void fsai_setup(int64_
 }
 
 // ---------------------------------------------------------------- adaptive patterns: enrichment by Kaporin gradient
-template <int LANES> __device__ __forceinline__ int group_max(int v) {
-  for (int o = LANES / 2; o; o >>= 1) {
-    const int w = __shfl_xor(v, o, 64);
-    v = w > v ? w : v;
-  }
-  return v;
-}
 
 // The sum over the lanes of a group, the same bits in every lane.  Partners at distance 1, 2, 4, ..: a row of k
 // members leaves exact zeros in the lanes from k on, so the rounded partial sums -- and the result -- are those of
@@ -546,20 +547,50 @@ __global__ __launch_bounds__((setup_threads<T, LANES>())) void fsai_enrich(
   }
 }
 
-struct FsaiScratch {                // released when the build returns, however it returns
+// per row the capacity min(max_row, k + grow) of an enriched pattern
+__global__ __launch_bounds__(kBlock) void fsai_capacity(int64_t n, int max_row, int grow, const int64_t *__restrict__ cnt,
+                                                        int64_t *__restrict__ cap) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
+    cap[i] = cnt[i] + grow < max_row ? cnt[i] + grow : max_row;
+}
+
+// ---------------------------------------------------------------- the host side
+// RLH_FSAI_BINS=0: the two bins of 8 and 64 lanes per row
+int four_bins() {
+  const char *e = getenv("RLH_FSAI_BINS");
+  return (e && e[0] == '0' && e[1] == 0) ? 0 : 1;
+}
+
+// What a build is asked to do, made by the entry points.  adaptive: one of the _adaptive entry points, whose steps and
+// step_size are checked; the others leave both 0.  four: read from the environment by every create call.
+struct FsaiPlan {
+  int max_row, levels;
+  bool adaptive;
+  int steps, step_size;
+  int four = four_bins();
+  int grow() const { return steps * step_size; }       // what enrichment can add to a row
+};
+
+// The device arrays and the events of one build: released when the build returns, however it returns.  Named here are
+// the arrays that pattern_totals works on; the others are locals of fsai_build.
+struct FsaiScratch {
   FsaiStatus *status = nullptr;
-  int64_t *indptr = nullptr, *cnt = nullptr, *ka = nullptr, *kb = nullptr, *start = nullptr, *gp = nullptr, *sa = nullptr,
-          *sb = nullptr, *bsum = nullptr;
-  int32_t *cols = nullptr, *gi = nullptr, *gp32 = nullptr, *rows = nullptr;
-  int64_t *cap = nullptr, *sp = nullptr;       // adaptive build: the rows' capacities, their scan,
-  int32_t *slab = nullptr, *level = nullptr;   // the enriched patterns at sp[i] and the level patterns they grew from
-  void *gv = nullptr;
+  int64_t *cnt = nullptr, *ka = nullptr, *kb = nullptr;      // per row: kept entries and the keys of the bin,
+  int64_t *gp = nullptr, *sa = nullptr, *sb = nullptr, *bsum = nullptr;      // their exclusive scans and the scans' tile sums
   hipEvent_t e0 = nullptr, e1 = nullptr;
+  std::vector<void *> held;
+  template <typename E> hipError_t get(E **p, int64_t count) {      // *p: `count` elements that live as long as the scratch
+    const hipError_t e = hipMalloc((void **)p, (size_t)count * sizeof(E));
+    if (e == hipSuccess) held.push_back(*p);
+    return e;
+  }
+  hipError_t release(void *p) {                                     // ahead of time
+    std::replace(held.begin(), held.end(), p, (void *)nullptr);
+    return hipFree(p);
+  }
   ~FsaiScratch() {
-    (void)hipFree(status); (void)hipFree(indptr); (void)hipFree(cnt); (void)hipFree(ka); (void)hipFree(kb); (void)hipFree(start);
-    (void)hipFree(gp); (void)hipFree(sa); (void)hipFree(sb); (void)hipFree(bsum); (void)hipFree(cols); (void)hipFree(gi);
-    (void)hipFree(gp32); (void)hipFree(rows); (void)hipFree(gv); (void)hipFree(cap); (void)hipFree(sp); (void)hipFree(slab);
-    (void)hipFree(level);
+    for (void *p : held) (void)hipFree(p);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
   }
@@ -591,43 +622,76 @@ int exclusive_scan(int64_t n, const int64_t *in, int64_t *bsum, int64_t *out) {
   return 0;
 }
 
-// one set-up kernel over the rows of one bin
-template <typename T, int LANES>
-void launch_setup(int64_t count, const int32_t *list, const int64_t *ip, const int32_t *ix, const T *va, const int64_t *gp,
-                  const int32_t *gi, T *gv, FsaiStatus *status) {
+// What the kernels found wrong, as the message of `name`.  cap: the entries the index and value arrays can hold.
+int report(const char *name, const FsaiStatus &s, int64_t cap) {
+  const int code = (int)(s.err >> 56);
+  const long long pos = (long long)(s.err & (((unsigned long long)1 << 56) - 1));
+  switch (code) {
+    case kErrFirst: set_error("%s: indptr[0] must be 0", name); break;
+    case kErrDecreasing: set_error("%s: indptr decreases at row %lld", name, pos); break;
+    case kErrLast:
+      set_error("%s: indptr's last entry (%lld) is not the number of stored entries (the index and value arrays "
+                "hold at most %lld)", name, s.nnz, (long long)cap);
+      break;
+    case kErrRange: set_error("%s: column index out of range in row %lld", name, pos); break;
+    case kErrOrder: set_error("%s: the columns of row %lld must ascend strictly (no duplicates)", name, pos); break;
+    case kErrDiag: set_error("%s: row %lld does not store its diagonal entry", name, pos); break;
+    case kErrPartner:
+      set_error("%s: the stored structure is not symmetric: entry (%lld, %lld) has no partner (%lld, %lld); the "
+                "device build creates no entries", name, s.row, s.col, s.col, s.row);
+      break;
+    default: set_error("%s: local block of row %lld is not positive definite", name, pos);
+  }
+  return 1;
+}
+
+// One kernel over the rows of one bin, a group of LANES lanes per row: kernel(count, list, args...)
+template <typename T, int LANES, typename Kernel, typename... Args>
+void launch_bin(Kernel kernel, int64_t count, const int32_t *list, Args... args) {
   if (!count) return;
   constexpr int kThreads = setup_threads<T, LANES>();
   const int64_t most = (int64_t)ctx().num_cu * kSetupBlocksPerCu;
-  hipLaunchKernelGGL((fsai_setup<T, LANES>), dim3(blocks_for(count, kThreads / LANES, most)), dim3(kThreads), 0, ctx().stream, count,
-                     list, ip, ix, va, gp, gi, gv, status);
+  hipLaunchKernelGGL(kernel, dim3(blocks_for(count, kThreads / LANES, most)), dim3(kThreads), 0, ctx().stream, count, list, args...);
 }
 
-// per row the capacity min(max_row, k + grow) of an enriched pattern
-__global__ __launch_bounds__(kBlock) void fsai_capacity(int64_t n, int max_row, int grow, const int64_t *__restrict__ cnt,
-                                                        int64_t *__restrict__ cap) {
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
-    cap[i] = cnt[i] + grow < max_row ? cnt[i] + grow : max_row;
+// visit(lanes, count, list) for the bins of 8, 16, 32 and 64 lanes per row in turn; lanes is a std::integral_constant
+template <typename Visit> void for_each_bin(const Bins &b, int64_t n, Visit visit) {
+  visit(std::integral_constant<int, kShort>(), b.c8, b.rows);
+  visit(std::integral_constant<int, 16>(), b.c16 - b.c8, b.rows + b.c8);
+  visit(std::integral_constant<int, 32>(), b.c32 - b.c16, b.rows + b.c16);
+  visit(std::integral_constant<int, kMaxRow>(), n - b.c32, b.rows + b.c32);
 }
 
-// one enrichment kernel over the rows of one bin (of capacities)
-template <typename T, int LANES>
-void launch_enrich(int64_t count, const int32_t *list, int max_row, int steps, int step_size, int four, const int64_t *ip,
-                   const int32_t *ix, const T *va, const int64_t *gp0, const int32_t *gi0, const int64_t *sp, int32_t *slab,
-                   int64_t *cnt, int64_t *ka, int64_t *kb, FsaiStatus *status) {
-  if (!count) return;
-  constexpr int kThreads = setup_threads<T, LANES>();
-  const int64_t most = (int64_t)ctx().num_cu * kSetupBlocksPerCu;
-  hipLaunchKernelGGL((fsai_enrich<T, LANES>), dim3(blocks_for(count, kThreads / LANES, most)), dim3(kThreads), 0, ctx().stream, count,
-                     list, max_row, steps, step_size, four, ip, ix, va, gp0, gi0, sp, slab, cnt, ka, kb, status);
+// The counts and keys of the rows (w.cnt, w.ka, w.kb) are scanned into w.gp, w.sa, w.sb; the host waits for the stream
+// and reports what the kernels found so far.  *hs: the status record; *gnnz: the entries of the pattern, which must lie
+// in [lo, hi]; bins: the scans and the totals of the keys.
+int pattern_totals(const char *name, int64_t n, const FsaiScratch &w, int64_t cap, int64_t lo, int64_t hi, FsaiStatus *hs,
+                   int64_t *gnnz, Bins *bins) {
+  hipStream_t st = ctx().stream;
+  if (int rc = exclusive_scan(n, w.cnt, w.bsum, w.gp)) return rc;
+  if (int rc = exclusive_scan(n, w.ka, w.bsum, w.sa)) return rc;
+  if (int rc = exclusive_scan(n, w.kb, w.bsum, w.sb)) return rc;
+  int64_t tot[3] = {0, 0, 0};
+  RLH_HIP(hipMemcpyAsync(hs, w.status, sizeof *hs, hipMemcpyDeviceToHost, st));
+  RLH_HIP(hipMemcpyAsync(&tot[0], w.gp + n, 8, hipMemcpyDeviceToHost, st));
+  RLH_HIP(hipMemcpyAsync(&tot[1], w.sa + n, 8, hipMemcpyDeviceToHost, st));
+  RLH_HIP(hipMemcpyAsync(&tot[2], w.sb + n, 8, hipMemcpyDeviceToHost, st));
+  RLH_HIP(hipStreamSynchronize(st));
+  if (hs->err != kNoError) return report(name, *hs, cap);
+  const int64_t c8 = tot[1] & 0xffffffff, c16 = tot[1] >> 32, c32 = tot[2];
+  RLH_REQUIRE(tot[0] >= lo && tot[0] <= hi && c8 >= 0 && c8 <= c16 && c16 <= c32 && c32 <= n,
+              "%s: inconsistent row counts of the pattern", name);
+  *gnnz = tot[0];
+  *bins = Bins{w.sa, w.sb, c8, c16, c32, bins->rows};
+  return 0;
 }
 
-// `name`: the entry point the messages speak for.  ip, ix, va: device arrays, n >= 1.  four: bins of 8, 16, 32 and 64
-// lanes per row (else 8 and 64).
+// `name`: the entry point the messages speak for.  ip, ix, va: device arrays, n >= 1.
 template <typename T, typename P, typename I>
-int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T *va, int max_row, int four) {
+int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T *va, const FsaiPlan &plan) {
   const int64_t es = sizeof(T), n = h->n;
-  const int levels = h->levels, steps = h->steps, step_size = h->step_size, grow = steps * step_size;
+  const int max_row = plan.max_row, levels = plan.levels, steps = plan.steps, step_size = plan.step_size, four = plan.four;
+  const int grow = plan.grow();
   hipStream_t st = ctx().stream;
   const dim3 blk(kBlock);
   FsaiScratch w;
@@ -641,7 +705,7 @@ int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T 
   if (!ix || !va) cap = 0;
   if (room_i >= 0) cap = std::min<int64_t>(cap, room_i / (int64_t)sizeof(I));
   if (room_v >= 0) cap = std::min<int64_t>(cap, room_v / es);
-  RLH_HIP(hipMalloc((void **)&w.status, sizeof(FsaiStatus)));
+  RLH_HIP(w.get(&w.status, 1));
   FsaiStatus hs{};
   hs.err = kNoError;
   RLH_HIP(hipMemcpyAsync(w.status, &hs, sizeof hs, hipMemcpyHostToDevice, st));
@@ -650,153 +714,106 @@ int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T 
   RLH_HIP(hipGetLastError());
   RLH_HIP(hipMemcpyAsync(&hs, w.status, sizeof hs, hipMemcpyDeviceToHost, st));
   RLH_HIP(hipStreamSynchronize(st));
-  auto report = [&](const FsaiStatus &s) {
-    const int code = (int)(s.err >> 56);
-    const long long pos = (long long)(s.err & (((unsigned long long)1 << 56) - 1));
-    switch (code) {
-      case kErrFirst: set_error("%s: indptr[0] must be 0", name); break;
-      case kErrDecreasing: set_error("%s: indptr decreases at row %lld", name, pos); break;
-      case kErrLast:
-        set_error("%s: indptr's last entry (%lld) is not the number of stored entries (the index and value arrays "
-                  "hold at most %lld)", name, s.nnz, (long long)cap);
-        break;
-      case kErrRange: set_error("%s: column index out of range in row %lld", name, pos); break;
-      case kErrOrder: set_error("%s: the columns of row %lld must ascend strictly (no duplicates)", name, pos); break;
-      case kErrDiag: set_error("%s: row %lld does not store its diagonal entry", name, pos); break;
-      case kErrPartner:
-        set_error("%s: the stored structure is not symmetric: entry (%lld, %lld) has no partner (%lld, %lld); the "
-                  "device build creates no entries", name, s.row, s.col, s.col, s.row);
-        break;
-      default: set_error("%s: local block of row %lld is not positive definite", name, pos);
-    }
-    return 1;
-  };
-  if (hs.err != kNoError) return report(hs);
+  if (hs.err != kNoError) return report(name, hs, cap);
   const int64_t nnz = hs.nnz;
   // ---- indptr as int64 and columns as int32 (the caller's own arrays where they already are)
   const int64_t *ip64;
   const int32_t *ix32;
+  int32_t *cols = nullptr;
   if constexpr (std::is_same<P, int64_t>::value) {
     ip64 = ip;
   } else {
-    RLH_HIP(hipMalloc((void **)&w.indptr, (size_t)(n + 1) * sizeof(int64_t)));
-    hipLaunchKernelGGL((spd_convert_index<P, int64_t>), dim3(blocks_for(n + 1, kBlock, 4096)), blk, 0, st, n + 1, ip, w.indptr);
-    ip64 = w.indptr;
+    int64_t *indptr = nullptr;
+    RLH_HIP(w.get(&indptr, n + 1));
+    hipLaunchKernelGGL((spd_convert_index<P, int64_t>), dim3(blocks_for(n + 1, kBlock, 4096)), blk, 0, st, n + 1, ip, indptr);
+    ip64 = indptr;
   }
   if constexpr (std::is_same<I, int32_t>::value) {
     ix32 = ix;
   } else {
-    RLH_HIP(hipMalloc((void **)&w.cols, (size_t)std::max<int64_t>(4 * nnz, 4)));
-    if (nnz) hipLaunchKernelGGL((spd_convert_index<I, int32_t>), dim3(blocks_for(nnz, kBlock, 8192)), blk, 0, st, nnz, ix, w.cols);
-    ix32 = w.cols;
+    RLH_HIP(w.get(&cols, std::max<int64_t>(nnz, 1)));
+    if (nnz) hipLaunchKernelGGL((spd_convert_index<I, int32_t>), dim3(blocks_for(nnz, kBlock, 8192)), blk, 0, st, nnz, ix, cols);
+    ix32 = cols;
   }
   // ---- the pattern
   const int64_t nb = (n + kScanTile - 1) / kScanTile;
   const int64_t most = (int64_t)ctx().num_cu * kSetupBlocksPerCu;
-  RLH_HIP(hipMalloc((void **)&w.cnt, (size_t)n * 8));
-  RLH_HIP(hipMalloc((void **)&w.ka, (size_t)n * 8));
-  RLH_HIP(hipMalloc((void **)&w.kb, (size_t)n * 8));
-  RLH_HIP(hipMalloc((void **)&w.start, (size_t)n * 8));
-  RLH_HIP(hipMalloc((void **)&w.gp, (size_t)(n + 1) * 8));
-  RLH_HIP(hipMalloc((void **)&w.sa, (size_t)(n + 1) * 8));
-  RLH_HIP(hipMalloc((void **)&w.sb, (size_t)(n + 1) * 8));
-  RLH_HIP(hipMalloc((void **)&w.bsum, (size_t)(nb + 1) * 8));
+  int64_t *start = nullptr;
+  for (int64_t **p : {&w.cnt, &w.ka, &w.kb, &start}) RLH_HIP(w.get(p, n));
+  for (int64_t **p : {&w.gp, &w.sa, &w.sb}) RLH_HIP(w.get(p, n + 1));
+  RLH_HIP(w.get(&w.bsum, nb + 1));
   hipLaunchKernelGGL(fsai_count, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, max_row, levels == 1 ? 1 : 0, four, grow, ip64,
-                     ix32, w.cnt, w.ka, w.kb, w.start, w.status);
+                     ix32, w.cnt, w.ka, w.kb, start, w.status);
   hipLaunchKernelGGL(fsai_resolve_error, dim3(1), dim3(1), 0, st, n, ip64, ix32, w.status);
   if (levels > 1)
     hipLaunchKernelGGL(fsai_pattern_count, dim3(blocks_for(n, kBlock / 64, most)), blk, 0, st, n, max_row, levels, four, grow, ip64,
                        ix32, w.cnt, w.ka, w.kb, w.status);
-  if (int rc = exclusive_scan(n, w.cnt, w.bsum, w.gp)) return rc;
-  if (int rc = exclusive_scan(n, w.ka, w.bsum, w.sa)) return rc;
-  if (int rc = exclusive_scan(n, w.kb, w.bsum, w.sb)) return rc;
-  int64_t tot[3] = {0, 0, 0};
-  RLH_HIP(hipMemcpyAsync(&hs, w.status, sizeof hs, hipMemcpyDeviceToHost, st));
-  RLH_HIP(hipMemcpyAsync(&tot[0], w.gp + n, 8, hipMemcpyDeviceToHost, st));
-  RLH_HIP(hipMemcpyAsync(&tot[1], w.sa + n, 8, hipMemcpyDeviceToHost, st));
-  RLH_HIP(hipMemcpyAsync(&tot[2], w.sb + n, 8, hipMemcpyDeviceToHost, st));
-  RLH_HIP(hipStreamSynchronize(st));
-  if (hs.err != kNoError) return report(hs);
-  int64_t gnnz = tot[0], c8 = tot[1] & 0xffffffff, c16 = tot[1] >> 32, c32 = tot[2];
-  RLH_REQUIRE(gnnz >= n && gnnz <= n * (int64_t)max_row && c8 >= 0 && c8 <= c16 && c16 <= c32 && c32 <= n,
-              "%s: inconsistent row counts of the pattern", name);
-  RLH_HIP(hipMalloc((void **)&w.gi, (size_t)gnnz * 4));
-  RLH_HIP(hipMalloc((void **)&w.rows, (size_t)n * 4));
-  Bins bins{w.sa, w.sb, c8, c16, c32, w.rows};
+  int64_t gnnz = 0;
+  Bins bins{};
+  if (int rc = pattern_totals(name, n, w, cap, n, n * (int64_t)max_row, &hs, &gnnz, &bins)) return rc;
+  int32_t *gi = nullptr;
+  RLH_HIP(w.get(&gi, gnnz));
+  RLH_HIP(w.get(&bins.rows, n));
   if (levels == 1)
-    hipLaunchKernelGGL(fsai_fill, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, ix32, w.start, w.gp, w.gi, bins);
+    hipLaunchKernelGGL(fsai_fill, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, ix32, start, w.gp, gi, bins);
   else
     hipLaunchKernelGGL(fsai_pattern_fill, dim3(blocks_for(n, kBlock / 64, most)), blk, 0, st, n, max_row, levels, ip64, ix32, w.gp,
-                       w.gi, bins);
+                       gi, bins);
   if (steps > 0) {
-    // ---- enrichment: so far the bins are those of the capacities and w.gi holds the level patterns.  The enriched
+    // ---- enrichment: so far the bins are those of the capacities and gi holds the level patterns.  The enriched
     // patterns go to a slab at the scanned capacities; counts, keys and scans are then made again for the final rows.
-    RLH_HIP(hipMalloc((void **)&w.cap, (size_t)n * 8));
-    RLH_HIP(hipMalloc((void **)&w.sp, (size_t)(n + 1) * 8));
-    hipLaunchKernelGGL(fsai_capacity, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, max_row, grow, w.cnt, w.cap);
-    if (int rc = exclusive_scan(n, w.cap, w.bsum, w.sp)) return rc;
+    int64_t *capacity = nullptr, *sp = nullptr;
+    RLH_HIP(w.get(&capacity, n));
+    RLH_HIP(w.get(&sp, n + 1));
+    hipLaunchKernelGGL(fsai_capacity, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, max_row, grow, w.cnt, capacity);
+    if (int rc = exclusive_scan(n, capacity, w.bsum, sp)) return rc;
     int64_t room = 0;
-    RLH_HIP(hipMemcpyAsync(&room, w.sp + n, 8, hipMemcpyDeviceToHost, st));
+    RLH_HIP(hipMemcpyAsync(&room, sp + n, 8, hipMemcpyDeviceToHost, st));
     RLH_HIP(hipStreamSynchronize(st));
     RLH_REQUIRE(room >= gnnz && room <= n * (int64_t)max_row, "%s: inconsistent row counts of the pattern", name);
-    RLH_HIP(hipMalloc((void **)&w.slab, (size_t)room * 4));
-    launch_enrich<T, kShort>(c8, w.rows, max_row, steps, step_size, four, ip64, ix32, va, w.gp, w.gi, w.sp, w.slab, w.cnt, w.ka,
-                             w.kb, w.status);
-    launch_enrich<T, 16>(c16 - c8, w.rows + c8, max_row, steps, step_size, four, ip64, ix32, va, w.gp, w.gi, w.sp, w.slab, w.cnt,
-                         w.ka, w.kb, w.status);
-    launch_enrich<T, 32>(c32 - c16, w.rows + c16, max_row, steps, step_size, four, ip64, ix32, va, w.gp, w.gi, w.sp, w.slab, w.cnt,
-                         w.ka, w.kb, w.status);
-    launch_enrich<T, kMaxRow>(n - c32, w.rows + c32, max_row, steps, step_size, four, ip64, ix32, va, w.gp, w.gi, w.sp, w.slab,
-                              w.cnt, w.ka, w.kb, w.status);
+    int32_t *slab = nullptr;
+    RLH_HIP(w.get(&slab, room));
+    const int32_t *level = gi;                     // the level patterns the rows grow from
+    for_each_bin(bins, n, [&](auto lanes, int64_t count, const int32_t *list) {
+      constexpr int kLanes = decltype(lanes)::value;
+      launch_bin<T, kLanes>(fsai_enrich<T, kLanes>, count, list, max_row, steps, step_size, four, ip64, ix32, va, w.gp, level, sp,
+                            slab, w.cnt, w.ka, w.kb, w.status);
+    });
     RLH_HIP(hipGetLastError());
-    if (int rc = exclusive_scan(n, w.cnt, w.bsum, w.gp)) return rc;      // (the kernels above are done with w.gp)
-    if (int rc = exclusive_scan(n, w.ka, w.bsum, w.sa)) return rc;
-    if (int rc = exclusive_scan(n, w.kb, w.bsum, w.sb)) return rc;
-    RLH_HIP(hipMemcpyAsync(&hs, w.status, sizeof hs, hipMemcpyDeviceToHost, st));
-    RLH_HIP(hipMemcpyAsync(&tot[0], w.gp + n, 8, hipMemcpyDeviceToHost, st));
-    RLH_HIP(hipMemcpyAsync(&tot[1], w.sa + n, 8, hipMemcpyDeviceToHost, st));
-    RLH_HIP(hipMemcpyAsync(&tot[2], w.sb + n, 8, hipMemcpyDeviceToHost, st));
-    RLH_HIP(hipStreamSynchronize(st));
-    if (hs.err != kNoError) return report(hs);
-    const int64_t before = gnnz;
-    gnnz = tot[0], c8 = tot[1] & 0xffffffff, c16 = tot[1] >> 32, c32 = tot[2];
-    RLH_REQUIRE(gnnz >= before && gnnz <= room && c8 >= 0 && c8 <= c16 && c16 <= c32 && c32 <= n,
-                "%s: inconsistent row counts of the pattern", name);
+    const int64_t before = gnnz;                   // (the kernels above are done with w.gp when the scans write it)
+    if (int rc = pattern_totals(name, n, w, cap, before, room, &hs, &gnnz, &bins)) return rc;
     hs.truncated = hs.limited;
-    w.level = w.gi;
-    w.gi = nullptr;
-    RLH_HIP(hipMalloc((void **)&w.gi, (size_t)gnnz * 4));
-    bins = Bins{w.sa, w.sb, c8, c16, c32, w.rows};
-    hipLaunchKernelGGL(fsai_fill, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, w.slab, w.sp, w.gp, w.gi, bins);
+    RLH_HIP(w.get(&gi, gnnz));
+    hipLaunchKernelGGL(fsai_fill, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, slab, sp, w.gp, gi, bins);
   }
   h->nnz = gnnz;
   h->truncated = (int64_t)hs.truncated;
   h->longest = hs.longest;
-  RLH_HIP(hipMalloc(&w.gv, (size_t)gnnz * es));
+  T *gv = nullptr;
+  RLH_HIP(w.get(&gv, gnnz));
   // ---- the rows, bin by bin
-  launch_setup<T, kShort>(c8, w.rows, ip64, ix32, va, w.gp, w.gi, (T *)w.gv, w.status);
-  launch_setup<T, 16>(c16 - c8, w.rows + c8, ip64, ix32, va, w.gp, w.gi, (T *)w.gv, w.status);
-  launch_setup<T, 32>(c32 - c16, w.rows + c16, ip64, ix32, va, w.gp, w.gi, (T *)w.gv, w.status);
-  launch_setup<T, kMaxRow>(n - c32, w.rows + c32, ip64, ix32, va, w.gp, w.gi, (T *)w.gv, w.status);
+  for_each_bin(bins, n, [&](auto lanes, int64_t count, const int32_t *list) {
+    constexpr int kLanes = decltype(lanes)::value;
+    launch_bin<T, kLanes>(fsai_setup<T, kLanes>, count, list, ip64, ix32, va, w.gp, gi, gv, w.status);
+  });
   RLH_HIP(hipGetLastError());
   RLH_HIP(hipMemcpyAsync(&hs, w.status, sizeof hs, hipMemcpyDeviceToHost, st));
   RLH_HIP(hipStreamSynchronize(st));
-  if (hs.err != kNoError) return report(hs);
+  if (hs.err != kNoError) return report(name, hs, cap);
   // ---- G and G^H as one sparse data operator (it copies the arrays: 32-bit row pointers where they can hold nnz)
   int rc;
   if (gnnz < INT32_MAX) {
-    RLH_HIP(hipMalloc((void **)&w.gp32, (size_t)(n + 1) * 4));
-    hipLaunchKernelGGL((spd_convert_index<int64_t, int32_t>), dim3(blocks_for(n + 1, kBlock, 4096)), blk, 0, st, n + 1, w.gp, w.gp32);
+    int32_t *gp32 = nullptr;
+    RLH_HIP(w.get(&gp32, n + 1));
+    hipLaunchKernelGGL((spd_convert_index<int64_t, int32_t>), dim3(blocks_for(n + 1, kBlock, 4096)), blk, 0, st, n + 1, w.gp, gp32);
     RLH_HIP(hipGetLastError());
-    rc = rlh_spd_create_device(&h->spd, h->dtype, n, n, 32, w.gp32, w.gi, w.gv);
+    rc = rlh_spd_create_device(&h->spd, h->dtype, n, n, 32, gp32, gi, gv);
   } else {
-    RLH_HIP(hipFree(w.cols));
-    w.cols = nullptr;
+    RLH_HIP(w.release(cols));         // (the set-up was the last to read the converted columns)
     int64_t *gi64 = nullptr;
-    RLH_HIP(hipMalloc((void **)&gi64, (size_t)gnnz * 8));
-    hipLaunchKernelGGL((spd_convert_index<int32_t, int64_t>), dim3(blocks_for(gnnz, kBlock, 8192)), blk, 0, st, gnnz, w.gi, gi64);
-    rc = rlh_spd_create_device(&h->spd, h->dtype, n, n, 64, w.gp, gi64, w.gv);
-    (void)hipFree(gi64);
+    RLH_HIP(w.get(&gi64, gnnz));
+    hipLaunchKernelGGL((spd_convert_index<int32_t, int64_t>), dim3(blocks_for(gnnz, kBlock, 8192)), blk, 0, st, gnnz, gi, gi64);
+    rc = rlh_spd_create_device(&h->spd, h->dtype, n, n, 64, w.gp, gi64, gv);
   }
   if (rc) return rc;
   RLH_HIP(hipEventRecord(w.e1, st));
@@ -808,62 +825,43 @@ int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T 
 }
 
 template <typename P, typename I>
-int fsai_build_any(rlh_fsai *h, const char *name, const void *ip, const void *ix, const void *va, int max_row, int four) {
+int fsai_build_any(rlh_fsai *h, const char *name, const void *ip, const void *ix, const void *va, const FsaiPlan &plan) {
   switch (h->dtype) {
-    case RLH_S: return fsai_build<float, P, I>(h, name, (const P *)ip, (const I *)ix, (const float *)va, max_row, four);
-    case RLH_D: return fsai_build<double, P, I>(h, name, (const P *)ip, (const I *)ix, (const double *)va, max_row, four);
-    case RLH_C: return fsai_build<c32, P, I>(h, name, (const P *)ip, (const I *)ix, (const c32 *)va, max_row, four);
-    case RLH_Z: return fsai_build<c64, P, I>(h, name, (const P *)ip, (const I *)ix, (const c64 *)va, max_row, four);
+    case RLH_S: return fsai_build<float, P, I>(h, name, (const P *)ip, (const I *)ix, (const float *)va, plan);
+    case RLH_D: return fsai_build<double, P, I>(h, name, (const P *)ip, (const I *)ix, (const double *)va, plan);
+    case RLH_C: return fsai_build<c32, P, I>(h, name, (const P *)ip, (const I *)ix, (const c32 *)va, plan);
+    case RLH_Z: return fsai_build<c64, P, I>(h, name, (const P *)ip, (const I *)ix, (const c64 *)va, plan);
   }
   return 1;
 }
 
 constexpr int kMaxSteps = 63, kMaxStepSize = 16;
 
-// steps = 0: a build without enrichment (the entry points that have no such argument)
-int check_create_args(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, const void *indptr, int max_row, int levels,
-                      bool adaptive, int steps, int step_size) {
+int check_create_args(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, const void *indptr, const FsaiPlan &plan) {
   RLH_REQUIRE(ph != nullptr, "%s: null handle pointer", name);
   *ph = nullptr;
   RLH_REQUIRE(dtype_valid(dtype), "%s: unknown dtype %d", name, dtype);
   RLH_REQUIRE(n >= 0 && n < INT32_MAX, "%s: the size must lie in [0, 2^31 - 1)", name);
-  RLH_REQUIRE(max_row >= 1 && max_row <= kMaxRow, "%s: max_row must lie in [1, %d], got %d", name, kMaxRow, max_row);
-  RLH_REQUIRE(levels >= 1 && levels <= kMaxLevels, "%s: levels must lie in [1, %d], got %d", name, kMaxLevels, levels);
-  if (adaptive) {
-    RLH_REQUIRE(steps >= 1 && steps <= kMaxSteps, "%s: steps must lie in [1, %d], got %d", name, kMaxSteps, steps);
-    RLH_REQUIRE(step_size >= 1 && step_size <= kMaxStepSize, "%s: step_size must lie in [1, %d], got %d", name, kMaxStepSize,
-                step_size);
+  RLH_REQUIRE(plan.max_row >= 1 && plan.max_row <= kMaxRow, "%s: max_row must lie in [1, %d], got %d", name, kMaxRow, plan.max_row);
+  RLH_REQUIRE(plan.levels >= 1 && plan.levels <= kMaxLevels, "%s: levels must lie in [1, %d], got %d", name, kMaxLevels, plan.levels);
+  if (plan.adaptive) {
+    RLH_REQUIRE(plan.steps >= 1 && plan.steps <= kMaxSteps, "%s: steps must lie in [1, %d], got %d", name, kMaxSteps, plan.steps);
+    RLH_REQUIRE(plan.step_size >= 1 && plan.step_size <= kMaxStepSize, "%s: step_size must lie in [1, %d], got %d", name,
+                kMaxStepSize, plan.step_size);
   }
   RLH_REQUIRE(indptr, "%s: null indptr", name);
   return 0;
 }
 
-// RLH_FSAI_BINS=0: the two bins of 8 and 64 lanes per row; read by every create call
-int four_bins() {
-  const char *e = getenv("RLH_FSAI_BINS");
-  return (e && e[0] == '0' && e[1] == 0) ? 0 : 1;
-}
-
-int create_device(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, int index_bits, const void *d_indptr,
-                  const void *d_indices, const void *d_values, int max_row, int levels, bool adaptive = false, int steps = 0,
-                  int step_size = 0) {
-  if (int rc = require_ready()) return rc;
-  if (int rc = check_create_args(name, ph, dtype, n, d_indptr, max_row, levels, adaptive, steps, step_size)) return rc;
-  RLH_REQUIRE(index_bits == 32 || index_bits == 64, "%s: index_bits must be 32 or 64, got %d", name, index_bits);
+// The handle of a build: build(h) runs for n > 0; *ph is set when it succeeds
+template <typename Build> int make_handle(rlh_fsai_t *ph, int dtype, int64_t n, const FsaiPlan &plan, Build build) {
   rlh_fsai *h = new rlh_fsai();
   h->dtype = dtype;
   h->n = n;
-  h->levels = levels;
-  if (adaptive) {
-    h->steps = steps;
-    h->step_size = step_size;
-  }
-  const int four = four_bins();
-  int rc = 0;
-  if (n > 0)
-    rc = index_bits == 32 ? fsai_build_any<int32_t, int32_t>(h, name, d_indptr, d_indices, d_values, max_row, four)
-                          : fsai_build_any<int64_t, int64_t>(h, name, d_indptr, d_indices, d_values, max_row, four);
-  if (rc) {
+  h->levels = plan.levels;
+  h->steps = plan.steps;
+  h->step_size = plan.step_size;
+  if (int rc = n > 0 ? build(h) : 0) {
     rlh_fsai_destroy(h);
     return rc;
   }
@@ -871,50 +869,44 @@ int create_device(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, int in
   return 0;
 }
 
-int create_host(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
-                const void *values, int max_row, int levels, bool adaptive = false, int steps = 0, int step_size = 0) {
+int create_device(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, int index_bits, const void *d_indptr,
+                  const void *d_indices, const void *d_values, const FsaiPlan &plan) {
   if (int rc = require_ready()) return rc;
-  if (int rc = check_create_args(name, ph, dtype, n, indptr, max_row, levels, adaptive, steps, step_size)) return rc;
+  if (int rc = check_create_args(name, ph, dtype, n, d_indptr, plan)) return rc;
+  RLH_REQUIRE(index_bits == 32 || index_bits == 64, "%s: index_bits must be 32 or 64, got %d", name, index_bits);
+  return make_handle(ph, dtype, n, plan, [&](rlh_fsai *h) {
+    return index_bits == 32 ? fsai_build_any<int32_t, int32_t>(h, name, d_indptr, d_indices, d_values, plan)
+                            : fsai_build_any<int64_t, int64_t>(h, name, d_indptr, d_indices, d_values, plan);
+  });
+}
+
+int create_host(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
+                const void *values, const FsaiPlan &plan) {
+  if (int rc = require_ready()) return rc;
+  if (int rc = check_create_args(name, ph, dtype, n, indptr, plan)) return rc;
   // what decides how much is uploaded is checked here; everything else by the kernels, as for device arrays
   RLH_REQUIRE(indptr[0] == 0, "%s: indptr[0] must be 0", name);
   for (int64_t r = 0; r < n; ++r) RLH_REQUIRE(indptr[r + 1] >= indptr[r], "%s: indptr decreases at row %lld", name, (long long)r);
   const int64_t nnz = indptr[n], es = dtype_size(dtype);
   RLH_REQUIRE(nnz == 0 || (indices && values), "%s: null indices or values", name);
-  rlh_fsai *h = new rlh_fsai();
-  h->dtype = dtype;
-  h->n = n;
-  h->levels = levels;
-  if (adaptive) {
-    h->steps = steps;
-    h->step_size = step_size;
-  }
-  const int four = four_bins();
-  int rc = 0;
-  if (n > 0) {
+  return make_handle(ph, dtype, n, plan, [&](rlh_fsai *h) {
     int64_t *d_ip = nullptr;
     int32_t *d_ix = nullptr;
     void *d_va = nullptr;
+    int rc = 0;
     hipError_t e = hipMalloc((void **)&d_ip, (size_t)(n + 1) * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&d_ix, (size_t)std::max<int64_t>(4 * nnz, 4));
     if (e == hipSuccess) e = hipMalloc(&d_va, (size_t)std::max<int64_t>(es * nnz, 16));
     if (e == hipSuccess) e = hipMemcpy(d_ip, indptr, (size_t)(n + 1) * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess && nnz) e = hipMemcpy(d_ix, indices, (size_t)nnz * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess && nnz) e = hipMemcpy(d_va, values, (size_t)(nnz * es), hipMemcpyHostToDevice);
-    if (e == hipSuccess) rc = fsai_build_any<int64_t, int32_t>(h, name, d_ip, d_ix, d_va, max_row, four);
+    if (e == hipSuccess) rc = fsai_build_any<int64_t, int32_t>(h, name, d_ip, d_ix, d_va, plan);
     (void)hipFree(d_ip);
     (void)hipFree(d_ix);
     (void)hipFree(d_va);
-    if (e != hipSuccess) {
-      rlh_fsai_destroy(h);
-      RLH_HIP(e);
-    }
-  }
-  if (rc) {
-    rlh_fsai_destroy(h);
+    RLH_HIP(e);
     return rc;
-  }
-  *ph = h;
-  return 0;
+  });
 }
 
 }  // namespace
@@ -924,34 +916,35 @@ using namespace rlh;
 
 extern "C" int rlh_fsai_create_device(rlh_fsai_t *ph, int dtype, int64_t n, int index_bits, const void *d_indptr,
                                       const void *d_indices, const void *d_values, int max_row) {
-  return create_device("rlh_fsai_create_device", ph, dtype, n, index_bits, d_indptr, d_indices, d_values, max_row, 1);
+  return create_device("rlh_fsai_create_device", ph, dtype, n, index_bits, d_indptr, d_indices, d_values, {max_row, 1, false, 0, 0});
 }
 
 extern "C" int rlh_fsai_create_levels_device(rlh_fsai_t *ph, int dtype, int64_t n, int index_bits, const void *d_indptr,
                                              const void *d_indices, const void *d_values, int max_row, int levels) {
-  return create_device("rlh_fsai_create_levels_device", ph, dtype, n, index_bits, d_indptr, d_indices, d_values, max_row, levels);
+  return create_device("rlh_fsai_create_levels_device", ph, dtype, n, index_bits, d_indptr, d_indices, d_values,
+                       {max_row, levels, false, 0, 0});
 }
 
 extern "C" int rlh_fsai_create(rlh_fsai_t *ph, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
                                const void *values, int max_row) {
-  return create_host("rlh_fsai_create", ph, dtype, n, indptr, indices, values, max_row, 1);
+  return create_host("rlh_fsai_create", ph, dtype, n, indptr, indices, values, {max_row, 1, false, 0, 0});
 }
 
 extern "C" int rlh_fsai_create_levels(rlh_fsai_t *ph, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
                                       const void *values, int max_row, int levels) {
-  return create_host("rlh_fsai_create_levels", ph, dtype, n, indptr, indices, values, max_row, levels);
+  return create_host("rlh_fsai_create_levels", ph, dtype, n, indptr, indices, values, {max_row, levels, false, 0, 0});
 }
 
 extern "C" int rlh_fsai_create_adaptive_device(rlh_fsai_t *ph, int dtype, int64_t n, int index_bits, const void *d_indptr,
                                                const void *d_indices, const void *d_values, int max_row, int levels, int steps,
                                                int step_size) {
-  return create_device("rlh_fsai_create_adaptive_device", ph, dtype, n, index_bits, d_indptr, d_indices, d_values, max_row, levels,
-                       true, steps, step_size);
+  return create_device("rlh_fsai_create_adaptive_device", ph, dtype, n, index_bits, d_indptr, d_indices, d_values,
+                       {max_row, levels, true, steps, step_size});
 }
 
 extern "C" int rlh_fsai_create_adaptive(rlh_fsai_t *ph, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
                                         const void *values, int max_row, int levels, int steps, int step_size) {
-  return create_host("rlh_fsai_create_adaptive", ph, dtype, n, indptr, indices, values, max_row, levels, true, steps, step_size);
+  return create_host("rlh_fsai_create_adaptive", ph, dtype, n, indptr, indices, values, {max_row, levels, true, steps, step_size});
 }
 
 extern "C" int rlh_fsai_adaptive(rlh_fsai_t h, int *steps, int *step_size) {

@@ -1,6 +1,6 @@
 """Adaptive patterns of the approximate inverse (rlh_fsai_create_adaptive*, ApproximateInverse(steps=..., step_size=...)):
-cases shared by the CPU tier (tests/fake_fsai_adaptive.py) and the GPU tier.  Matrices, helpers and the bound of the
-defining property come from tests/_fsai_cases.py (`base`) and tests/_fsai_levels_cases.py (`lv`).
+cases shared by the CPU tier (tests/fake_fsai.py) and the GPU tier.  The raw entry points (`create`, `built`), matrices,
+helpers and the bound of the defining property come from tests/_fsai_cases.py (`base`) and tests/_fsai_levels_cases.py (`lv`).
 
 THE ORACLE (`oracle_row`, `oracle`) is written from the definition in include/rlhip.h and shares nothing with the
 library or the stand-in.  Per row, in dense float64 / complex128 NumPy: it starts from the level pattern (`lv.oracle`:
@@ -23,7 +23,6 @@ its bin in a grid-stride loop; rows go to the bin of their capacity min(max_row,
 16-lane bin takes 16 rows per workgroup in real arithmetic (256 threads).
 """
 
-import ctypes
 import functools
 
 import numpy as np
@@ -32,7 +31,8 @@ import scipy.sparse as sp
 
 import _fsai_cases as base
 import _fsai_levels_cases as lv
-from _fsai_cases import TYPES, _L, _check, check_row, csr_tensor, destroy, get, hermitian_from_upper, info, kaporin, last_error, same_bits
+from _fsai_cases import (TYPES, _check, adaptive_of, built, check_row, create, csr_tensor, destroy, hermitian_from_upper, kaporin,
+                         last_error, levels_of, same_bits)
 
 BLOCKS_PER_CU = 8
 ENRICH_ROWS_PER_BLOCK = {16: 16}
@@ -151,45 +151,6 @@ def oracle(A, levels, steps, step_size, max_row=64):
     return _oracle(id(A), levels, steps, step_size, max_row)
 
 
-# ---------------------------------------------------------------- the raw entry points
-def create_adaptive_device(A, levels, steps, step_size, bits=64, max_row=64):
-    from raleigh_amd import _lib
-    it = {32: np.int32, 64: np.int64}[bits]
-    arrays = (A.indptr.astype(it), A.indices.astype(it), np.ascontiguousarray(A.data))
-    bufs = [base.dev(a) for a in arrays]
-    h = ctypes.c_void_p(12345)
-    rc = _L().rlh_fsai_create_adaptive_device(ctypes.byref(h), _lib.DTYPE_CODE[A.dtype.type], A.shape[0], bits, bufs[0].ptr,
-                                              bufs[1].ptr, bufs[2].ptr, max_row, levels, steps, step_size)
-    return rc, h
-
-
-def create_adaptive_host(A, levels, steps, step_size, max_row=64):
-    from raleigh_amd import _lib
-    ip, ix, va = A.indptr.astype(np.int64), A.indices.astype(np.int32), np.ascontiguousarray(A.data)
-    h = ctypes.c_void_p(12345)
-    rc = _L().rlh_fsai_create_adaptive(ctypes.byref(h), _lib.DTYPE_CODE[A.dtype.type], A.shape[0], _lib.host_ptr(ip),
-                                       _lib.host_ptr(ix), _lib.host_ptr(va), max_row, levels, steps, step_size)
-    return rc, h
-
-
-def adaptive_of(h):
-    a, b = ctypes.c_int(-1), ctypes.c_int(-1)
-    _check(_L().rlh_fsai_adaptive(h, ctypes.byref(a), ctypes.byref(b)))
-    return a.value, b.value
-
-
-def built(A, levels, steps, step_size, host=False, **kw):
-    """G (SciPy) and the info record of an adaptive build that must succeed."""
-    make = create_adaptive_host if host else create_adaptive_device
-    rc, h = make(A, levels, steps, step_size, **kw)
-    _check(rc)
-    try:
-        assert lv.levels_of(h) == levels and adaptive_of(h) == (steps, step_size)
-        return get(h, A.dtype.type), info(h)
-    finally:
-        destroy(h)
-
-
 def row_of(G, i):
     return G.indices[G.indptr[i]:G.indptr[i + 1]]
 
@@ -213,7 +174,7 @@ def pattern(which, config):
     if which == 'cut-d' or (levels == 2 and which != 'lap'):
         assert o.cut_and_kept > 0
     for bits in (32, 64):
-        G, f = built(A, levels, steps, step_size, bits=bits, max_row=max_row)
+        G, f = built(A, '_adaptive', levels, steps, step_size, bits=bits, max_row=max_row)
         assert f['nnz'] == G.nnz == int(G.indptr[-1]) and G.shape == (n, n)
         if left_out == 0:
             assert np.array_equal(G.indptr, o.indptr) and np.array_equal(G.indices, o.indices), (which, config, bits)
@@ -226,29 +187,17 @@ def pattern(which, config):
 # ---------------------------------------------------------------- 2. padding, bit for bit
 def padded_on(A, G):
     """A plus explicit zeros on the pattern of G and its mirror image (as lv.padded, from a fetched pattern)."""
-    n = A.shape[0]
-    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(A.indptr))
-    own = rows * n + A.indices
-    pr = np.repeat(np.arange(n, dtype=np.int64), np.diff(G.indptr))
-    pc = G.indices.astype(np.int64)
-    key = np.unique(np.concatenate([own, pr * n + pc, pc * n + pr]))
-    data = np.zeros(key.size, dtype=A.dtype)
-    data[np.searchsorted(key, own)] = A.data
-    indptr = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum(np.bincount(key // n, minlength=n), out=indptr[1:])
-    B = sp.csr_matrix((data, (key % n).astype(np.int32), indptr), shape=A.shape)
-    assert B.nnz == key.size and B.has_sorted_indices
-    return B
+    return base.padded_with(A, np.repeat(np.arange(A.shape[0]), np.diff(G.indptr)), G.indices)
 
 
 def padding(code):
     for A, (levels, steps, step_size) in ((lv.lap(code), (1, 4, 2)), (lv.banded(code), (2, 2, 4)), (lv.banded(code), (1, 4, 2))):
         for max_row in (64, 12):
-            G, f = built(A, levels, steps, step_size, max_row=max_row)
+            G, f = built(A, '_adaptive', levels, steps, step_size, max_row=max_row)
             assert G.nnz > lv.oracle(A, levels, max_row)[1].size               # (it grew)
-            want, _ = base.built(padded_on(A, G), max_row=max_row)
+            want, _ = built(padded_on(A, G), max_row=max_row)
             assert same_bits(G, want), (levels, steps, step_size, max_row)
-            Gh, fh = built(A, levels, steps, step_size, host=True, max_row=max_row)
+            Gh, fh = built(A, '_adaptive', levels, steps, step_size, host=True, max_row=max_row)
             assert same_bits(Gh, want) and fh['truncated'] == f['truncated'] and fh['longest'] == f['longest']
 
 
@@ -260,7 +209,7 @@ def defining_property(code, config):
     B = A.copy()
     rows = np.repeat(np.arange(n), np.diff(A.indptr))
     B.data[B.indices < rows] = np.nan                      # nothing below the diagonal is read
-    G, f = built(B, levels, steps, step_size, bits=32)
+    G, f = built(B, '_adaptive', levels, steps, step_size, bits=32)
     ip0, ix0, _, _ = lv.oracle(A, levels, 64)
     assert G.nnz > ix0.size
     worst = 0.0
@@ -278,9 +227,9 @@ def nesting():
         n = A.shape[0]
         u = base.unit(np.float64)
         for step_size in (1, 3):
-            before, _ = lv.built(A, 1, bits=32)
+            before, _ = built(A, '_levels', 1, bits=32)
             for t in (1, 2, 3, 4):
-                G, _ = built(A, 1, t, step_size, bits=32)
+                G, _ = built(A, '_adaptive', 1, t, step_size, bits=32)
                 assert G.nnz > before.nnz, (t, step_size)
                 for i in range(n):
                     assert np.all(np.isin(row_of(before, i), row_of(G, i))), (t, step_size, i)
@@ -296,7 +245,7 @@ def quality():
         d = hermitian_from_upper(A).toarray()
         ks = []
         for steps, step_size in ((0, 0), (2, 3), (4, 4)):
-            G, _ = built(A, 1, steps, step_size, bits=32) if steps else lv.built(A, 1, bits=32)
+            G, _ = built(A, '_adaptive', 1, steps, step_size, bits=32) if steps else built(A, '_levels', 1, bits=32)
             g = G.toarray()
             ks.append(kaporin(g @ d @ g.T))
         print('Kaporin numbers at level 1, + 2 steps of 3, + 4 steps of 4 (n = %d): %.6f %.6f %.6f' % ((n,) + tuple(ks)))
@@ -310,13 +259,13 @@ def quality():
 def unchanged_without_steps(code, device):
     from raleigh_amd.algebra.hip.precond import ApproximateInverse
     A = base.matrix(code)
-    want, _ = base.built(A, bits=32)
+    want, _ = built(A, bits=32)
     made = [ApproximateInverse(A), ApproximateInverse(A, steps=0, step_size=5), ApproximateInverse(csr_tensor(A, device), steps=0)]
     for T in made:
         assert same_bits(T.csr(), want) and (T.levels, T.steps) == (1, 0)
         assert adaptive_of(T._h) == (0, 0)
     assert made[0].step_size == 1 and made[1].step_size == 5
-    two, _ = lv.built(A, 2, bits=32)
+    two, _ = built(A, '_levels', 2, bits=32)
     assert same_bits(ApproximateInverse(A, levels=2, steps=0).csr(), two)
 
 
@@ -324,9 +273,9 @@ def unchanged_without_steps(code, device):
 def bins(code, monkeypatch):
     A = lv.banded(code)
     monkeypatch.setenv('RLH_FSAI_BINS', '0')
-    two, f2 = built(A, 1, 4, 2, bits=32)
+    two, f2 = built(A, '_adaptive', 1, 4, 2, bits=32)
     monkeypatch.delenv('RLH_FSAI_BINS')
-    four, f4 = built(A, 1, 4, 2, bits=32)
+    four, f4 = built(A, '_adaptive', 1, 4, 2, bits=32)
     assert same_bits(two, four) and f2['truncated'] == f4['truncated'] and f2['longest'] == f4['longest']
     lens = np.diff(four.indptr)
     for lo, hi in lv.CLASSES[:4]:
@@ -341,7 +290,7 @@ def loops(cu):
     per_pass = cu * BLOCKS_PER_CU * ENRICH_ROWS_PER_BLOCK[16]
     n = per_pass + 300
     A = lv.band(np.full(n, w), np.float64, 33)
-    G, f = built(A, levels, steps, step_size, bits=32)
+    G, f = built(A, '_adaptive', levels, steps, step_size, bits=32)
     lens0 = np.minimum(np.arange(n), w) + 1
     in_bin = np.flatnonzero(lens0 + steps * step_size > 8)               # ascending: the order of the bin's list
     assert in_bin.size > per_pass and np.all(lens0[in_bin] + steps * step_size <= 16)
@@ -372,25 +321,25 @@ def indefinite():
 
 def rejections_raw():
     A = base.matrix('d')
-    for make, name in ((create_adaptive_device, 'rlh_fsai_create_adaptive_device'), (create_adaptive_host, 'rlh_fsai_create_adaptive')):
+    for host, name in ((False, 'rlh_fsai_create_adaptive_device'), (True, 'rlh_fsai_create_adaptive')):
         for args, kw, text in (((1, 0, 1), {}, 'steps must lie in [1, 63], got 0'), ((1, 64, 1), {}, 'steps must lie in [1, 63], got 64'),
                                ((1, 1, 0), {}, 'step_size must lie in [1, 16], got 0'),
                                ((1, 1, 17), {}, 'step_size must lie in [1, 16], got 17'),
                                ((0, 1, 1), {}, 'levels must lie in [1, 8], got 0'), ((9, 1, 1), {}, 'levels must lie in [1, 8], got 9'),
                                ((1, 1, 1), {'max_row': 65}, 'max_row must lie in [1, 64], got 65')):
-            rc, h = make(A, *args, **kw)
+            rc, h = create(A, '_adaptive', *args, host=host, **kw)
             assert rc != 0 and not h.value, (name, args)
             assert last_error().endswith('%s: %s' % (name, text)), last_error()
         B = indefinite()
         for steps in (1, 2):                # found by the set-up of the final pattern, by the second step's own solve
-            rc, h = make(B, 1, steps, 1)
+            rc, h = create(B, '_adaptive', 1, steps, 1, host=host)
             assert rc != 0 and not h.value
             assert last_error().endswith('%s: local block of row 21 is not positive definite' % name), last_error()
-        rc, h = make(A, 8, 63, 16, max_row=3)
+        rc, h = create(A, '_adaptive', 8, 63, 16, host=host, max_row=3)
         _check(rc)
-        assert lv.levels_of(h) == 8 and adaptive_of(h) == (63, 16)
+        assert levels_of(h) == 8 and adaptive_of(h) == (63, 16)
         destroy(h)
-    rc, h = lv.create_levels_device(B, 1)                     # (the level pattern alone is fine)
+    rc, h = create(B, '_levels', 1)                             # (the level pattern alone is fine)
     _check(rc)
     assert adaptive_of(h) == (0, 0)
     destroy(h)
@@ -419,12 +368,12 @@ def rejections_class(fake=None):
 def class_inputs(device):
     from raleigh_amd.algebra.hip.precond import ApproximateInverse
     A = lv.banded('d')
-    want, f = built(A, 1, 4, 2)
+    want, f = built(A, '_adaptive', 1, 4, 2)
     made = [ApproximateInverse(A, steps=4, step_size=2), ApproximateInverse(csr_tensor(A, device), steps=4, step_size=2),
             ApproximateInverse(csr_tensor(A, 'cpu'), steps=4, step_size=2)]
     for T in made:
         assert (T.levels, T.steps, T.step_size) == (1, 4, 2) and same_bits(T.csr(), want)
-        assert adaptive_of(T._h) == (4, 2) and lv.levels_of(T._h) == 1
+        assert adaptive_of(T._h) == (4, 2) and levels_of(T._h) == 1
         assert T.truncated_rows == f['truncated'] and T.longest_row == f['longest'] and T.nnz == want.nnz
         assert abs(T.fill - want.nnz / A.nnz) < 1e-15
     return made

@@ -85,7 +85,6 @@ def unit(dt):
     return float(np.finfo(np.dtype(dt)).eps) / 2
 
 
-
 def rsqrt_rounded(d):
     """d^(-1/2) correctly rounded to double: the longdouble value rounded, then moved to a neighbour where the exact
     comparison d m^2 <> 1 at the midpoint m says so (rounding twice, 64 then 53 bits, misses about one value in 2^11)."""
@@ -155,27 +154,24 @@ def dense_wide(code, which='profile'):
 
 
 # ---------------------------------------------------------------- the raw entry points
-def create_device(A, bits=64, max_row=64, indptr=None, indices=None, keep=None, n=None):
-    """(rc, handle) of rlh_fsai_create_device on device copies of A's arrays (or of the given ones)."""
+def create(A, entry='', levels=None, steps=None, step_size=None, host=False, bits=64, max_row=64, indptr=None, indices=None,
+           keep=None, n=None):
+    """(rc, handle) of one of the six create calls: rlh_fsai_create<entry> on A's arrays (host=True) or
+    rlh_fsai_create<entry>_device on device copies of them (or of the given indptr / indices; keep collects the arrays
+    and their buffers).  entry: '' , '_levels' (takes levels) or '_adaptive' (takes levels, steps and step_size)."""
     from raleigh_amd import _lib
+    more = {'': (), '_levels': (levels,), '_adaptive': (levels, steps, step_size)}[entry]
     it = {32: np.int32, 64: np.int64}.get(bits, np.int64)
-    arrays = ((A.indptr if indptr is None else indptr).astype(it), (A.indices if indices is None else indices).astype(it),
-              np.ascontiguousarray(A.data))
-    bufs = [dev(a) for a in arrays]
+    arrays = ((A.indptr if indptr is None else indptr).astype(np.int64 if host else it),
+              (A.indices if indices is None else indices).astype(np.int32 if host else it), np.ascontiguousarray(A.data))
     h = ctypes.c_void_p(12345)
-    rc = _L().rlh_fsai_create_device(ctypes.byref(h), _lib.DTYPE_CODE[A.dtype.type], A.shape[0] if n is None else n, bits,
-                                     bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, max_row)
+    head = (ctypes.byref(h), _lib.DTYPE_CODE[A.dtype.type], A.shape[0] if n is None else n)
+    if host:
+        return getattr(_L(), 'rlh_fsai_create' + entry)(*head, *[_lib.host_ptr(a) for a in arrays], max_row, *more), h
+    bufs = [dev(a) for a in arrays]
+    rc = getattr(_L(), 'rlh_fsai_create%s_device' % entry)(*head, bits, *[b.ptr for b in bufs], max_row, *more)
     if keep is not None:
         keep.extend(zip(arrays, bufs))
-    return rc, h
-
-
-def create_host(A, max_row=64):
-    from raleigh_amd import _lib
-    ip, ix, va = A.indptr.astype(np.int64), A.indices.astype(np.int32), np.ascontiguousarray(A.data)
-    h = ctypes.c_void_p(12345)
-    rc = _L().rlh_fsai_create(ctypes.byref(h), _lib.DTYPE_CODE[A.dtype.type], A.shape[0], _lib.host_ptr(ip), _lib.host_ptr(ix),
-                              _lib.host_ptr(va), max_row)
     return rc, h
 
 
@@ -203,14 +199,46 @@ def destroy(h):
     _L().rlh_fsai_destroy(h)
 
 
-def built(A, **kw):
-    """G (SciPy) and the info record of a device build that must succeed."""
-    rc, h = create_device(A, **kw)
+def levels_of(h):
+    v = ctypes.c_int(-1)
+    _check(_L().rlh_fsai_levels(h, ctypes.byref(v)))
+    return v.value
+
+
+def adaptive_of(h):
+    a, b = ctypes.c_int(-1), ctypes.c_int(-1)
+    _check(_L().rlh_fsai_adaptive(h, ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value
+
+
+def built(A, entry='', levels=None, steps=None, step_size=None, **kw):
+    """G (SciPy) and the info record of a build (the arguments of `create`) that must succeed; where the entry point
+    takes levels or steps, the handle must answer with them."""
+    rc, h = create(A, entry, levels, steps, step_size, **kw)
     _check(rc)
     try:
+        if entry:
+            assert levels_of(h) == levels
+        if entry == '_adaptive':
+            assert adaptive_of(h) == (steps, step_size)
         return get(h, A.dtype.type), info(h)
     finally:
         destroy(h)
+
+
+def padded_with(A, rows, cols):
+    """A plus explicit zeros at the positions (rows, cols) and at their mirror images."""
+    n = A.shape[0]
+    own = np.repeat(np.arange(n, dtype=np.int64), np.diff(A.indptr)) * n + A.indices
+    pr, pc = np.asarray(rows, dtype=np.int64), np.asarray(cols, dtype=np.int64)
+    key = np.unique(np.concatenate([own, pr * n + pc, pc * n + pr]))
+    data = np.zeros(key.size, dtype=A.dtype)
+    data[np.searchsorted(key, own)] = A.data
+    indptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(key // n, minlength=n), out=indptr[1:])
+    B = sp.csr_matrix((data, (key % n).astype(np.int32), indptr), shape=A.shape)
+    assert B.nnz == key.size and B.has_sorted_indices
+    return B
 
 
 def same_bits(G1, G2):
@@ -269,7 +297,7 @@ def check_all_rows(G, code, which, max_row=64):
 def defining_property(code, bits):
     A = matrix(code)
     kept = []
-    rc, h = create_device(A, bits, keep=kept)
+    rc, h = create(A, bits=bits, keep=kept)
     _check(rc)
     try:
         G, f = get(h, A.dtype.type), info(h)
@@ -311,12 +339,7 @@ def bit_identity(code):
     G, _ = built(A, bits=64)
     G2, _ = built(A, bits=64)
     G32, _ = built(A, bits=32)
-    rc, h = create_host(A)
-    _check(rc)
-    try:
-        Gh = get(h, A.dtype.type)
-    finally:
-        destroy(h)
+    Gh, _ = built(A, host=True)
     assert same_bits(G, G2) and same_bits(G, G32) and same_bits(G, Gh)
 
 
@@ -361,7 +384,7 @@ def loops_long(cu):
 def application(code):
     dt = TYPES[code]
     A = matrix(code)
-    rc, h = create_device(A, 32)
+    rc, h = create(A, bits=32)
     _check(rc)
     try:
         G = get(h, dt)
@@ -410,7 +433,7 @@ def _without(A, i, j):
 
 
 def _refused(text, A, **kw):
-    rc, h = create_device(A, **kw)
+    rc, h = create(A, **kw)
     assert rc != 0 and not h.value, text
     assert text in last_error(), (text, last_error())
 
@@ -449,9 +472,9 @@ def rejections_raw():
     _refused('indptr[0] must be 0', A, indptr=changed(ip, 0, 1))
     _refused('column index out of range in row %d' % row, A, indices=changed(ix, k, N))
     _refused('columns of row %d must ascend strictly' % row, A, indices=swapped)
-    rc, h = create_host(C)
+    rc, h = create(C, host=True)
     assert rc != 0 and not h.value and 'rlh_fsai_create: local block of row 350 is not positive definite' in last_error()
-    rc, h = create_device(A)
+    rc, h = create(A)
     _check(rc)
     destroy(h)
 

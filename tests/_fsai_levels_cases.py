@@ -1,6 +1,6 @@
 """Level-of-fill patterns of the approximate inverse (rlh_fsai_create_levels*, ApproximateInverse(levels=...)): cases
-shared by the CPU tier (tests/fake_fsai_levels.py) and the GPU tier.  Helpers, the bound of the defining property
-(`check_row`, `beta`) and the N = 777 profile matrix come from tests/_fsai_cases.py.
+shared by the CPU tier (tests/fake_fsai.py) and the GPU tier.  The raw entry points (`create`, `built`), the helpers, the
+bound of the defining property (`check_row`, `beta`) and the N = 777 profile matrix come from tests/_fsai_cases.py.
 
 THE ORACLE.  With T the boolean pattern of the stored entries (i, j), j <= i, of A (explicit zeros count), the level
 pattern is that of T^levels, formed by SciPy sparse products; a row keeps its max_row largest columns, and is
@@ -17,7 +17,6 @@ grid-stride loop; the pattern kernels take 4 rows per workgroup (one wave each),
 set-up 8 rows in real arithmetic.
 """
 
-import ctypes
 import functools
 
 import numpy as np
@@ -25,7 +24,8 @@ import pytest
 import scipy.sparse as sp
 
 import _fsai_cases as base
-from _fsai_cases import TYPES, _L, _check, check_row, csr_tensor, destroy, get, hermitian_from_upper, info, kaporin, last_error, same_bits
+from _fsai_cases import (TYPES, _L, _check, built, check_row, create, csr_tensor, destroy, get, hermitian_from_upper, kaporin,
+                         last_error, levels_of, same_bits)
 
 BLOCKS_PER_CU = 8
 PATTERN_ROWS_PER_BLOCK = 4
@@ -118,57 +118,8 @@ def oracle(A, levels, max_row):
 
 def padded(A, levels):
     """A plus explicit zeros on the symmetrised pattern of tril(A)^levels."""
-    n = A.shape[0]
     P = full_pattern(A, levels).tocoo()
-    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(A.indptr))
-    own = rows * n + A.indices
-    pr, pc = P.row.astype(np.int64), P.col.astype(np.int64)
-    key = np.unique(np.concatenate([own, pr * n + pc, pc * n + pr]))
-    data = np.zeros(key.size, dtype=A.dtype)
-    data[np.searchsorted(key, own)] = A.data
-    indptr = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum(np.bincount(key // n, minlength=n), out=indptr[1:])
-    B = sp.csr_matrix((data, (key % n).astype(np.int32), indptr), shape=A.shape)
-    assert B.nnz == key.size and B.has_sorted_indices
-    return B
-
-
-# ---------------------------------------------------------------- the raw entry points
-def create_levels_device(A, levels, bits=64, max_row=64):
-    from raleigh_amd import _lib
-    it = {32: np.int32, 64: np.int64}[bits]
-    arrays = (A.indptr.astype(it), A.indices.astype(it), np.ascontiguousarray(A.data))
-    bufs = [base.dev(a) for a in arrays]
-    h = ctypes.c_void_p(12345)
-    rc = _L().rlh_fsai_create_levels_device(ctypes.byref(h), _lib.DTYPE_CODE[A.dtype.type], A.shape[0], bits, bufs[0].ptr,
-                                            bufs[1].ptr, bufs[2].ptr, max_row, levels)
-    return rc, h
-
-
-def create_levels_host(A, levels, max_row=64):
-    from raleigh_amd import _lib
-    ip, ix, va = A.indptr.astype(np.int64), A.indices.astype(np.int32), np.ascontiguousarray(A.data)
-    h = ctypes.c_void_p(12345)
-    rc = _L().rlh_fsai_create_levels(ctypes.byref(h), _lib.DTYPE_CODE[A.dtype.type], A.shape[0], _lib.host_ptr(ip),
-                                     _lib.host_ptr(ix), _lib.host_ptr(va), max_row, levels)
-    return rc, h
-
-
-def levels_of(h):
-    v = ctypes.c_int(-1)
-    _check(_L().rlh_fsai_levels(h, ctypes.byref(v)))
-    return v.value
-
-
-def built(A, levels, host=False, **kw):
-    """G (SciPy) and the info record of a build with levels that must succeed."""
-    rc, h = create_levels_host(A, levels, **kw) if host else create_levels_device(A, levels, **kw)
-    _check(rc)
-    try:
-        assert levels_of(h) == levels
-        return get(h, A.dtype.type), info(h)
-    finally:
-        destroy(h)
+    return base.padded_with(A, P.row, P.col)
 
 
 # ---------------------------------------------------------------- 1. the pattern, exactly
@@ -184,7 +135,7 @@ def pattern(which, levels):
     for max_row in (64, 5):
         indptr, indices, cut, longest = oracle(A, levels, max_row)
         for bits in (32, 64):
-            G, f = built(A, levels, bits=bits, max_row=max_row)
+            G, f = built(A, '_levels', levels, bits=bits, max_row=max_row)
             assert np.array_equal(G.indptr, indptr) and np.array_equal(G.indices, indices), (which, levels, max_row, bits)
             assert f['truncated'] == cut and f['longest'] == longest and f['nnz'] == len(indices)
 
@@ -195,11 +146,11 @@ def padding(code):
         for levels in (2, 3):
             B = padded(A, levels)
             for max_row in (64, 5):
-                want, fw = base.built(B, max_row=max_row)
+                want, fw = built(B, max_row=max_row)
                 cut = oracle(A, levels, max_row)[2]
                 assert fw['truncated'] == cut and (cut > 0) == (max_row == 5 or A is banded(code))
                 for host in (False, True):
-                    G, f = built(A, levels, host=host, max_row=max_row)
+                    G, f = built(A, '_levels', levels, host=host, max_row=max_row)
                     assert same_bits(G, want), (levels, max_row, host)
                     assert f['truncated'] == cut
 
@@ -210,7 +161,7 @@ def defining_property(code, levels):
     B = A.copy()
     rows = np.repeat(np.arange(A.shape[0]), np.diff(A.indptr))
     B.data[B.indices < rows] = np.nan                      # nothing below the diagonal is read
-    G, f = built(B, levels, bits=32)
+    G, f = built(B, '_levels', levels, bits=32)
     indptr, indices, cut, longest = oracle(A, levels, 64)
     assert np.array_equal(G.indptr, indptr) and f['truncated'] == cut and cut > 0 and f['longest'] == longest == 64
     worst = 0.0
@@ -225,7 +176,7 @@ def unchanged_level_one(code):
     from raleigh_amd.algebra.hip.precond import ApproximateInverse
     A = base.matrix(code)
     dt = A.dtype.type
-    made = [create_levels_device(A, 1, bits=32), base.create_device(A, 32), create_levels_host(A, 1), base.create_host(A)]
+    made = [create(A, '_levels', 1, bits=32), create(A, bits=32), create(A, '_levels', 1, host=True), create(A, host=True)]
     try:
         for rc, _ in made:
             _check(rc)
@@ -257,9 +208,9 @@ def unchanged_level_one(code):
 def bins(code, monkeypatch):
     A = banded(code)
     monkeypatch.setenv('RLH_FSAI_BINS', '0')
-    two, f2 = built(A, 2, bits=32)
+    two, f2 = built(A, '_levels', 2, bits=32)
     monkeypatch.delenv('RLH_FSAI_BINS')
-    four, f4 = built(A, 2, bits=32)
+    four, f4 = built(A, '_levels', 2, bits=32)
     assert same_bits(two, four) and f2['truncated'] == f4['truncated'] > 0 and f2['longest'] == f4['longest'] == 64
     lens = np.diff(four.indptr)
     for lo, hi in CLASSES[:4]:
@@ -274,7 +225,7 @@ def loops(cu, lanes):
     per_pass, per_pattern_pass = cu * BLOCKS_PER_CU * ROWS_PER_BLOCK[lanes], cu * BLOCKS_PER_CU * PATTERN_ROWS_PER_BLOCK
     n = per_pass + 300
     A = band(np.full(n, w), np.float64, 32)
-    G, f = built(A, 2, bits=32)
+    G, f = built(A, '_levels', 2, bits=32)
     indptr, indices, cut, longest = oracle(A, 2, 64)
     assert cut == 0 == f['truncated'] and longest == 2 * w + 1 == f['longest']
     assert np.array_equal(G.indptr, indptr) and np.array_equal(G.indices, indices)
@@ -297,7 +248,7 @@ def monotone_quality():
         d = hermitian_from_upper(A).toarray()
         ks = []
         for levels in (1, 2, 3):
-            G, f = built(A, levels, bits=32)
+            G, f = built(A, '_levels', levels, bits=32)
             assert f['truncated'] == 0, levels
             g = G.toarray()
             ks.append(kaporin(g @ d @ g.T))
@@ -311,15 +262,15 @@ def monotone_quality():
 # ---------------------------------------------------------------- 8. rejections
 def rejections_raw():
     A = base.matrix('d')
-    for make, name in ((create_levels_device, 'rlh_fsai_create_levels_device'), (create_levels_host, 'rlh_fsai_create_levels')):
+    for host, name in ((False, 'rlh_fsai_create_levels_device'), (True, 'rlh_fsai_create_levels')):
         for levels in (0, 9):
-            rc, h = make(A, levels)
+            rc, h = create(A, '_levels', levels, host=host)
             assert rc != 0 and not h.value
             assert last_error().endswith('%s: levels must lie in [1, 8], got %d' % (name, levels)), last_error()
-        rc, h = make(A, 9, max_row=65)
+        rc, h = create(A, '_levels', 9, host=host, max_row=65)
         assert rc != 0 and not h.value
         assert last_error().endswith('%s: max_row must lie in [1, 64], got 65' % name), last_error()
-        rc, h = make(A, 8, max_row=3)
+        rc, h = create(A, '_levels', 8, host=host, max_row=3)
         _check(rc)
         assert levels_of(h) == 8
         destroy(h)
@@ -342,7 +293,7 @@ def rejections_class(fake=None):
 def class_inputs(device):
     from raleigh_amd.algebra.hip.precond import ApproximateInverse
     A = banded('d')
-    want, f = built(A, 2)
+    want, f = built(A, '_levels', 2)
     made = [ApproximateInverse(A, levels=2), ApproximateInverse(csr_tensor(A, device), levels=2),
             ApproximateInverse(csr_tensor(A, 'cpu'), levels=2)]
     for T in made:

@@ -1,11 +1,11 @@
-"""CPU tier: adaptive patterns of the approximate inverse over tests/fake_fsai_adaptive.py (a NumPy stand-in for the
+"""CPU tier: adaptive patterns of the approximate inverse over tests/fake_fsai.py (a NumPy stand-in for the
 rlh_fsai_* entry points; CPU tensors stand for device tensors): the host logic of ApproximateInverse(steps=...,
 step_size=...), the checks and their messages, and the mathematics of the cases in tests/_fsai_adaptive_cases.py, which
 the GPU tier runs on the real library."""
 
 import pytest
 
-import fake_fsai_adaptive
+import fake_fsai
 import fake_lib
 import _fsai_adaptive_cases as cases
 
@@ -17,14 +17,14 @@ OLD = ('fsai_create', 'fsai_create_device', 'fsai_create_levels', 'fsai_create_l
 
 @pytest.fixture(autouse=True)
 def fake():
-    f = fake_fsai_adaptive.install()
+    f = fake_fsai.install()
     yield f
     fake_lib.uninstall()
 
 
 @pytest.fixture
 def device(monkeypatch):
-    fake_fsai_adaptive.as_device(monkeypatch)
+    fake_fsai.as_device(monkeypatch)
     return 'cpu'
 
 

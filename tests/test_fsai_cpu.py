@@ -1,4 +1,4 @@
-"""CPU tier: the approximate-inverse preconditioner over tests/fake_fsai.py (a NumPy stand-in for the six rlh_fsai_*
+"""CPU tier: the approximate-inverse preconditioner over tests/fake_fsai.py (a NumPy stand-in for the rlh_fsai_*
 entry points; CPU tensors stand for device tensors): the host logic of ApproximateInverse, the checks and their
 messages, and the mathematics of the cases in tests/_fsai_cases.py, which the GPU tier runs on the real library."""
 
@@ -22,6 +22,12 @@ def fake():
 def device(monkeypatch):
     fake_fsai.as_device(monkeypatch)
     return 'cpu'
+
+
+def test_stand_in_has_every_entry_point(fake):
+    from raleigh_amd import _lib
+    names = [name for name in _lib.SIGNATURES if name.startswith('rlh_fsai_')]
+    assert names and all(callable(getattr(fake, name, None)) for name in names), names
 
 
 @pytest.mark.parametrize('bits', [32, 64])

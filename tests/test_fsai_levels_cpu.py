@@ -1,11 +1,11 @@
-"""CPU tier: level-of-fill patterns of the approximate inverse over tests/fake_fsai_levels.py (a NumPy stand-in for the
+"""CPU tier: level-of-fill patterns of the approximate inverse over tests/fake_fsai.py (a NumPy stand-in for the
 rlh_fsai_* entry points; CPU tensors stand for device tensors): the host logic of ApproximateInverse(levels=...), the
 checks and their messages, and the mathematics of the cases in tests/_fsai_levels_cases.py, which the GPU tier runs on
 the real library."""
 
 import pytest
 
-import fake_fsai_levels
+import fake_fsai
 import fake_lib
 import _fsai_levels_cases as cases
 
@@ -14,14 +14,14 @@ torch = pytest.importorskip('torch')
 
 @pytest.fixture(autouse=True)
 def fake():
-    f = fake_fsai_levels.install()
+    f = fake_fsai.install()
     yield f
     fake_lib.uninstall()
 
 
 @pytest.fixture
 def device(monkeypatch):
-    fake_fsai_levels.as_device(monkeypatch)
+    fake_fsai.as_device(monkeypatch)
     return 'cpu'
 
 
