@@ -210,10 +210,46 @@ class FakeLib:
         return 0
 
     # ---- updates
+    # (refusals, their order and their messages as in raleigh_amd/csrc/update.hip)
+    _SLOT = 1 << 20                        # bytes of a coefficient staging slot
+
+    @staticmethod
+    def _overlap(code, n, a, ka, lda, b, kb, ldb):
+        es = np.dtype(_DT[code]).itemsize
+        a, b = _addr(a), _addr(b)
+        return a < b + ((kb - 1) * ldb + n) * es and b < a + ((ka - 1) * lda + n) * es
+
+    @staticmethod
+    def _padded(code, m):
+        """(columns of the staged coefficient block, its element size): m rounded up to the kernel's panel."""
+        cplx = code >= 2
+        jt = 8 if m <= 8 else (16 if (m <= 16 or cplx) else (64 if (code == 1 and m > 32) else 32))
+        return (m + jt - 1) // jt * jt, np.dtype(_DT[code]).itemsize
+
+    @staticmethod
+    def _qmat(q, dt, k, m, rs, cs):
+        qf = _flat(q, dt, (k - 1) * rs + (m - 1) * cs + 1)
+        return np.lib.stride_tricks.as_strided(qf, shape=(k, m), strides=(rs * dt.itemsize, cs * dt.itemsize))
+
     def rlh_block_update(self, code, n, k, X, ldx, m, Out, ldo, q, q_rs, q_cs, alpha, beta):
         self._count('block_update')
+        if code not in _DT:
+            return self._fail('rlh_block_update: unknown dtype %d' % code)
+        if n < 0 or k < 0 or m < 0:
+            return self._fail('rlh_block_update: negative size')
+        if beta not in (0, 1):
+            return self._fail('rlh_block_update: beta must be 0 or 1')
         if n == 0 or m == 0:
             return 0
+        if not (_addr(Out) and _addr(alpha)) or (k > 0 and not (_addr(X) and _addr(q))):
+            return self._fail('rlh_block_update: null pointer')
+        if ldo < n or (k > 0 and ldx < n):
+            return self._fail('rlh_block_update: leading dimension smaller than n')
+        if k > 0 and self._overlap(code, n, X, k, ldx, Out, m, ldo):
+            return self._fail('rlh_block_update: output window overlaps the input window')
+        mpad, es = self._padded(code, m)
+        if self._SLOT // (mpad * es) // 4 * 4 < 4:
+            return self._fail('rlh_block_update: %d output vectors exceed the staging slot' % m)
         dt = np.dtype(_DT[code])
         a = _flat(alpha, np.float64, 2)
         al = complex(a[0], a[1]) if dt.kind == 'c' else a[0]
@@ -222,48 +258,63 @@ class FakeLib:
             if not beta:
                 out[:, :] = 0
             return 0
-        span = (k - 1) * q_rs + (m - 1) * q_cs + 1
-        qf = _flat(q, dt, span)
-        qm = np.lib.stride_tricks.as_strided(qf, shape=(k, m),
-                                             strides=(q_rs * dt.itemsize, q_cs * dt.itemsize))
         x = _block(X, code, n, k, ldx)
-        upd = (al * qm).T @ x
-        out[:, :] = (out + upd if beta else upd).astype(dt)
+        upd = (al * self._qmat(q, dt, k, m, q_rs, q_cs)).T @ x
+        out[:, :] = (out + upd if beta else upd + 0).astype(dt)       # (+ 0: no -0.0, as accumulators that start at +0)
         return 0
 
     def rlh_block_update2(self, code, n, k1, X1, ldx1, q1, q1_rs, q1_cs, k2, X2, ldx2, q2, q2_rs, q2_cs, m, Out, ldo,
                           alpha, beta):
         self._count('block_update2')
+        if code not in _DT:
+            return self._fail('rlh_block_update2: unknown dtype %d' % code)
+        if n < 0 or k1 < 1 or k2 < 1 or m < 0:
+            return self._fail('rlh_block_update2: bad size')
+        if beta not in (0, 1):
+            return self._fail('rlh_block_update2: beta must be 0 or 1')
         if n == 0 or m == 0:
             return 0
+        if not all(_addr(p) for p in (Out, alpha, X1, X2, q1, q2)):
+            return self._fail('rlh_block_update2: null pointer')
+        if ldo < n or ldx1 < n or ldx2 < n:
+            return self._fail('rlh_block_update2: leading dimension smaller than n')
+        if self._overlap(code, n, X1, k1, ldx1, Out, m, ldo) or self._overlap(code, n, X2, k2, ldx2, Out, m, ldo):
+            return self._fail('rlh_block_update2: output window overlaps an input window')
+        mpad, es = self._padded(code, m)
+        nbytes = ((k1 + 3) // 4 * 4 + (k2 + 3) // 4 * 4) * mpad * es
+        if nbytes > self._SLOT:
+            return self._fail('rlh_block_update2: coefficient blocks of %d bytes exceed the staging slot' % nbytes)
         dt = np.dtype(_DT[code])
         a = _flat(alpha, np.float64, 2)
         al = complex(a[0], a[1]) if dt.kind == 'c' else a[0]
-
-        def qmat(q, k, rs, cs):
-            qf = _flat(q, dt, (k - 1) * rs + (m - 1) * cs + 1)
-            return np.lib.stride_tricks.as_strided(qf, shape=(k, m), strides=(rs * dt.itemsize, cs * dt.itemsize))
-        upd = (al * qmat(q1, k1, q1_rs, q1_cs)).T @ _block(X1, code, n, k1, ldx1) \
-            + (al * qmat(q2, k2, q2_rs, q2_cs)).T @ _block(X2, code, n, k2, ldx2)
+        upd = (al * self._qmat(q1, dt, k1, m, q1_rs, q1_cs)).T @ _block(X1, code, n, k1, ldx1) \
+            + (al * self._qmat(q2, dt, k2, m, q2_rs, q2_cs)).T @ _block(X2, code, n, k2, ldx2)
         out = _block(Out, code, n, m, ldo)
-        out[:, :] = (out + upd if beta else upd).astype(dt)
+        out[:, :] = (out + upd if beta else upd + 0).astype(dt)
         return 0
 
     def rlh_block_update2x2(self, code, n, k1, X1, ldx1, q1, q1_rs, q1_cs, k2, X2, ldx2, q2, q2_rs, q2_cs, ma, OutA, ldoa,
                             mb, OutB, ldob):
         self._count('block_update2x2')
+        if code not in _DT:
+            return self._fail('rlh_block_update2x2: unknown dtype %d' % code)
+        if n < 0 or k1 < 1 or k2 < 1 or ma < 1 or mb < 1:
+            return self._fail('rlh_block_update2x2: bad size')
         if n == 0:
             return 0
+        if not all(_addr(p) for p in (OutA, OutB, X1, X2, q1, q2)):
+            return self._fail('rlh_block_update2x2: null pointer')
+        if ldoa < n or ldob < n or ldx1 < n or ldx2 < n:
+            return self._fail('rlh_block_update2x2: leading dimension smaller than n')
+        if any(self._overlap(code, n, X, k, ldx, O, mo, ldo) for X, k, ldx in ((X1, k1, ldx1), (X2, k2, ldx2))
+               for O, mo, ldo in ((OutA, ma, ldoa), (OutB, mb, ldob))) or self._overlap(code, n, OutA, ma, ldoa, OutB, mb, ldob):
+            return self._fail('rlh_block_update2x2: an output window overlaps an input window or the other output')
         dt = np.dtype(_DT[code])
         m = ma + mb
-
-        def qmat(q, k, rs, cs):
-            qf = _flat(q, dt, (k - 1) * rs + (m - 1) * cs + 1)
-            return np.lib.stride_tricks.as_strided(qf, shape=(k, m), strides=(rs * dt.itemsize, cs * dt.itemsize))
-        upd = qmat(q1, k1, q1_rs, q1_cs).T @ _block(X1, code, n, k1, ldx1) \
-            + qmat(q2, k2, q2_rs, q2_cs).T @ _block(X2, code, n, k2, ldx2)
-        _block(OutA, code, n, ma, ldoa)[:, :] = upd[:ma].astype(dt)
-        _block(OutB, code, n, mb, ldob)[:, :] = upd[ma:].astype(dt)
+        upd = self._qmat(q1, dt, k1, m, q1_rs, q1_cs).T @ _block(X1, code, n, k1, ldx1) \
+            + self._qmat(q2, dt, k2, m, q2_rs, q2_cs).T @ _block(X2, code, n, k2, ldx2)
+        _block(OutA, code, n, ma, ldoa)[:, :] = (upd[:ma] + 0).astype(dt)
+        _block(OutB, code, n, mb, ldob)[:, :] = (upd[ma:] + 0).astype(dt)
         return 0
 
     def rlh_lincomb_cols(self, code, n, m, a, A, lda, b, B, ldb, Out, ldo):
