@@ -56,6 +56,9 @@ int rlh_finalize(void);
 int rlh_set_stream(void *hip_stream);
 int rlh_sync(void);                          /* cuda_wrap.py synchronize */
 int rlh_mem_info(int64_t *free_bytes, int64_t *total_bytes);
+/* Device memory the library holds for its handles and their builds (not rlh_malloc's buffers, not the context's own):
+ * bytes and allocations alive now.  Valid before rlh_init (0, 0). */
+int rlh_device_live(int64_t *bytes, int64_t *blocks);
 
 /* ---- device memory (cuda_wrap.py malloc/free/memset/memcpy/memcpy2D;
  *      dense_cublas.py:801-811 _Data) ---- */

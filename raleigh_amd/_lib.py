@@ -33,6 +33,7 @@ SIGNATURES = {
     'rlh_set_stream': [_p],
     'rlh_sync': [],
     'rlh_mem_info': [ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
+    'rlh_device_live': [ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
     'rlh_malloc': [ctypes.POINTER(_p), _i64],
     'rlh_free': [_p],
     'rlh_memset': [_p, _int, _i64],

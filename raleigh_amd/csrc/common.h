@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "rlhip.h"
+#include "device_mem.h"
 
 namespace rlh {
 

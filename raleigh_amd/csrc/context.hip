@@ -4,6 +4,10 @@
 // stream, a pinned coefficient ring and a reduction workspace.
 #include <stdarg.h>
 
+#include <atomic>
+#include <mutex>
+#include <unordered_map>
+
 #include "common.h"
 
 namespace rlh {
@@ -53,6 +57,49 @@ int check_async_error() {
     *(volatile unsigned *)c.async_err_h = 0;
     return 1;
   }
+  return 0;
+}
+
+// ---- device memory owned for handles and builds (device_mem.h): the only allocation point, counted
+static std::atomic<int64_t> g_live_bytes{0}, g_live_blocks{0};
+static std::mutex g_live_mutex;                                  // (handles are created on Python worker threads too)
+static std::unordered_map<void *, size_t> g_live_size;           // what device_release takes off the counters
+
+bool device_context_live() { return ctx().ready; }
+
+int device_alloc(void **p, size_t bytes) {
+  *p = nullptr;
+  RLH_HIP(hipMalloc(p, bytes));
+  if (*p) {
+    std::lock_guard<std::mutex> lock(g_live_mutex);
+    g_live_size[*p] = bytes;
+    g_live_bytes += (int64_t)bytes;
+    g_live_blocks += 1;
+  }
+  return 0;
+}
+
+void device_release(void *p) {
+  if (!p || !device_context_live()) return;
+  {
+    std::lock_guard<std::mutex> lock(g_live_mutex);
+    auto it = g_live_size.find(p);
+    if (it != g_live_size.end()) {
+      g_live_bytes -= (int64_t)it->second;
+      g_live_blocks -= 1;
+      g_live_size.erase(it);
+    }
+  }
+  (void)hipFree(p);
+}
+
+int device_copy_in(void *dst, const void *src, size_t bytes) {
+  RLH_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+  return 0;
+}
+
+int device_stream_sync() {
+  RLH_HIP(hipStreamSynchronize(ctx().stream));
   return 0;
 }
 
@@ -206,6 +253,12 @@ int rlh_mem_info(int64_t *free_bytes, int64_t *total_bytes) {
   RLH_HIP(hipMemGetInfo(&f, &t));
   if (free_bytes) *free_bytes = (int64_t)f;
   if (total_bytes) *total_bytes = (int64_t)t;
+  return 0;
+}
+
+int rlh_device_live(int64_t *bytes, int64_t *blocks) {
+  if (bytes) *bytes = g_live_bytes.load();
+  if (blocks) *blocks = g_live_blocks.load();
   return 0;
 }
 

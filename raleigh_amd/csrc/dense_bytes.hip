@@ -27,6 +27,7 @@
 // (128 consecutive bytes each) and every thread transposes a 4 x 4 block of bytes in registers, so that it
 // too is written with 8-byte pieces of four consecutive k (rows 4 q + j of the image: the row permutation
 // spreads them over the bank line).
+#include <memory>
 #include <type_traits>
 
 #include "common.h"
@@ -36,11 +37,9 @@ struct rlh_bytes {
   int64_t rows = 0, cols = 0, lda = 0; // lda: bytes per row on the device, a multiple of 16
   int64_t ncp = 0;                     // cols rounded up to 16: what the kernels read of a row (zero padded when owned;
                                        // a borrowed matrix has ncp == cols, so nothing beyond its columns is read)
-  unsigned char *A = nullptr;
-  int64_t a_bytes = 0;                 // bytes owned by the handle: 0 for a borrowed matrix
-  bool owned = true;
-  char *work = nullptr;                // split-K partial tiles
-  int64_t work_bytes = 0;
+  const unsigned char *A = nullptr;     // what the kernels read: own.get(), or the caller's array (borrowed)
+  rlh::DevBuf<unsigned char> own;      // the handle's padded copy: empty for a borrowed matrix
+  rlh::DevBuf<char> work;              // split-K partial tiles
 };
 
 namespace rlh {
@@ -370,14 +369,7 @@ int launch_bytes(rlh_bytes *h, const BytesArgs &a, bool a_kc) {
   float *part = nullptr;
   if (splits > 1) {
     const int64_t need = splits * (int64_t)a.m * a.ny * (int64_t)sizeof(float);
-    if (need > h->work_bytes) {          // grows once per larger product, then reused without allocation
-      RLH_HIP(hipStreamSynchronize(c.stream));
-      if (h->work) RLH_HIP(hipFree(h->work));
-      h->work = nullptr;
-      h->work_bytes = 0;
-      RLH_HIP(hipMalloc(&h->work, need));
-      h->work_bytes = need;
-    }
+    if (int rc = h->work.reserve((size_t)need)) return rc;      // grows once per larger product, then reused without allocation
     part = (float *)h->work;
   }
   const dim3 grid((unsigned)bx, (unsigned)by, (unsigned)splits);
@@ -413,24 +405,18 @@ extern "C" int rlh_bytes_create(rlh_bytes_t *ph, int kind, int64_t n_rows, int64
   RLH_REQUIRE(n_rows >= 0 && n_cols >= 0, "rlh_bytes_create: negative size");
   RLH_REQUIRE(n_rows == 0 || n_cols == 0 || h_data, "rlh_bytes_create: null data");
   RLH_REQUIRE(row_stride >= n_cols, "rlh_bytes_create: row stride smaller than the number of columns");
-  rlh_bytes *h = new rlh_bytes();
+  std::unique_ptr<rlh_bytes> h(new rlh_bytes());
   h->kind = kind;
   h->rows = n_rows;
   h->cols = n_cols;
   h->lda = (n_cols + 15) / 16 * 16;
   if (h->lda < 16) h->lda = 16;
   h->ncp = h->lda;
-  h->a_bytes = (n_rows > 0 ? n_rows : 1) * h->lda;
-  hipError_t e = hipMalloc(&h->A, h->a_bytes);
-  if (e == hipSuccess && h->lda != n_cols) e = hipMemset(h->A, 0, h->a_bytes);
-  if (e == hipSuccess && n_rows > 0 && n_cols > 0)
-    e = hipMemcpy2D(h->A, h->lda, h_data, row_stride, n_cols, n_rows, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    if (h->A) (void)hipFree(h->A);
-    delete h;
-    return hip_fail(e, "rlh_bytes_create: device copy", __FILE__, __LINE__);
-  }
-  *ph = h;
+  if (int rc = h->own.alloc((size_t)((n_rows > 0 ? n_rows : 1) * h->lda))) return rc;
+  h->A = h->own.get();
+  if (h->lda != n_cols) RLH_HIP(hipMemset(h->own, 0, h->own.bytes()));
+  if (n_rows > 0 && n_cols > 0) RLH_HIP(hipMemcpy2D(h->own, h->lda, h_data, row_stride, n_cols, n_rows, hipMemcpyHostToDevice));
+  *ph = h.release();
   return 0;
 }
 
@@ -443,47 +429,38 @@ extern "C" int rlh_bytes_create_device(rlh_bytes_t *ph, int kind, int64_t n_rows
   RLH_REQUIRE(n_rows >= 0 && n_cols >= 0, "rlh_bytes_create_device: negative size");
   RLH_REQUIRE(n_rows == 0 || n_cols == 0 || d_data, "rlh_bytes_create_device: null data");
   RLH_REQUIRE(row_stride >= n_cols, "rlh_bytes_create_device: row stride smaller than the number of columns");
-  rlh_bytes *h = new rlh_bytes();
+  std::unique_ptr<rlh_bytes> h(new rlh_bytes());
   h->kind = kind;
   h->rows = n_rows;
   h->cols = n_cols;
   if (n_rows > 0 && n_cols > 0 && n_cols % 16 == 0 && row_stride % 16 == 0 && (reinterpret_cast<uintptr_t>(d_data) & 15u) == 0) {
-    h->owned = false;                    // borrowed: every 16-byte piece the kernels read lies within the columns
-    h->A = (unsigned char *)const_cast<void *>(d_data);
+    h->A = (const unsigned char *)d_data;      // borrowed: every 16-byte piece the kernels read lies within the columns
     h->lda = row_stride;
     h->ncp = n_cols;
-    h->a_bytes = 0;
-    *ph = h;
+    *ph = h.release();
     return 0;
   }
   h->lda = (n_cols + 15) / 16 * 16;
   if (h->lda < 16) h->lda = 16;
   h->ncp = h->lda;
-  h->a_bytes = (n_rows > 0 ? n_rows : 1) * h->lda;
   Context &c = ctx();
-  hipError_t e = hipMalloc(&h->A, h->a_bytes);
-  if (e == hipSuccess && n_rows == 0) e = hipMemsetAsync(h->A, 0, h->a_bytes, c.stream);
-  if (e == hipSuccess && n_rows > 0) {
+  if (int rc = h->own.alloc((size_t)((n_rows > 0 ? n_rows : 1) * h->lda))) return rc;
+  h->A = h->own.get();
+  if (n_rows == 0) RLH_HIP(hipMemsetAsync(h->own, 0, h->own.bytes(), c.stream));
+  if (n_rows > 0) {
     int64_t nb = (n_rows * (h->lda / 4) + 255) / 256;
     if (nb > 65536) nb = 65536;
-    hipLaunchKernelGGL(bytes_pad_copy_kernel, dim3((unsigned)nb), dim3(256), 0, c.stream, h->A, h->lda, (const unsigned char *)d_data,
+    hipLaunchKernelGGL(bytes_pad_copy_kernel, dim3((unsigned)nb), dim3(256), 0, c.stream, h->own, h->lda, (const unsigned char *)d_data,
                        row_stride, n_rows, n_cols);
-    e = hipGetLastError();
+    RLH_HIP(hipGetLastError());
   }
-  if (e != hipSuccess) {
-    if (h->A) (void)hipFree(h->A);
-    delete h;
-    return hip_fail(e, "rlh_bytes_create_device: device copy", __FILE__, __LINE__);
-  }
-  *ph = h;
+  *ph = h.release();
   return 0;
 }
 
 extern "C" int rlh_bytes_destroy(rlh_bytes_t h) {
   if (!h) return 0;
   if (ctx().ready) (void)hipStreamSynchronize(ctx().stream);
-  (void)hipFree(h->work);
-  if (h->owned) (void)hipFree(h->A);
   delete h;
   return 0;
 }
@@ -492,8 +469,8 @@ extern "C" int rlh_bytes_info(rlh_bytes_t h, int64_t *n_rows, int64_t *n_cols, i
   RLH_REQUIRE(h, "rlh_bytes_info: null handle");
   if (n_rows) *n_rows = h->rows;
   if (n_cols) *n_cols = h->cols;
-  if (device_bytes) *device_bytes = h->a_bytes + h->work_bytes;
-  if (workspace_bytes) *workspace_bytes = h->work_bytes;
+  if (device_bytes) *device_bytes = (int64_t)(h->own.bytes() + h->work.bytes());
+  if (workspace_bytes) *workspace_bytes = (int64_t)h->work.bytes();
   return 0;
 }
 
@@ -526,16 +503,14 @@ extern "C" int rlh_bytes_row_sumsq(rlh_bytes_t h, double *h_out) {
   if (h->rows == 0) return 0;
   RLH_REQUIRE(h_out, "rlh_bytes_row_sumsq: null output");
   Context &c = ctx();
-  double *d = nullptr;
-  RLH_HIP(hipMalloc(&d, h->rows * sizeof(double)));
+  DevBuf<double> d;
+  if (int rc = d.alloc((size_t)h->rows)) return rc;
   const dim3 grid((unsigned)((h->rows + 3) / 4));
   if (h->kind == RLH_BYTES_I8) hipLaunchKernelGGL(bytes_row_sumsq_kernel<true>, grid, dim3(256), 0, c.stream, h->A, h->rows, h->lda, h->ncp, d);
   else hipLaunchKernelGGL(bytes_row_sumsq_kernel<false>, grid, dim3(256), 0, c.stream, h->A, h->rows, h->lda, h->ncp, d);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-  if (e == hipSuccess) e = hipMemcpy(h_out, d, h->rows * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  RLH_HIP(e);
+  RLH_HIP(hipGetLastError());
+  RLH_HIP(hipStreamSynchronize(c.stream));
+  RLH_HIP(hipMemcpy(h_out, d, h->rows * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -548,16 +523,14 @@ extern "C" int rlh_bytes_absmax(rlh_bytes_t h, double *h_out) {
   const int64_t rowdw = h->ncp / 4, dwords = h->rows * rowdw;
   int64_t nb = (dwords + 255) / 256;
   if (nb > 1024) nb = 1024;
-  int *d = nullptr;
-  RLH_HIP(hipMalloc(&d, nb * sizeof(int)));
+  DevBuf<int> d;
+  if (int rc = d.alloc((size_t)nb)) return rc;
   if (h->kind == RLH_BYTES_I8) hipLaunchKernelGGL(bytes_absmax_kernel<true>, dim3((unsigned)nb), dim3(256), 0, c.stream, h->A, dwords, rowdw, h->lda, d);
   else hipLaunchKernelGGL(bytes_absmax_kernel<false>, dim3((unsigned)nb), dim3(256), 0, c.stream, h->A, dwords, rowdw, h->lda, d);
   std::vector<int> host((size_t)nb);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-  if (e == hipSuccess) e = hipMemcpy(host.data(), d, nb * sizeof(int), hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  RLH_HIP(e);
+  RLH_HIP(hipGetLastError());
+  RLH_HIP(hipStreamSynchronize(c.stream));
+  RLH_HIP(hipMemcpy(host.data(), d, nb * sizeof(int), hipMemcpyDeviceToHost));
   int mx = 0;
   for (int v : host) mx = v > mx ? v : mx;
   *h_out = (double)mx;

@@ -40,8 +40,8 @@
 // What a kernel finds wrong goes to the status record (code and the smallest position), never to a trap.
 //
 // The host side follows the kernels.  An entry point makes an FsaiPlan (what the build is asked to do); create_host and
-// create_device check it and run fsai_build inside make_handle.  fsai_build is the one build path: FsaiScratch owns every
-// device array it allocates, pattern_totals is the scan-fetch-wait-check sequence after the level pattern and again after
+// create_device check it and run fsai_build inside make_handle.  fsai_build is the one build path: its device arrays are
+// DevBufs (FsaiScratch holds those that pattern_totals works on), pattern_totals is the scan-fetch-wait-check sequence after the level pattern and again after
 // enrichment, and for_each_bin with launch_bin launches the enrichment and the set-up kernels bin by bin.
 #include "device_build.h"
 #include "spmm_data.h"
@@ -572,25 +572,14 @@ struct FsaiPlan {
   int grow() const { return steps * step_size; }       // what enrichment can add to a row
 };
 
-// The device arrays and the events of one build: released when the build returns, however it returns.  Named here are
-// the arrays that pattern_totals works on; the others are locals of fsai_build.
+// The device arrays that pattern_totals works on and the events of one build: released when the build returns, however
+// it returns.  The other arrays are locals of fsai_build.
 struct FsaiScratch {
-  FsaiStatus *status = nullptr;
-  int64_t *cnt = nullptr, *ka = nullptr, *kb = nullptr;      // per row: kept entries and the keys of the bin,
-  int64_t *gp = nullptr, *sa = nullptr, *sb = nullptr, *bsum = nullptr;      // their exclusive scans and the scans' tile sums
+  DevBuf<FsaiStatus> status;
+  DevBuf<int64_t> cnt, ka, kb;            // per row: kept entries and the keys of the bin,
+  DevBuf<int64_t> gp, sa, sb, bsum;       // their exclusive scans and the scans' tile sums
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  std::vector<void *> held;
-  template <typename E> hipError_t get(E **p, int64_t count) {      // *p: `count` elements that live as long as the scratch
-    const hipError_t e = hipMalloc((void **)p, (size_t)count * sizeof(E));
-    if (e == hipSuccess) held.push_back(*p);
-    return e;
-  }
-  hipError_t release(void *p) {                                     // ahead of time
-    std::replace(held.begin(), held.end(), p, (void *)nullptr);
-    return hipFree(p);
-  }
   ~FsaiScratch() {
-    for (void *p : held) (void)hipFree(p);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
   }
@@ -605,8 +594,7 @@ struct rlh_fsai {
   int longest = 0, levels = 1, steps = 0, step_size = 0;
   double setup_seconds = 0;
   rlh_spd_t spd = nullptr;          // G and G^H with their partitions
-  char *work = nullptr;             // the n x m block between the two products
-  int64_t work_bytes = 0;
+  rlh::DevBuf<char> work;           // the n x m block between the two products
 };
 
 namespace rlh {
@@ -705,7 +693,7 @@ int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T 
   if (!ix || !va) cap = 0;
   if (room_i >= 0) cap = std::min<int64_t>(cap, room_i / (int64_t)sizeof(I));
   if (room_v >= 0) cap = std::min<int64_t>(cap, room_v / es);
-  RLH_HIP(w.get(&w.status, 1));
+  if (int rc = w.status.alloc(1)) return rc;
   FsaiStatus hs{};
   hs.err = kNoError;
   RLH_HIP(hipMemcpyAsync(w.status, &hs, sizeof hs, hipMemcpyHostToDevice, st));
@@ -719,29 +707,31 @@ int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T 
   // ---- indptr as int64 and columns as int32 (the caller's own arrays where they already are)
   const int64_t *ip64;
   const int32_t *ix32;
-  int32_t *cols = nullptr;
+  DevBuf<int64_t> indptr;
+  DevBuf<int32_t> cols;
   if constexpr (std::is_same<P, int64_t>::value) {
     ip64 = ip;
   } else {
-    int64_t *indptr = nullptr;
-    RLH_HIP(w.get(&indptr, n + 1));
+    if (int rc = indptr.alloc(n + 1)) return rc;
     hipLaunchKernelGGL((spd_convert_index<P, int64_t>), dim3(blocks_for(n + 1, kBlock, 4096)), blk, 0, st, n + 1, ip, indptr);
     ip64 = indptr;
   }
   if constexpr (std::is_same<I, int32_t>::value) {
     ix32 = ix;
   } else {
-    RLH_HIP(w.get(&cols, std::max<int64_t>(nnz, 1)));
+    if (int rc = cols.alloc(std::max<int64_t>(nnz, 1))) return rc;
     if (nnz) hipLaunchKernelGGL((spd_convert_index<I, int32_t>), dim3(blocks_for(nnz, kBlock, 8192)), blk, 0, st, nnz, ix, cols);
     ix32 = cols;
   }
   // ---- the pattern
   const int64_t nb = (n + kScanTile - 1) / kScanTile;
   const int64_t most = (int64_t)ctx().num_cu * kSetupBlocksPerCu;
-  int64_t *start = nullptr;
-  for (int64_t **p : {&w.cnt, &w.ka, &w.kb, &start}) RLH_HIP(w.get(p, n));
-  for (int64_t **p : {&w.gp, &w.sa, &w.sb}) RLH_HIP(w.get(p, n + 1));
-  RLH_HIP(w.get(&w.bsum, nb + 1));
+  DevBuf<int64_t> start;
+  for (DevBuf<int64_t> *p : {&w.cnt, &w.ka, &w.kb, &start})
+    if (int rc = p->alloc(n)) return rc;
+  for (DevBuf<int64_t> *p : {&w.gp, &w.sa, &w.sb})
+    if (int rc = p->alloc(n + 1)) return rc;
+  if (int rc = w.bsum.alloc(nb + 1)) return rc;
   hipLaunchKernelGGL(fsai_count, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, max_row, levels == 1 ? 1 : 0, four, grow, ip64,
                      ix32, w.cnt, w.ka, w.kb, start, w.status);
   hipLaunchKernelGGL(fsai_resolve_error, dim3(1), dim3(1), 0, st, n, ip64, ix32, w.status);
@@ -751,50 +741,51 @@ int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T 
   int64_t gnnz = 0;
   Bins bins{};
   if (int rc = pattern_totals(name, n, w, cap, n, n * (int64_t)max_row, &hs, &gnnz, &bins)) return rc;
-  int32_t *gi = nullptr;
-  RLH_HIP(w.get(&gi, gnnz));
-  RLH_HIP(w.get(&bins.rows, n));
+  DevBuf<int32_t> gi, bin_rows;
+  if (int rc = gi.alloc(gnnz)) return rc;
+  if (int rc = bin_rows.alloc(n)) return rc;
+  bins.rows = bin_rows;
   if (levels == 1)
     hipLaunchKernelGGL(fsai_fill, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, ix32, start, w.gp, gi, bins);
   else
     hipLaunchKernelGGL(fsai_pattern_fill, dim3(blocks_for(n, kBlock / 64, most)), blk, 0, st, n, max_row, levels, ip64, ix32, w.gp,
                        gi, bins);
+  DevBuf<int64_t> capacity, sp;
+  DevBuf<int32_t> slab, level;
   if (steps > 0) {
     // ---- enrichment: so far the bins are those of the capacities and gi holds the level patterns.  The enriched
     // patterns go to a slab at the scanned capacities; counts, keys and scans are then made again for the final rows.
-    int64_t *capacity = nullptr, *sp = nullptr;
-    RLH_HIP(w.get(&capacity, n));
-    RLH_HIP(w.get(&sp, n + 1));
+    if (int rc = capacity.alloc(n)) return rc;
+    if (int rc = sp.alloc(n + 1)) return rc;
     hipLaunchKernelGGL(fsai_capacity, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, max_row, grow, w.cnt, capacity);
     if (int rc = exclusive_scan(n, capacity, w.bsum, sp)) return rc;
     int64_t room = 0;
     RLH_HIP(hipMemcpyAsync(&room, sp + n, 8, hipMemcpyDeviceToHost, st));
     RLH_HIP(hipStreamSynchronize(st));
     RLH_REQUIRE(room >= gnnz && room <= n * (int64_t)max_row, "%s: inconsistent row counts of the pattern", name);
-    int32_t *slab = nullptr;
-    RLH_HIP(w.get(&slab, room));
-    const int32_t *level = gi;                     // the level patterns the rows grow from
+    if (int rc = slab.alloc(room)) return rc;
+    level = std::move(gi);                         // the level patterns the rows grow from
     for_each_bin(bins, n, [&](auto lanes, int64_t count, const int32_t *list) {
       constexpr int kLanes = decltype(lanes)::value;
-      launch_bin<T, kLanes>(fsai_enrich<T, kLanes>, count, list, max_row, steps, step_size, four, ip64, ix32, va, w.gp, level, sp,
-                            slab, w.cnt, w.ka, w.kb, w.status);
+      launch_bin<T, kLanes>(fsai_enrich<T, kLanes>, count, list, max_row, steps, step_size, four, ip64, ix32, va, w.gp.get(), (const int32_t *)level,
+                            sp.get(), slab.get(), w.cnt.get(), w.ka.get(), w.kb.get(), w.status.get());
     });
     RLH_HIP(hipGetLastError());
     const int64_t before = gnnz;                   // (the kernels above are done with w.gp when the scans write it)
     if (int rc = pattern_totals(name, n, w, cap, before, room, &hs, &gnnz, &bins)) return rc;
     hs.truncated = hs.limited;
-    RLH_HIP(w.get(&gi, gnnz));
+    if (int rc = gi.alloc(gnnz)) return rc;
     hipLaunchKernelGGL(fsai_fill, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, slab, sp, w.gp, gi, bins);
   }
   h->nnz = gnnz;
   h->truncated = (int64_t)hs.truncated;
   h->longest = hs.longest;
-  T *gv = nullptr;
-  RLH_HIP(w.get(&gv, gnnz));
+  DevBuf<T> gv;
+  if (int rc = gv.alloc(gnnz)) return rc;
   // ---- the rows, bin by bin
   for_each_bin(bins, n, [&](auto lanes, int64_t count, const int32_t *list) {
     constexpr int kLanes = decltype(lanes)::value;
-    launch_bin<T, kLanes>(fsai_setup<T, kLanes>, count, list, ip64, ix32, va, w.gp, gi, gv, w.status);
+    launch_bin<T, kLanes>(fsai_setup<T, kLanes>, count, list, ip64, ix32, va, w.gp.get(), gi.get(), gv.get(), w.status.get());
   });
   RLH_HIP(hipGetLastError());
   RLH_HIP(hipMemcpyAsync(&hs, w.status, sizeof hs, hipMemcpyDeviceToHost, st));
@@ -802,16 +793,16 @@ int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T 
   if (hs.err != kNoError) return report(name, hs, cap);
   // ---- G and G^H as one sparse data operator (it copies the arrays: 32-bit row pointers where they can hold nnz)
   int rc;
+  DevBuf<int32_t> gp32;
+  DevBuf<int64_t> gi64;
   if (gnnz < INT32_MAX) {
-    int32_t *gp32 = nullptr;
-    RLH_HIP(w.get(&gp32, n + 1));
+    if (int rc2 = gp32.alloc(n + 1)) return rc2;
     hipLaunchKernelGGL((spd_convert_index<int64_t, int32_t>), dim3(blocks_for(n + 1, kBlock, 4096)), blk, 0, st, n + 1, w.gp, gp32);
     RLH_HIP(hipGetLastError());
     rc = rlh_spd_create_device(&h->spd, h->dtype, n, n, 32, gp32, gi, gv);
   } else {
-    RLH_HIP(w.release(cols));         // (the set-up was the last to read the converted columns)
-    int64_t *gi64 = nullptr;
-    RLH_HIP(w.get(&gi64, gnnz));
+    cols.reset();                     // (the set-up was the last to read the converted columns)
+    if (int rc2 = gi64.alloc(gnnz)) return rc2;
     hipLaunchKernelGGL((spd_convert_index<int32_t, int64_t>), dim3(blocks_for(gnnz, kBlock, 8192)), blk, 0, st, gnnz, gi, gi64);
     rc = rlh_spd_create_device(&h->spd, h->dtype, n, n, 64, w.gp, gi64, gv);
   }
@@ -890,22 +881,13 @@ int create_host(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, const in
   const int64_t nnz = indptr[n], es = dtype_size(dtype);
   RLH_REQUIRE(nnz == 0 || (indices && values), "%s: null indices or values", name);
   return make_handle(ph, dtype, n, plan, [&](rlh_fsai *h) {
-    int64_t *d_ip = nullptr;
-    int32_t *d_ix = nullptr;
-    void *d_va = nullptr;
-    int rc = 0;
-    hipError_t e = hipMalloc((void **)&d_ip, (size_t)(n + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_ix, (size_t)std::max<int64_t>(4 * nnz, 4));
-    if (e == hipSuccess) e = hipMalloc(&d_va, (size_t)std::max<int64_t>(es * nnz, 16));
-    if (e == hipSuccess) e = hipMemcpy(d_ip, indptr, (size_t)(n + 1) * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess && nnz) e = hipMemcpy(d_ix, indices, (size_t)nnz * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && nnz) e = hipMemcpy(d_va, values, (size_t)(nnz * es), hipMemcpyHostToDevice);
-    if (e == hipSuccess) rc = fsai_build_any<int64_t, int32_t>(h, name, d_ip, d_ix, d_va, plan);
-    (void)hipFree(d_ip);
-    (void)hipFree(d_ix);
-    (void)hipFree(d_va);
-    RLH_HIP(e);
-    return rc;
+    DevBuf<int64_t> d_ip;
+    DevBuf<int32_t> d_ix;
+    DevBuf<void> d_va;
+    if (int rc = d_ip.upload(indptr, (size_t)(n + 1) * 8)) return rc;
+    if (int rc = d_ix.upload(indices, (size_t)nnz * 4, 4)) return rc;
+    if (int rc = d_va.upload(values, (size_t)(nnz * es), 16)) return rc;
+    return fsai_build_any<int64_t, int32_t>(h, name, d_ip, d_ix, d_va, plan);
   });
 }
 
@@ -962,9 +944,8 @@ extern "C" int rlh_fsai_levels(rlh_fsai_t h, int *levels) {
 
 extern "C" int rlh_fsai_destroy(rlh_fsai_t h) {
   if (!h) return 0;
-  if (h->work) (void)hipStreamSynchronize(ctx().stream);
+  if (ctx().ready) (void)hipStreamSynchronize(ctx().stream);
   if (h->spd) rlh_spd_destroy(h->spd);
-  (void)hipFree(h->work);
   delete h;
   return 0;
 }
@@ -980,7 +961,7 @@ extern "C" int rlh_fsai_info(rlh_fsai_t h, int64_t *n, int64_t *nnz, int64_t *lo
     int64_t held = 0;
     if (h->spd)
       if (int rc = rlh_spd_info(h->spd, nullptr, nullptr, nullptr, &held)) return rc;
-    *device_bytes = held + h->work_bytes;
+    *device_bytes = held + (int64_t)h->work.bytes();
   }
   if (setup_seconds) *setup_seconds = h->setup_seconds;
   return 0;
@@ -1013,14 +994,7 @@ extern "C" int rlh_fsai_apply(rlh_fsai_t h, int64_t m, const void *X, int64_t ld
   RLH_REQUIRE(ldx >= h->n && ldy >= h->n, "rlh_fsai_apply: Matrix and vectors dimensions incompatible");
   const int64_t ldw = (h->n + 15) & ~(int64_t)15;
   const int64_t need = ldw * m * dtype_size(h->dtype);
-  if (need > h->work_bytes) {              // grows once per wider block, then reused without allocation
-    RLH_HIP(hipStreamSynchronize(ctx().stream));
-    if (h->work) RLH_HIP(hipFree(h->work));
-    h->work = nullptr;
-    h->work_bytes = 0;
-    RLH_HIP(hipMalloc((void **)&h->work, (size_t)need));
-    h->work_bytes = need;
-  }
+  if (int rc = h->work.reserve((size_t)need)) return rc;      // grows once per wider block, then reused without allocation
   if (int rc = rlh_spd_apply(h->spd, 0, m, X, ldx, h->work, ldw, nullptr, nullptr)) return rc;
   return rlh_spd_apply(h->spd, 1, m, h->work, ldw, Y, ldy, nullptr, nullptr);
 }

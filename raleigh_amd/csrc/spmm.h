@@ -32,19 +32,11 @@ struct WideMeta {
 struct WideSched {         // launch order built for one (resident workgroups, part, n_own) combination
   int slots, grid, part;
   int64_t n_own;
-  int32_t *sched;          // device
+  rlh::DevBuf<int32_t> sched;
   int64_t len;
 };
 
 namespace rlh {
-
-// n bytes of `src` in a new device allocation of max(bytes, at_least) bytes
-template <typename P>
-static inline int upload(P *&dst, const void *src, size_t bytes, size_t at_least = 0) {
-  RLH_HIP(hipMalloc((void **)&dst, std::max(bytes, at_least)));
-  RLH_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-  return 0;
-}
 
 // Launch order of a windowed layout's blocks.  Workgroup w of the persistent grid processes
 // sched[w], sched[w + grid], ...; workgroups w and w + 8 share an XCD and its L2 under the
@@ -80,12 +72,12 @@ static inline void well_layout(const std::vector<int32_t> &order, int slots, std
 // exchange with the interior rows) -- the units that reference only own columns, and the rest; each keeps the grouped
 // order of the full schedule.
 struct LaunchOrder {
-  int32_t *sched = nullptr;              // device: unit processed at launch position p (-1: none)
+  DevBuf<int32_t> sched;                 // device: unit processed at launch position p (-1: none)
   int64_t len = 0;
   int grid = 0;                          // workgroups the schedule was laid out for
   std::vector<int32_t> order, maxcol;    // host: the grouped order of the units; largest column each references
   int64_t split_at = -1;                 // n_own the part schedules were built for (-1: none)
-  int32_t *part_sched[2] = {nullptr, nullptr};
+  DevBuf<int32_t> part_sched[2];
   int64_t part_len[2] = {0, 0};
   int part_grid[2] = {0, 0};
 
@@ -97,7 +89,12 @@ struct LaunchOrder {
   }
   int split(int64_t n_own) {
     if (split_at == n_own) return 0;
-    release_parts();
+    for (int k = 0; k < 2; ++k) {
+      part_sched[k].reset();
+      part_len[k] = 0;
+      part_grid[k] = 0;
+    }
+    split_at = -1;
     std::vector<int32_t> part[2];
     for (int32_t u : order) part[maxcol[(size_t)u] < n_own ? 0 : 1].push_back(u);
     for (int k = 0; k < 2; ++k)
@@ -112,29 +109,13 @@ struct LaunchOrder {
     *len_ = part == 0 ? len : part_len[part - 1];
     *grid_ = part == 0 ? grid : part_grid[part - 1];
   }
-  void release() {
-    if (sched) (void)hipFree(sched);
-    sched = nullptr;
-    len = 0;
-    grid = 0;
-    release_parts();
-  }
 
  private:
-  static int place(const std::vector<int32_t> &units, int32_t *&d_sched, int64_t &d_len, int &d_grid) {
+  static int place(const std::vector<int32_t> &units, DevBuf<int32_t> &d_sched, int64_t &d_len, int &d_grid) {
     std::vector<int32_t> host;
     well_layout(units, ctx().num_cu, host, d_grid);
     d_len = (int64_t)host.size();
-    return upload(d_sched, host.data(), host.size() * sizeof(int32_t));
-  }
-  void release_parts() {
-    for (int k = 0; k < 2; ++k) {
-      if (part_sched[k]) (void)hipFree(part_sched[k]);
-      part_sched[k] = nullptr;
-      part_len[k] = 0;
-      part_grid[k] = 0;
-    }
-    split_at = -1;
+    return d_sched.upload(host.data(), host.size() * sizeof(int32_t));
   }
 };
 
@@ -145,17 +126,17 @@ struct rlh_csr {
   int64_t n_rows = 0, n_cols = 0, nnz = 0;
   int64_t n_slices = 0;
   int64_t padded = 0;                // stored entries incl. padding
-  int64_t *slice_ptr = nullptr;      // device, n_slices + 1 (entry offsets)
-  int32_t *cols = nullptr;           // device, padded
-  void *vals = nullptr;              // device, padded
+  rlh::DevBuf<int64_t> slice_ptr;    // device, n_slices + 1 (entry offsets)
+  rlh::DevBuf<int32_t> cols;         // device, padded
+  rlh::DevBuf<void> vals;            // device, padded
   int64_t device_bytes = 0;
   // 1024-row windowed layout (rows of at most 8 entries, real types)
   int64_t well_blocks = 0;           // 0: not built
   int well_wmax = 0;                 // register slots per row the kernel is instantiated for
-  WellMeta *well_meta = nullptr;     // device, well_blocks
-  int32_t *well_gsrc = nullptr;      // device: first column of every 64-entry staging group
-  uint16_t *well_idx = nullptr;      // device: position of the entry's column in the staged image
-  void *well_vals = nullptr;         // device
+  rlh::DevBuf<WellMeta> well_meta;   // device, well_blocks
+  rlh::DevBuf<int32_t> well_gsrc;    // device: first column of every 64-entry staging group
+  rlh::DevBuf<uint16_t> well_idx;    // device: position of the entry's column in the staged image
+  rlh::DevBuf<void> well_vals;       // device
   double well_ratio = 0.0;           // staged elements per stored entry slot (diagnostic)
   rlh::LaunchOrder well_launch;      // of the blocks
   int well_inbounds = 0;             // every staging group lies inside [0, n_cols)
@@ -163,18 +144,18 @@ struct rlh_csr {
   // the same layout over STACKS of row blocks (spmm.hip, "Stacked blocks"): a workgroup takes kStkR 1024-row blocks whose
   // windows overlap (for a 3-D stencil two blocks one grid plane apart) and stages the union of their windows once
   int64_t stk_blocks = 0;            // stacks; 0: not built
-  WellMeta *stk_meta = nullptr;      // device, per stack (eoff counts slots: member r's 8 slots start at eoff + 8 r)
-  int32_t *stk_member = nullptr;     // device, kStkR pairs per stack: (first row, rows) of the stack's row blocks ((0, 0): none)
-  int32_t *stk_gsrc = nullptr;       // device
-  uint16_t *stk_idx = nullptr;       // device
-  void *stk_vals = nullptr;          // device
+  rlh::DevBuf<WellMeta> stk_meta;    // device, per stack (eoff counts slots: member r's 8 slots start at eoff + 8 r)
+  rlh::DevBuf<int32_t> stk_member;   // device, kStkR pairs per stack: (first row, rows) of the stack's row blocks ((0, 0): none)
+  rlh::DevBuf<int32_t> stk_gsrc;     // device
+  rlh::DevBuf<uint16_t> stk_idx;     // device
+  rlh::DevBuf<void> stk_vals;        // device
   // value dictionary of the stacks (constant-coefficient stencils repeat a few dozen rows of values: 27 for the 7-point
   // Laplacian): per row the index of its 8-slot value tuple, and the table of distinct tuples -- 4 bytes per row
   // instead of 8 values; nullptr when the rows have more than kStkMaxPatterns distinct tuples
-  int32_t *stk_pat = nullptr;        // device, [stack][member][row of the block]: value pattern | position pattern << 16
-  uint16_t *stk_dtab = nullptr;      // device, [stack][member][kStkMaxDeltas][8]: positions minus the row's index in its block, per
+  rlh::DevBuf<int32_t> stk_pat;      // device, [stack][member][row of the block]: value pattern | position pattern << 16
+  rlh::DevBuf<uint16_t> stk_dtab;    // device, [stack][member][kStkMaxDeltas][8]: positions minus the row's index in its block, per
                                      // position pattern of that member (a stencil's interior rows all share one); nullptr: none
-  void *stk_table = nullptr;         // device, [pattern][8 values]
+  rlh::DevBuf<void> stk_table;       // device, [pattern][8 values]
   int64_t stk_npat = 0;
   rlh::LaunchOrder stk_launch;       // of the stacks
   int stk_gmax = 0;                  // largest number of staging groups of a stack
@@ -185,10 +166,10 @@ struct rlh_csr {
   double well_staged = 0.0;
   // 256-row interleaved layout (any row length, any type)
   int64_t wide_blocks = 0;           // 0: not built
-  WideMeta *wide_meta = nullptr;     // device
-  int32_t *wide_gsrc = nullptr;      // device
-  void *wide_idx = nullptr;          // device: 16-byte pieces of 8 positions, [chunk][row]
-  void *wide_vals = nullptr;         // device: 16-byte pieces of values, [chunk][piece][row]
+  rlh::DevBuf<WideMeta> wide_meta;   // device
+  rlh::DevBuf<int32_t> wide_gsrc;    // device
+  rlh::DevBuf<void> wide_idx;        // device: 16-byte pieces of 8 positions, [chunk][row]
+  rlh::DevBuf<void> wide_vals;       // device: 16-byte pieces of values, [chunk][piece][row]
   int wide_gmax = 0;                 // largest number of staging groups of a block
   int wide_k = 1;                    // rows per thread of the interleaved layout: 2 where consecutive rows share their column pattern (FE nodes)
   std::vector<int32_t> wide_order, wide_maxcol;
@@ -545,7 +526,6 @@ int wide_stride(int nv, int es);
 int wide_min_nv(int dtype);
 int wide_sched(rlh_csr *h, int slots, int part, int64_t n_own, const int32_t **sched, int64_t *len, int *grid);
 int wide_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices, const void *values, bool force);
-void wide_destroy(rlh_csr *h);
 // Y = A X (cheb == nullptr) or the fused Chebyshev step on part 0 / 1 / 2 of the rows
 int wide_spmm_s(rlh_csr *h, int part, int64_t m, const void *X, int64_t ldx, int64_t n_own, const void *H, int64_t ldh,
                 void *Y, int64_t ldy, const void *B, int64_t ldb, double cy, double cp, double cb);

@@ -1556,10 +1556,10 @@ static int csr_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices, 
   }
   h->n_slices = ns;
   h->padded = padded;
-  if (int rc = upload(h->slice_ptr, sp.data(), (size_t)(ns + 1) * sizeof(int64_t))) return rc;
+  if (int rc = h->slice_ptr.upload(sp.data(), (size_t)(ns + 1) * sizeof(int64_t))) return rc;
   if (padded > 0) {
-    if (int rc = upload(h->cols, cols.data(), (size_t)padded * sizeof(int32_t))) return rc;
-    if (int rc = upload(h->vals, vals.data(), (size_t)padded * sizeof(T))) return rc;
+    if (int rc = h->cols.upload(cols.data(), (size_t)padded * sizeof(int32_t))) return rc;
+    if (int rc = h->vals.upload(vals.data(), (size_t)padded * sizeof(T))) return rc;
   }
   h->device_bytes = (ns + 1) * 8 + padded * (4 + (int64_t)sizeof(T));
   return 0;
@@ -1671,11 +1671,11 @@ static int well_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices,
   for (int64_t b = 0; b < nblocks; ++b) maxcol[(size_t)b] = wins[b].back().start + wins[b].back().len - 1;
   clk.lap("well: schedule");
   if (int rc = h->well_launch.set(std::move(order), std::move(maxcol))) return rc;
-  if (int rc = upload(h->well_meta, meta.data(), (size_t)nblocks * sizeof(WellMeta))) return rc;
-  if (int rc = upload(h->well_gsrc, gsrc.data(), (size_t)goff * sizeof(int32_t), sizeof(int32_t))) return rc;
+  if (int rc = h->well_meta.upload(meta.data(), (size_t)nblocks * sizeof(WellMeta))) return rc;
+  if (int rc = h->well_gsrc.upload(gsrc.data(), (size_t)goff * sizeof(int32_t), sizeof(int32_t))) return rc;
   const size_t ne = (size_t)(eoff + epad) * kWellRows;
-  if (int rc = upload(h->well_idx, idx.data(), ne * sizeof(uint16_t), sizeof(uint16_t))) return rc;
-  if (int rc = upload(h->well_vals, vals.data(), ne * sizeof(T), sizeof(T))) return rc;
+  if (int rc = h->well_idx.upload(idx.data(), ne * sizeof(uint16_t), sizeof(uint16_t))) return rc;
+  if (int rc = h->well_vals.upload(vals.data(), ne * sizeof(T), sizeof(T))) return rc;
   h->padded = eoff * kWellRows;
   h->device_bytes = nblocks * (int64_t)sizeof(WellMeta) + h->well_launch.len * 4 + goff * 4 + (int64_t)ne * (2 + (int64_t)sizeof(T));
   h->well_blocks = nblocks;
@@ -1963,7 +1963,7 @@ static int stack_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices
   well_schedule(swins, nst, n, kWellRows, ctx().num_cu, order, &granule_owner);
   clk.lap("stack: schedule");
   if (int rc = h->stk_launch.set(std::move(order), std::move(maxcol))) return rc;
-  if (int rc = upload(h->stk_meta, meta.data(), (size_t)nst * sizeof(WellMeta))) return rc;
+  if (int rc = h->stk_meta.upload(meta.data(), (size_t)nst * sizeof(WellMeta))) return rc;
   {
     std::vector<int32_t> ranges(members.size() * 2, 0);                   // (first row, rows) of every member; (0, 0): none
     for (size_t k = 0; k < members.size(); ++k)
@@ -1971,9 +1971,9 @@ static int stack_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices
         ranges[2 * k] = (int32_t)brow[(size_t)members[k]];
         ranges[2 * k + 1] = (int32_t)(brow[(size_t)members[k] + 1] - brow[(size_t)members[k]]);
       }
-    if (int rc = upload(h->stk_member, ranges.data(), ranges.size() * sizeof(int32_t))) return rc;
+    if (int rc = h->stk_member.upload(ranges.data(), ranges.size() * sizeof(int32_t))) return rc;
   }
-  if (int rc = upload(h->stk_gsrc, gsrc.data(), (size_t)goff * sizeof(int32_t), sizeof(int32_t))) return rc;
+  if (int rc = h->stk_gsrc.upload(gsrc.data(), (size_t)goff * sizeof(int32_t), sizeof(int32_t))) return rc;
   // value dictionary: the distinct 8-slot value tuples of the rows (byte-wise), given up beyond kStkMaxPatterns
   {
     std::vector<int32_t> pat((size_t)nst * R * kWellRows, 0);
@@ -2044,17 +2044,17 @@ static int stack_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices
     h->stk_npat = 0;
     if (ok && !table.empty()) {
       if (dok) {
-        if (int rc = upload(h->stk_dtab, dtab.data(), dtab.size() * sizeof(uint16_t))) return rc;
+        if (int rc = h->stk_dtab.upload(dtab.data(), dtab.size() * sizeof(uint16_t))) return rc;
         h->device_bytes += (int64_t)dtab.size() * 2;
       }
       h->stk_npat = (int64_t)table.size() / 8;
-      if (int rc = upload(h->stk_pat, pat.data(), pat.size() * sizeof(int32_t))) return rc;
-      if (int rc = upload(h->stk_table, table.data(), table.size() * sizeof(T))) return rc;
+      if (int rc = h->stk_pat.upload(pat.data(), pat.size() * sizeof(int32_t))) return rc;
+      if (int rc = h->stk_table.upload(table.data(), table.size() * sizeof(T))) return rc;
       h->device_bytes += (int64_t)pat.size() * 4 + (int64_t)table.size() * (int64_t)sizeof(T);
     }
   }
-  if (int rc = upload(h->stk_idx, idx.data(), ne * sizeof(uint16_t))) return rc;
-  if (int rc = upload(h->stk_vals, vals.data(), ne * sizeof(T))) return rc;
+  if (int rc = h->stk_idx.upload(idx.data(), ne * sizeof(uint16_t))) return rc;
+  if (int rc = h->stk_vals.upload(vals.data(), ne * sizeof(T))) return rc;
   h->device_bytes += nst * (int64_t)sizeof(WellMeta) + h->stk_launch.len * 4 + goff * 4 + (int64_t)members.size() * 8 +
                      (int64_t)ne * (2 + (int64_t)sizeof(T));
   h->stk_blocks = nst;
@@ -2249,27 +2249,7 @@ int rlh_csr_create_upper(rlh_csr_t *out, int dtype, int64_t n, const int64_t *in
 
 int rlh_csr_destroy(rlh_csr_t h) {
   if (!h) return 0;
-  if (ctx().ready) {
-    (void)hipStreamSynchronize(ctx().stream);
-    if (h->slice_ptr) (void)hipFree(h->slice_ptr);
-    if (h->cols) (void)hipFree(h->cols);
-    if (h->vals) (void)hipFree(h->vals);
-    if (h->well_meta) (void)hipFree(h->well_meta);
-    if (h->well_gsrc) (void)hipFree(h->well_gsrc);
-    if (h->well_idx) (void)hipFree(h->well_idx);
-    if (h->well_vals) (void)hipFree(h->well_vals);
-    if (h->stk_meta) (void)hipFree(h->stk_meta);
-    if (h->stk_member) (void)hipFree(h->stk_member);
-    if (h->stk_gsrc) (void)hipFree(h->stk_gsrc);
-    if (h->stk_idx) (void)hipFree(h->stk_idx);
-    if (h->stk_vals) (void)hipFree(h->stk_vals);
-    if (h->stk_pat) (void)hipFree(h->stk_pat);
-    if (h->stk_table) (void)hipFree(h->stk_table);
-    if (h->stk_dtab) (void)hipFree(h->stk_dtab);
-    h->well_launch.release();
-    h->stk_launch.release();
-    wide_destroy(h);
-  }
+  if (ctx().ready) (void)hipStreamSynchronize(ctx().stream);
   delete h;
   return 0;
 }

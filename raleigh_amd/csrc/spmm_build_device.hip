@@ -286,14 +286,10 @@ __global__ __launch_bounds__(kWideRows) void wide_fill(int64_t n, bool mirror, c
 }
 
 struct CsrScratch {                 // released when the build returns, however it returns
-  CsrStatus *status = nullptr;
-  int64_t *indptr = nullptr, *widths = nullptr, *bsum = nullptr;
-  int32_t *cols = nullptr, *groups = nullptr;
-  BlockRec *rec = nullptr;
-  ~CsrScratch() {
-    (void)hipFree(status); (void)hipFree(indptr); (void)hipFree(widths); (void)hipFree(bsum);
-    (void)hipFree(cols); (void)hipFree(groups); (void)hipFree(rec);
-  }
+  DevBuf<CsrStatus> status;
+  DevBuf<int64_t> indptr, widths, bsum;
+  DevBuf<int32_t> cols, groups;
+  DevBuf<BlockRec> rec;
 };
 
 struct Lap {                        // RLH_SPMM_VERBOSE=1: the kernels of a phase have run before its time is taken
@@ -312,11 +308,11 @@ int sell_build_device(rlh_csr *h, CsrScratch &w, bool mirror, const int64_t *ip,
   hipStream_t st = ctx().stream;
   const int64_t n = h->n_rows, ns = (n + 63) / 64;
   const int64_t nb = (ns + kScanTile - 1) / kScanTile;
-  RLH_HIP(hipMalloc((void **)&h->slice_ptr, (size_t)(ns + 1) * sizeof(int64_t)));
+  if (int rc = h->slice_ptr.alloc((size_t)(ns + 1))) return rc;
   int64_t padded = 0;
   if (ns > 0) {
-    RLH_HIP(hipMalloc((void **)&w.widths, (size_t)ns * sizeof(int64_t)));
-    RLH_HIP(hipMalloc((void **)&w.bsum, (size_t)(nb + 1) * sizeof(int64_t)));
+    if (int rc = w.widths.alloc((size_t)ns)) return rc;
+    if (int rc = w.bsum.alloc((size_t)(nb + 1))) return rc;
     hipLaunchKernelGGL(sell_widths, dim3(blocks_for(ns, kBlock, INT32_MAX)), dim3(kBlock), 0, st, n, ns, ip, w.widths);
     hipLaunchKernelGGL(scan_tile_sums, dim3((unsigned)nb), dim3(kBlock), 0, st, ns, w.widths, w.bsum);
     hipLaunchKernelGGL(scan_of_sums, dim3(1), dim3(kBlock), 0, st, nb, w.bsum);
@@ -330,8 +326,8 @@ int sell_build_device(rlh_csr *h, CsrScratch &w, bool mirror, const int64_t *ip,
   h->n_slices = ns;
   h->padded = padded;
   if (padded > 0) {
-    RLH_HIP(hipMalloc((void **)&h->cols, (size_t)padded * sizeof(int32_t)));
-    RLH_HIP(hipMalloc((void **)&h->vals, (size_t)padded * sizeof(T)));
+    if (int rc = h->cols.alloc((size_t)padded)) return rc;
+    if (int rc = h->vals.alloc((size_t)padded * sizeof(T))) return rc;
     hipLaunchKernelGGL(sell_fill<T>, dim3((unsigned)ns), dim3(64), 0, st, n, mirror, ip, ix, va, h->slice_ptr, h->cols, (T *)h->vals);
     RLH_HIP(hipGetLastError());
   }
@@ -350,8 +346,8 @@ int wide_build_device(rlh_csr *h, CsrScratch &w, Lap &lap, bool mirror, bool for
   const int64_t nblocks = (n + kWideRows - 1) / kWideRows;
   h->wide_blocks = 0;
   if (nblocks == 0 || h->nnz == 0) return 0;
-  RLH_HIP(hipMalloc((void **)&w.rec, (size_t)nblocks * sizeof(BlockRec)));
-  RLH_HIP(hipMalloc((void **)&w.groups, (size_t)nblocks * kGroupCap * sizeof(int32_t)));
+  if (int rc = w.rec.alloc((size_t)nblocks)) return rc;
+  if (int rc = w.groups.alloc((size_t)nblocks * kGroupCap)) return rc;
   hipLaunchKernelGGL(wide_collect, dim3((unsigned)nblocks), dim3(kWideRows), 0, st, n, ip, ix, w.rec, w.groups);
   RLH_HIP(hipGetLastError());
   std::vector<BlockRec> rec((size_t)nblocks);
@@ -384,10 +380,10 @@ int wide_build_device(rlh_csr *h, CsrScratch &w, Lap &lap, bool mirror, bool for
   RLH_REQUIRE(goff < ((int64_t)1 << 31), "rlh_csr_create_device: too many staging groups");
   const int64_t nchunks = eoff + kWidePadChunks;  // padding: the kernel's prefetch runs ahead of the last block's chunks
   const size_t idx_bytes = (size_t)nchunks * TPS * 16, val_bytes = (size_t)nchunks * VP * kWideRows * 16;
-  RLH_HIP(hipMalloc((void **)&h->wide_meta, (size_t)nblocks * sizeof(WideMeta)));
-  RLH_HIP(hipMalloc((void **)&h->wide_gsrc, (size_t)goff * sizeof(int32_t)));
-  RLH_HIP(hipMalloc((void **)&h->wide_idx, idx_bytes));
-  RLH_HIP(hipMalloc((void **)&h->wide_vals, val_bytes));
+  if (int rc = h->wide_meta.alloc((size_t)nblocks)) return rc;
+  if (int rc = h->wide_gsrc.alloc((size_t)goff)) return rc;
+  if (int rc = h->wide_idx.alloc(idx_bytes)) return rc;
+  if (int rc = h->wide_vals.alloc(val_bytes)) return rc;
   RLH_HIP(hipMemcpyAsync(h->wide_meta, meta.data(), (size_t)nblocks * sizeof(WideMeta), hipMemcpyHostToDevice, st));
   // (the fill writes every slot of every block: what is zeroed here is the padding behind the last block)
   RLH_HIP(hipMemsetAsync((char *)h->wide_idx + (size_t)eoff * TPS * 16, 0, idx_bytes - (size_t)eoff * TPS * 16, st));
@@ -450,7 +446,7 @@ int csr_create_device_impl(rlh_csr *h, const I *ip, const I *ix, const T *va, bo
   if (room_v >= 0) cap = std::min<int64_t>(cap, room_v / es);
   const bool real = std::is_same<T, float>::value || std::is_same<T, double>::value;
   const bool pair_test = real && env_int("RLH_WIDE_PAIR", 1) != 0 && !want_sell;
-  RLH_HIP(hipMalloc((void **)&w.status, sizeof(CsrStatus)));
+  if (int rc = w.status.alloc(1)) return rc;
   CsrStatus hs{{kNoError, 0}, 0, 0, 0};
   RLH_HIP(hipMemcpyAsync(w.status, &hs, sizeof hs, hipMemcpyHostToDevice, st));
   const unsigned row_waves = blocks_for(M, kBlock / 64, 8192);
@@ -491,11 +487,11 @@ int csr_create_device_impl(rlh_csr *h, const I *ip, const I *ix, const T *va, bo
   const int32_t *ix32;
   if constexpr (std::is_same<I, int64_t>::value) {
     ip64 = ip;
-    RLH_HIP(hipMalloc((void **)&w.cols, (size_t)std::max<int64_t>(4 * h->nnz, 4)));
+    if (int rc = w.cols.alloc((size_t)std::max<int64_t>(h->nnz, 1))) return rc;
     if (h->nnz) hipLaunchKernelGGL((spd_convert_index<I, int32_t>), dim3(blocks_for(h->nnz, kBlock, 8192)), blk, 0, st, h->nnz, ix, w.cols);
     ix32 = w.cols;
   } else {
-    RLH_HIP(hipMalloc((void **)&w.indptr, (size_t)(M + 1) * sizeof(int64_t)));
+    if (int rc = w.indptr.alloc((size_t)(M + 1))) return rc;
     hipLaunchKernelGGL((spd_convert_index<I, int64_t>), dim3(blocks_for(M + 1, kBlock, 4096)), blk, 0, st, M + 1, ip, w.indptr);
     ip64 = w.indptr;
     ix32 = ix;
@@ -506,7 +502,6 @@ int csr_create_device_impl(rlh_csr *h, const I *ip, const I *ix, const T *va, bo
     if (int rc = wide_build_device<T>(h, w, lap, mirror, force_wide, paired, ip64, ix32, va)) return rc;
   }
   if (h->wide_blocks == 0) {
-    wide_destroy(h);                         // (arrays of a layout that was given up)
     h->wide_k = 1;
     if (int rc = sell_build_device<T>(h, w, mirror, ip64, ix32, va)) return rc;
     if (int rc = lap("sliced ELL")) return rc;

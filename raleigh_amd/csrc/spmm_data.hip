@@ -195,10 +195,10 @@ __global__ __launch_bounds__(kBlock) void spd_fixup(int64_t M, int64_t total, in
 // One orientation of the operator on the device: CSR arrays and the merge-path partition.
 struct Side {
   int64_t rows = 0, cols = 0, nnz = 0, G = 0;
-  int64_t *indptr = nullptr;
-  int32_t *idx = nullptr;
-  void *val = nullptr;
-  int32_t *row_at = nullptr;      // G + 1 start rows
+  DevBuf<int64_t> indptr;
+  DevBuf<int32_t> idx;
+  DevBuf<void> val;
+  DevBuf<int32_t> row_at;         // G + 1 start rows
 };
 
 }  // namespace
@@ -209,8 +209,7 @@ struct rlh_spd {
   rlh::Side side[2];              // 0: A, 1: A^H
   double transpose_seconds = 0;
   // workspace, grown on demand: Xi, Yi, partials
-  char *work = nullptr;
-  int64_t work_bytes = 0;
+  rlh::DevBuf<char> work;
 };
 
 namespace rlh {
@@ -292,25 +291,10 @@ int upload_side(Side &s, int64_t rows, int64_t cols, const int64_t *ip, const in
   s.G = (rows + s.nnz + kItems - 1) / kItems;
   std::vector<int32_t> row_at;
   partition(ip, rows, s.nnz, s.G, row_at);
-  RLH_HIP(hipMalloc(&s.indptr, 8 * (rows + 1)));
-  RLH_HIP(hipMalloc(&s.idx, std::max<int64_t>(4 * s.nnz, 4)));
-  RLH_HIP(hipMalloc(&s.val, std::max<int64_t>(es * s.nnz, 16)));
-  RLH_HIP(hipMalloc(&s.row_at, 4 * (s.G + 1)));
-  RLH_HIP(hipMemcpy(s.indptr, ip, 8 * (rows + 1), hipMemcpyHostToDevice));
-  if (s.nnz) {
-    RLH_HIP(hipMemcpy(s.idx, ix, 4 * s.nnz, hipMemcpyHostToDevice));
-    RLH_HIP(hipMemcpy(s.val, va, es * s.nnz, hipMemcpyHostToDevice));
-  }
-  RLH_HIP(hipMemcpy(s.row_at, row_at.data(), 4 * (s.G + 1), hipMemcpyHostToDevice));
-  return 0;
-}
-
-void free_side(Side &s) {
-  (void)hipFree(s.indptr);
-  (void)hipFree(s.idx);
-  (void)hipFree(s.val);
-  (void)hipFree(s.row_at);
-  s = Side();
+  if (int rc = s.indptr.upload(ip, 8 * (rows + 1))) return rc;
+  if (int rc = s.idx.upload(ix, 4 * s.nnz, 4)) return rc;
+  if (int rc = s.val.upload(va, es * s.nnz, 16)) return rc;
+  return s.row_at.upload(row_at.data(), 4 * (s.G + 1));
 }
 
 template <typename T>
@@ -441,19 +425,15 @@ int alloc_side(Side &s, int64_t rows, int64_t cols, int64_t nnz, int64_t es) {
   s.cols = cols;
   s.nnz = nnz;
   s.G = (rows + nnz + kItems - 1) / kItems;
-  RLH_HIP(hipMalloc(&s.indptr, 8 * (rows + 1)));
-  RLH_HIP(hipMalloc(&s.idx, std::max<int64_t>(4 * nnz, 4)));
-  RLH_HIP(hipMalloc(&s.val, std::max<int64_t>(es * nnz, 16)));
-  RLH_HIP(hipMalloc(&s.row_at, 4 * (s.G + 1)));
-  return 0;
+  if (int rc = s.indptr.alloc(rows + 1)) return rc;
+  if (int rc = s.idx.alloc(std::max<int64_t>(nnz, 1))) return rc;
+  if (int rc = s.val.alloc(std::max<int64_t>(es * nnz, 16))) return rc;
+  return s.row_at.alloc(s.G + 1);
 }
 
-struct BuildScratch {               // released when the build returns, however it returns
-  BuildStatus *status = nullptr;
-  int64_t *rstart = nullptr, *cnt = nullptr, *tot = nullptr, *bsum = nullptr;
+struct BuildScratch {               // the timing events: destroyed when the build returns, however it returns
   hipEvent_t e0 = nullptr, e1 = nullptr;
   ~BuildScratch() {
-    (void)hipFree(status); (void)hipFree(rstart); (void)hipFree(cnt); (void)hipFree(tot); (void)hipFree(bsum);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
   }
@@ -476,6 +456,8 @@ int create_device_impl(rlh_spd *h, int64_t M, int64_t N, const I *ip, const I *i
   hipStream_t st = ctx().stream;
   const dim3 blk(kBlock);
   BuildScratch w;
+  DevBuf<BuildStatus> status;
+  DevBuf<int64_t> rstart, cnt, tot, bsum;
   // ---- the checks: one status record comes back
   int64_t cap = INT64_MAX;
   const int64_t room_p = bytes_from(ip), room_i = bytes_from(ix), room_v = bytes_from(va);
@@ -483,13 +465,13 @@ int create_device_impl(rlh_spd *h, int64_t M, int64_t N, const I *ip, const I *i
   if (!ix || !va) cap = 0;
   if (room_i >= 0) cap = std::min<int64_t>(cap, room_i / (int64_t)sizeof(I));
   if (room_v >= 0) cap = std::min<int64_t>(cap, room_v / es);
-  RLH_HIP(hipMalloc(&w.status, sizeof(BuildStatus)));
+  if (int rc = status.alloc(1)) return rc;
   BuildStatus hs{kNoError, 0};
-  RLH_HIP(hipMemcpyAsync(w.status, &hs, sizeof hs, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(spd_check_indptr<I>, dim3(blocks_for(M + 1, kBlock, 4096)), blk, 0, st, M, ip, cap, w.status);
-  hipLaunchKernelGGL(spd_check_columns<I>, dim3(blocks_for(M, kBlock / 64, 8192)), blk, 0, st, M, N, ip, ix, w.status);
+  RLH_HIP(hipMemcpyAsync(status, &hs, sizeof hs, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(spd_check_indptr<I>, dim3(blocks_for(M + 1, kBlock, 4096)), blk, 0, st, M, ip, cap, status);
+  hipLaunchKernelGGL(spd_check_columns<I>, dim3(blocks_for(M, kBlock / 64, 8192)), blk, 0, st, M, N, ip, ix, status);
   RLH_HIP(hipGetLastError());
-  RLH_HIP(hipMemcpyAsync(&hs, w.status, sizeof hs, hipMemcpyDeviceToHost, st));
+  RLH_HIP(hipMemcpyAsync(&hs, status, sizeof hs, hipMemcpyDeviceToHost, st));
   RLH_HIP(hipStreamSynchronize(st));
   if (hs.err != kNoError) {
     const int code = (int)(hs.err >> 56);
@@ -522,26 +504,26 @@ int create_device_impl(rlh_spd *h, int64_t M, int64_t N, const I *ip, const I *i
   if (int rc = alloc_side(b, N, M, nnz, es)) return rc;
   const int64_t C = chunk_count(nnz, N);
   const int64_t nb = (N + kScanTile - 1) / kScanTile;
-  RLH_HIP(hipMalloc(&w.rstart, 8 * (C + 1)));
-  RLH_HIP(hipMalloc(&w.cnt, std::max<int64_t>(8 * C * N, 8)));
-  RLH_HIP(hipMalloc(&w.tot, std::max<int64_t>(8 * N, 8)));
-  RLH_HIP(hipMalloc(&w.bsum, 8 * (nb + 1)));
+  if (int rc = rstart.alloc(C + 1)) return rc;
+  if (int rc = cnt.alloc(std::max<int64_t>(C * N, 1))) return rc;
+  if (int rc = tot.alloc(std::max<int64_t>(N, 1))) return rc;
+  if (int rc = bsum.alloc(nb + 1)) return rc;
   RLH_HIP(hipEventCreate(&w.e0));
   RLH_HIP(hipEventCreate(&w.e1));
   RLH_HIP(hipEventRecord(w.e0, st));
-  RLH_HIP(hipMemsetAsync(w.cnt, 0, std::max<int64_t>(8 * C * N, 8), st));
-  hipLaunchKernelGGL(spd_chunk_rows, dim3(blocks_for(C + 1, kBlock, INT32_MAX)), blk, 0, st, M, nnz, C, a.indptr, w.rstart);
+  RLH_HIP(hipMemsetAsync(cnt, 0, std::max<int64_t>(8 * C * N, 8), st));
+  hipLaunchKernelGGL(spd_chunk_rows, dim3(blocks_for(C + 1, kBlock, INT32_MAX)), blk, 0, st, M, nnz, C, a.indptr, rstart);
   const int S = (int)std::max<int64_t>(1, std::min<int64_t>(64, 2048 / C));
   if (nnz && N)
-    hipLaunchKernelGGL(spd_count, dim3((unsigned)(C * S)), blk, 0, st, N, S, a.indptr, w.rstart, a.idx, (unsigned long long *)w.cnt);
-  if (N) hipLaunchKernelGGL(spd_column_totals, dim3(blocks_for(N, kBlock, INT32_MAX)), blk, 0, st, N, C, w.cnt, w.tot);
-  if (nb) hipLaunchKernelGGL(scan_tile_sums, dim3((unsigned)nb), blk, 0, st, N, w.tot, w.bsum);
-  hipLaunchKernelGGL(scan_of_sums, dim3(1), blk, 0, st, nb, w.bsum);
-  if (nb) hipLaunchKernelGGL(scan_tiles, dim3((unsigned)nb), blk, 0, st, N, nb, w.tot, w.bsum, b.indptr);
+    hipLaunchKernelGGL(spd_count, dim3((unsigned)(C * S)), blk, 0, st, N, S, a.indptr, rstart, a.idx, (unsigned long long *)cnt);
+  if (N) hipLaunchKernelGGL(spd_column_totals, dim3(blocks_for(N, kBlock, INT32_MAX)), blk, 0, st, N, C, cnt, tot);
+  if (nb) hipLaunchKernelGGL(scan_tile_sums, dim3((unsigned)nb), blk, 0, st, N, tot, bsum);
+  hipLaunchKernelGGL(scan_of_sums, dim3(1), blk, 0, st, nb, bsum);
+  if (nb) hipLaunchKernelGGL(scan_tiles, dim3((unsigned)nb), blk, 0, st, N, nb, tot, bsum, b.indptr);
   else RLH_HIP(hipMemsetAsync(b.indptr, 0, 8, st));
-  if (N) hipLaunchKernelGGL(spd_chunk_places, dim3(blocks_for(N, kBlock, INT32_MAX)), blk, 0, st, N, C, b.indptr, w.cnt);
+  if (N) hipLaunchKernelGGL(spd_chunk_places, dim3(blocks_for(N, kBlock, INT32_MAX)), blk, 0, st, N, C, b.indptr, cnt);
   if (nnz && N)
-    hipLaunchKernelGGL(spd_scatter<T>, dim3((unsigned)C), dim3(64), 0, st, a.indptr, w.rstart, a.idx, (const T *)a.val, N, w.cnt,
+    hipLaunchKernelGGL(spd_scatter<T>, dim3((unsigned)C), dim3(64), 0, st, a.indptr, rstart, a.idx, (const T *)a.val, N, cnt,
                        b.idx, (T *)b.val);
   hipLaunchKernelGGL(spd_partition, dim3(blocks_for(b.G + 1, kBlock, INT32_MAX)), blk, 0, st, N, nnz, b.G, b.indptr, b.row_at);
   RLH_HIP(hipGetLastError());
@@ -654,14 +636,7 @@ int apply_impl(rlh_spd *h, const Side &s, int64_t m, const T *X, int64_t ldx, T 
   int Lshift, wpmax;
   panel_shape(wmax, es, &Lshift, &wpmax);
   const int64_t need = work_need(s, wpmax, es);
-  if (need > h->work_bytes) {            // grows once per larger block, then reused without allocation
-    RLH_HIP(hipStreamSynchronize(st));
-    if (h->work) RLH_HIP(hipFree(h->work));
-    h->work = nullptr;
-    h->work_bytes = 0;
-    RLH_HIP(hipMalloc(&h->work, need));
-    h->work_bytes = need;
-  }
+  if (int rc = h->work.reserve(need)) return rc;      // grows once per larger block, then reused without allocation
   for (int64_t j0 = 0; j0 < m; j0 += kPanel) {
     const int w = (int)std::min<int64_t>(kPanel, m - j0);
     int wp;
@@ -778,19 +753,17 @@ extern "C" int rlh_spd_row_sumsq(rlh_spd_t h, double *h_out) {
   const Side &s = h->side[0];
   if (s.rows == 0) return 0;
   RLH_REQUIRE(h_out, "rlh_spd_row_sumsq: null output");
-  double *d = nullptr;
-  RLH_HIP(hipMalloc(&d, s.rows * sizeof(double)));
+  DevBuf<double> d;
+  if (int rc = d.alloc(s.rows)) return rc;
   switch (h->dtype) {
     case RLH_S: row_sumsq_impl<float>(s, d); break;
     case RLH_D: row_sumsq_impl<double>(s, d); break;
     case RLH_C: row_sumsq_impl<c32>(s, d); break;
     case RLH_Z: row_sumsq_impl<c64>(s, d); break;
   }
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx().stream);
-  if (e == hipSuccess) e = hipMemcpy(h_out, d, s.rows * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  RLH_HIP(e);
+  RLH_HIP(hipGetLastError());
+  RLH_HIP(hipStreamSynchronize(ctx().stream));
+  RLH_HIP(hipMemcpy(h_out, d, s.rows * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -801,8 +774,8 @@ extern "C" int rlh_spd_absmax(rlh_spd_t h, double *h_out) {
   const Side &s = h->side[0];
   if (s.nnz == 0) return 0;
   const unsigned nb = blocks_for(s.nnz, kBlock, 1024);
-  double *d = nullptr;
-  RLH_HIP(hipMalloc(&d, nb * sizeof(double)));
+  DevBuf<double> d;
+  if (int rc = d.alloc(nb)) return rc;
   switch (h->dtype) {
     case RLH_S: absmax_impl<float>(s, nb, d); break;
     case RLH_D: absmax_impl<double>(s, nb, d); break;
@@ -810,11 +783,9 @@ extern "C" int rlh_spd_absmax(rlh_spd_t h, double *h_out) {
     case RLH_Z: absmax_impl<c64>(s, nb, d); break;
   }
   std::vector<double> host(nb);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx().stream);
-  if (e == hipSuccess) e = hipMemcpy(host.data(), d, nb * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  RLH_HIP(e);
+  RLH_HIP(hipGetLastError());
+  RLH_HIP(hipStreamSynchronize(ctx().stream));
+  RLH_HIP(hipMemcpy(host.data(), d, nb * sizeof(double), hipMemcpyDeviceToHost));
   double mx = 0.0;
   for (double v : host) mx = v > mx ? v : mx;
   *h_out = mx;
@@ -823,10 +794,7 @@ extern "C" int rlh_spd_absmax(rlh_spd_t h, double *h_out) {
 
 extern "C" int rlh_spd_destroy(rlh_spd_t h) {
   if (!h) return 0;
-  if (h->work) (void)hipStreamSynchronize(ctx().stream);
-  free_side(h->side[0]);
-  free_side(h->side[1]);
-  (void)hipFree(h->work);
+  if (ctx().ready) (void)hipStreamSynchronize(ctx().stream);
   delete h;
   return 0;
 }
@@ -837,13 +805,13 @@ extern "C" int rlh_spd_info(rlh_spd_t h, int64_t *n_rows, int64_t *n_cols, int64
   if (n_rows) *n_rows = h->side[0].rows;
   if (n_cols) *n_cols = h->side[0].cols;
   if (nnz) *nnz = h->side[0].nnz;
-  if (device_bytes) *device_bytes = side_bytes(h->side[0], es) + side_bytes(h->side[1], es) + h->work_bytes;
+  if (device_bytes) *device_bytes = side_bytes(h->side[0], es) + side_bytes(h->side[1], es) + (int64_t)h->work.bytes();
   return 0;
 }
 
 extern "C" int rlh_spd_stats(rlh_spd_t h, int64_t *workspace_bytes, double *transpose_seconds) {
   RLH_REQUIRE(h, "rlh_spd_stats: null handle");
-  if (workspace_bytes) *workspace_bytes = h->work_bytes;
+  if (workspace_bytes) *workspace_bytes = (int64_t)h->work.bytes();
   if (transpose_seconds) *transpose_seconds = h->transpose_seconds;
   return 0;
 }

@@ -127,25 +127,14 @@ int wide_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices, const 
   h->wide_maxcol.resize((size_t)nblocks);
   for (int64_t b = 0; b < nblocks; ++b) h->wide_maxcol[(size_t)b] = wins[b].back().start + wins[b].back().len - 1;
   h->wide_gmax = gmax;
-  if (int rc = upload(h->wide_meta, meta.data(), (size_t)nblocks * sizeof(WideMeta))) return rc;
-  if (int rc = upload(h->wide_gsrc, gsrc.data(), (size_t)goff * sizeof(int32_t), sizeof(int32_t))) return rc;
-  if (int rc = upload(h->wide_idx, idx.data(), idx.size())) return rc;
-  if (int rc = upload(h->wide_vals, vals.data(), vals.size())) return rc;
+  if (int rc = h->wide_meta.upload(meta.data(), (size_t)nblocks * sizeof(WideMeta))) return rc;
+  if (int rc = h->wide_gsrc.upload(gsrc.data(), (size_t)goff * sizeof(int32_t), sizeof(int32_t))) return rc;
+  if (int rc = h->wide_idx.upload(idx.data(), idx.size())) return rc;
+  if (int rc = h->wide_vals.upload(vals.data(), vals.size())) return rc;
   h->padded = eoff * 8 * kWideRows;
   h->device_bytes = nblocks * (int64_t)sizeof(WideMeta) + goff * 4 + (int64_t)idx.size() + (int64_t)vals.size();
   h->wide_blocks = nblocks;
   return 0;
-}
-
-void wide_destroy(rlh_csr *h) {
-  if (h->wide_meta) (void)hipFree(h->wide_meta);
-  if (h->wide_gsrc) (void)hipFree(h->wide_gsrc);
-  if (h->wide_idx) (void)hipFree(h->wide_idx);
-  if (h->wide_vals) (void)hipFree(h->wide_vals);
-  for (WideSched &s : h->wide_scheds)
-    if (s.sched) (void)hipFree(s.sched);
-  h->wide_scheds.clear();
-  h->wide_meta = nullptr; h->wide_gsrc = nullptr; h->wide_idx = nullptr; h->wide_vals = nullptr;
 }
 
 // The launch order for `slots` resident workgroups over all blocks (part 0), the blocks that
@@ -162,21 +151,18 @@ int wide_sched(rlh_csr *h, int slots, int part, int64_t n_own, const int32_t **s
     const bool interior = h->wide_maxcol[(size_t)b] < n_own;
     if (part == 0 || (part == 1) == interior) list.push_back(b);
   }
-  WideSched s{slots, 0, part, n_own, nullptr, 0};
+  WideSched s{slots, 0, part, n_own, {}, 0};
   if (!list.empty()) {
     well_layout(list, slots, sch, s.grid);
     s.len = (int64_t)sch.size();
-    if (int rc = upload(s.sched, sch.data(), sch.size() * sizeof(int32_t))) return rc;
+    if (int rc = s.sched.upload(sch.data(), sch.size() * sizeof(int32_t))) return rc;
   }
   if (h->wide_scheds.size() >= 16) {             // a bounded cache: drop the oldest
-    if (h->wide_scheds.front().sched) {
-      (void)hipStreamSynchronize(ctx().stream);
-      (void)hipFree(h->wide_scheds.front().sched);
-    }
+    if (h->wide_scheds.front().sched) (void)hipStreamSynchronize(ctx().stream);
     h->wide_scheds.erase(h->wide_scheds.begin());
   }
-  h->wide_scheds.push_back(s);
   *sched = s.sched; *len = s.len; *grid = s.grid;
+  h->wide_scheds.push_back(std::move(s));
   return 0;
 }
 

@@ -36,8 +36,8 @@ namespace rlh { struct TrsvUnit; struct TrsvRow; }
 struct TrsvPlan {                  // units of an operator for `pl` lanes across the pieces of a row
   int pl = 0;
   int64_t nunits = 0;
-  rlh::TrsvUnit *units = nullptr;  // device
-  rlh::TrsvRow *rows = nullptr;    // device, by position
+  rlh::DevBuf<rlh::TrsvUnit> units;
+  rlh::DevBuf<rlh::TrsvRow> rows;  // by position
 };
 
 struct rlh_sptrsv {
@@ -49,9 +49,9 @@ struct rlh_sptrsv {
   // come first), then rhs entries (column = original row; see sptrsv_build).  The result image of an operator is
   // indexed by position too: rows of one level that read neighbouring rows of an earlier level -- any structured grid
   // or node-blocked matrix -- then gather neighbouring pieces, which the memory pipeline merges into few requests
-  int32_t *cols;
-  void *vals;
-  int32_t *pos_of;                 // row -> position
+  rlh::DevBuf<int32_t> cols;
+  rlh::DevBuf<void> vals;
+  rlh::DevBuf<int32_t> pos_of;     // row -> position
   std::vector<int64_t> lev_off;    // host: first position of every level, nlevels + 1
   std::vector<int64_t> rowptr_h;   // host: first entry of every position, n + 1
   std::vector<int32_t> dep_pos_h;  // host: per x entry, the position of the row it reads (plans are built from it)
@@ -62,8 +62,7 @@ struct rlh_sptrsv {
   int plan_lru;
   int64_t device_bytes;
   // scratch (control words + block images) of the chain this operator heads
-  void *work;
-  int64_t work_bytes;
+  rlh::DevBuf<void> work;
 };
 
 namespace rlh {
@@ -777,17 +776,17 @@ static int build_plan(rlh_sptrsv *t, int pl, TrsvPlan *plan) {
   }
   plan->pl = pl;
   plan->nunits = (int64_t)units.size();
-  RLH_HIP(hipMalloc((void **)&plan->units, std::max<size_t>(units.size(), 1) * sizeof(TrsvUnit)));
-  RLH_HIP(hipMalloc((void **)&plan->rows, rows.size() * sizeof(TrsvRow)));
+  if (int rc = plan->units.alloc(std::max<size_t>(units.size(), 1))) return rc;
+  if (int rc = plan->rows.alloc(rows.size())) return rc;
   if (!units.empty()) RLH_HIP(hipMemcpy(plan->units, units.data(), units.size() * sizeof(TrsvUnit), hipMemcpyHostToDevice));
   RLH_HIP(hipMemcpy(plan->rows, rows.data(), rows.size() * sizeof(TrsvRow), hipMemcpyHostToDevice));
   return 0;
 }
 
 static void free_plan(TrsvPlan *p) {
-  if (p->units) (void)hipFree(p->units);
-  if (p->rows) (void)hipFree(p->rows);
-  p->units = nullptr; p->rows = nullptr; p->pl = 0; p->nunits = 0;
+  p->units.reset();
+  p->rows.reset();
+  p->pl = 0; p->nunits = 0;
 }
 
 static int plan_for(rlh_sptrsv *t, int pl, TrsvPlan **out) {
@@ -836,13 +835,7 @@ static int solve_chain_impl(int nops, rlh_sptrsv *const *ops, const int64_t *per
   const int64_t slot_pieces = (int64_t)ngroups * n8 * ppt;
   const int64_t scratch_bytes = (int64_t)(nops + 1) * slot_pieces * 16;
   const int64_t need = ctrl_bytes + scratch_bytes;
-  if (head->work_bytes < need) {
-    RLH_HIP(hipStreamSynchronize(c.stream));
-    if (head->work) RLH_HIP(hipFree(head->work));
-    head->work = nullptr; head->work_bytes = 0;
-    RLH_HIP(hipMalloc(&head->work, (size_t)need));
-    head->work_bytes = need;
-  }
+  if (int rc = head->work.reserve((size_t)need)) return rc;
   a.nops = nops; a.total_units = (int)total_units; a.ngroups = ngroups; a.ppt = ppt; a.pl = pl;
   a.n8 = n8;
   a.ctrl = (unsigned *)head->work;                            // (the control words open the allocation: zeroed per call)
@@ -852,8 +845,10 @@ static int solve_chain_impl(int nops, rlh_sptrsv *const *ops, const int64_t *per
   { const char *e = getenv("RLH_SPTRSV_SPIN_TICKS"); if (e && *e && atoll(e) > 0) a.spin_ticks = (unsigned long long)atoll(e); }   // (tests)
   { const char *e = getenv("RLH_SPTRSV_NAP"); a.nap = (e && *e) ? atoi(e) : 1; }      // s_sleep between poll rounds (tunable)
   const char *trace_path = getenv("RLH_SPTRSV_TRACE");      // diagnostics: per-unit stamps of group 0 to this file (synchronises)
+  DevBuf<unsigned long long> trace;
   if (trace_path && *trace_path) {
-    RLH_HIP(hipMalloc((void **)&a.trace, (size_t)total_units * 128));
+    if (int rc = trace.alloc((size_t)total_units * 16)) return rc;
+    a.trace = trace;
     RLH_HIP(hipMemsetAsync(a.trace, 0, (size_t)total_units * 128, c.stream));
   }
   RLH_HIP(hipMemsetAsync(head->work, 0, (size_t)ctrl_bytes, c.stream));
@@ -892,7 +887,6 @@ static int solve_chain_impl(int nops, rlh_sptrsv *const *ops, const int64_t *per
     std::vector<unsigned long long> h((size_t)total_units * 16);
     RLH_HIP(hipStreamSynchronize(c.stream));
     RLH_HIP(hipMemcpy(h.data(), a.trace, h.size() * 8, hipMemcpyDeviceToHost));
-    RLH_HIP(hipFree(a.trace));
     if (FILE *f = fopen(trace_path, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
   }
   return 0;
@@ -1201,13 +1195,13 @@ static int sptrsv_build(rlh_sptrsv *t, const int64_t *indptr, const int32_t *ind
   t->rowptr_h = rp;
   t->entries = (int64_t)cols.size();
   lap("level order");
-  RLH_HIP(hipMalloc((void **)&t->cols, std::max<size_t>(cols.size(), 1) * sizeof(int32_t)));
-  RLH_HIP(hipMalloc((void **)&t->vals, std::max<size_t>(vals.size(), 1) * sizeof(T)));
+  if (int rc = t->cols.alloc(std::max<size_t>(cols.size(), 1))) return rc;
+  if (int rc = t->vals.alloc(std::max<size_t>(vals.size(), 1) * sizeof(T))) return rc;
   if (!cols.empty()) {
     RLH_HIP(hipMemcpy(t->cols, cols.data(), cols.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     RLH_HIP(hipMemcpy(t->vals, vals.data(), vals.size() * sizeof(T), hipMemcpyHostToDevice));
   }
-  RLH_HIP(hipMalloc((void **)&t->pos_of, std::max<size_t>((size_t)n, 1) * sizeof(int32_t)));
+  if (int rc = t->pos_of.alloc(std::max<size_t>((size_t)n, 1))) return rc;
   if (n > 0) RLH_HIP(hipMemcpy(t->pos_of, pos_of.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
   t->device_bytes = (int64_t)cols.size() * (4 + (int64_t)sizeof(T)) + n * 4 + n * 16;
   lap("upload");
@@ -1305,8 +1299,8 @@ int rlh_sptrsv_create(rlh_sptrsv_t *out, int dtype, int64_t n, const int64_t *in
   RLH_REQUIRE(indptr[n] == 0 || (indices && values), "rlh_sptrsv_create: null indices/values");
   rlh_sptrsv *t = new rlh_sptrsv();
   t->dtype = dtype; t->n = n; t->nnz = 0; t->lower = lower ? 1 : 0; t->unit = unit_diag ? 1 : 0;
-  t->cols = nullptr; t->vals = nullptr; t->pos_of = nullptr; t->plan_lru = 0; t->entries = 0; t->nblocks = 0; t->levels_plain = 0;
-  t->device_bytes = 0; t->work = nullptr; t->work_bytes = 0;
+  t->plan_lru = 0; t->entries = 0; t->nblocks = 0; t->levels_plain = 0;
+  t->device_bytes = 0;
   int rc = 1;
   switch (dtype) {
     case RLH_S: rc = sptrsv_build<RLH_S>(t, indptr, indices, values); break;
@@ -1348,15 +1342,7 @@ int rlh_sptrsv_solve_chain(int nops, const rlh_sptrsv_t *ops, const int64_t *d_p
 
 int rlh_sptrsv_destroy(rlh_sptrsv_t t) {
   if (!t) return 0;
-  if (ctx().ready) {
-    (void)hipStreamSynchronize(ctx().stream);
-    free_plan(&t->plan[0]);
-    free_plan(&t->plan[1]);
-    if (t->cols) (void)hipFree(t->cols);
-    if (t->vals) (void)hipFree(t->vals);
-    if (t->pos_of) (void)hipFree(t->pos_of);
-    if (t->work) (void)hipFree(t->work);
-  }
+  if (ctx().ready) (void)hipStreamSynchronize(ctx().stream);
   delete t;
   return 0;
 }

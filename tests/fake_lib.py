@@ -94,6 +94,11 @@ class FakeLib:
     def rlh_mem_info(self, f, t):
         return 0
 
+    def rlh_device_live(self, nbytes, nblocks):
+        nbytes._obj.value = 0
+        nblocks._obj.value = 0
+        return 0
+
     # ---- memory
     def rlh_malloc(self, pp, nbytes):
         buf = ctypes.create_string_buffer(max(int(nbytes), 1))
