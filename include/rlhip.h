@@ -542,6 +542,31 @@ int rlh_fsai_info(rlh_fsai_t h, int64_t *n, int64_t *nnz, int64_t *longest_row, 
 int rlh_fsai_get(rlh_fsai_t h, int64_t *indptr, int32_t *indices, void *values);
 int rlh_fsai_destroy(rlh_fsai_t h);
 
+/* ---- the approximate inverse's own application: Y = G^H (G X) in two kernels, the work block W = G X kept in the
+ *      handle's type or narrower.  A plan is made from a built handle and owns copies of G and G^H in a layout of its
+ *      own (slices of 64 rows stored position-major, the long rows' remainders in a CSR tail; never more than twice
+ *      the entries in slots: before the first product device_bytes <= 2 (nnz(G) + nnz(G^H)) (4 + sizeof V) + 64 n +
+ *      4096 for every matrix); the handle is not referenced after the return and may be destroyed first.
+ * work 0 (native): values and W in the handle's dtype T.  work 1 (float32): values rounded once to float / complex
+ * float (V), W kept in that type.  work 2 (bf16, real dtypes only): values in float, W in bfloat16 (rounded once per
+ * element to nearest even on the float32 bits, as rlh_bf16_pack does).  All arithmetic is in T.  On float / complex
+ * float handles work 1 is work 0.  The narrow forms are for blocks within the float32 range.
+ * rlh_fsapply_create ends with a checking pass over the finished layout; a violation, an unknown `work`, work 2 on a
+ * complex handle or a null argument return non-zero, a message that names the entry point, and a null plan.  n = 0
+ * gives a valid empty plan.
+ * rlh_fsapply_run: column-major DEVICE blocks of m vectors at element alignment, leading dimensions >= n, Y may be X;
+ * rows from n on and vectors from m on are neither read nor written.  The order of every sum is fixed by the layout:
+ * the same bits from call to call, and column j of a call with m vectors has the bits of the same vector applied
+ * alone.  W grows when a wider block than before arrives (that call synchronises the stream once); otherwise
+ * asynchronous on the library stream.
+ * rlh_fsapply_info: the work form, the slots of the sliced parts (padding included) and the entries in the tails, both
+ * layouts together, and the device bytes held (layouts and W). */
+typedef struct rlh_fsapply *rlh_fsapply_t;
+int rlh_fsapply_create(rlh_fsapply_t *p, rlh_fsai_t h, int work);
+int rlh_fsapply_run(rlh_fsapply_t p, int64_t m, const void *X, int64_t ldx, void *Y, int64_t ldy);
+int rlh_fsapply_info(rlh_fsapply_t p, int *work, int64_t *stored_slots, int64_t *tail_entries, int64_t *device_bytes);
+int rlh_fsapply_destroy(rlh_fsapply_t p);
+
 /* ---- profiling aid: HIP-event time of the last `count` kernels ---- */
 int rlh_timer_start(void);
 int rlh_timer_stop(float *milliseconds);

@@ -131,6 +131,10 @@ SIGNATURES = {
                       ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)],
     'rlh_fsai_get': [_p, _p, _p, _p],
     'rlh_fsai_destroy': [_p],
+    'rlh_fsapply_create': [ctypes.POINTER(_p), _p, _int],
+    'rlh_fsapply_run': [_p, _i64, _p, _i64, _p, _i64],
+    'rlh_fsapply_info': [_p, ctypes.POINTER(_int), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
+    'rlh_fsapply_destroy': [_p],
     'rlh_timer_start': [],
     'rlh_timer_stop': [ctypes.POINTER(ctypes.c_float)],
 }

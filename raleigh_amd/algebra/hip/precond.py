@@ -221,12 +221,28 @@ class ApproximateInverse:
     g the row solved on P.  The choice is by value, made on the device, and invariant under diagonal scaling; a row
     stops at `max_row` columns or when no candidate lowers the functional.  `truncated_rows` then counts the rows that
     `max_row` held back: cut level patterns, rows full before one of their steps, steps that had to leave candidates
-    for lack of room.  ``steps=0`` (the default) is the build without enrichment through the entry points it always had."""
+    for lack of room.  ``steps=0`` (the default) is the build without enrichment through the entry points it always had.
 
-    def __init__(self, matrix, max_row=64, levels=1, steps=0, step_size=1):
+    work (None, 'native', 'float32' or 'bf16') chooses how T is applied.  ``None`` (the default) is the application it
+    always had: two products of the general sparse data operator (rlh_fsai_apply).  The other values make a plan
+    (rlh_fsapply_*) after the build and apply T by its own two kernels, W = G x held between them in a layout made for
+    the second product's gathers: 'native' keeps the values of G and W in the matrix type, 'float32' rounds G once to
+    float32 / complex64 and keeps W in that type (on float32 / complex64 matrices it is 'native'), 'bf16' (real
+    matrices only) keeps G in float32 and W in bfloat16.  The arithmetic stays in the matrix type.  The low-precision
+    forms are for blocks inside the float32 range.  They change iteration counts by a few, not the accuracy of the
+    eigenpairs, because the residuals are formed with A in full precision; the solver then sees a preconditioner that
+    is linear only up to the rounding of W, exactly as with ``ChebyshevPreconditioner(storage='bf16')``.  `csr()` still
+    returns G in the matrix type: the handle keeps it."""
+
+    WORK = {'native': 0, 'float32': 1, 'bf16': 2}
+
+    def __init__(self, matrix, max_row=64, levels=1, steps=0, step_size=1, work=None):
         from . import device_data
         L = self._L = _lib.lib()                          # (the handle belongs to THIS library object)
-        self._h = None
+        self._h = self._plan = None
+        if work is not None and work not in self.WORK:
+            raise ValueError("work must be None, 'native', 'float32' or 'bf16', got %r" % (work,))
+        self.work = work
         max_row = int(max_row)
         if not 1 <= max_row <= 64:
             raise ValueError('max_row must lie in [1, 64], got %d' % max_row)
@@ -280,8 +296,14 @@ class ApproximateInverse:
             args = (_lib.DTYPE_CODE[self._dtype], self._n, _lib.host_ptr(indptr), _lib.host_ptr(indices),
                     _lib.host_ptr(values))
         h = ctypes.c_void_p()
+        if work == 'bf16' and np.dtype(self._dtype).kind == 'c':
+            raise ValueError("work='bf16' is for real matrices only")
         self._create(getattr(L, name), name, h, *args, max_row, *more)
         self._finish(h)
+        if work is not None:
+            plan = ctypes.c_void_p()
+            _lib.check(L.rlh_fsapply_create(ctypes.byref(plan), h, self.WORK[work]))
+            self._plan = plan
 
     @staticmethod
     def _create(fn, name, h, *args):
@@ -308,6 +330,12 @@ class ApproximateInverse:
         self.fill = self.nnz / float(max(self._nnz_a, 1))
 
     def __del__(self):
+        plan, self._plan = getattr(self, '_plan', None), None
+        if plan:
+            try:
+                self._L.rlh_fsapply_destroy(plan)
+            except Exception:
+                pass
         h, self._h = getattr(self, '_h', None), None
         if h:
             try:
@@ -322,10 +350,12 @@ class ApproximateInverse:
         return np.dtype(self._dtype)
 
     def device_bytes(self):
-        """Device memory held: G, G^H, their partitions and the workspaces."""
-        nb = ctypes.c_int64()
+        """Device memory held: G, G^H, their partitions and the workspaces; with `work`, the plan's layouts and its W too."""
+        nb, more = ctypes.c_int64(), ctypes.c_int64()
         _lib.check(self._L.rlh_fsai_info(self._h, None, None, None, None, ctypes.byref(nb), None))
-        return int(nb.value)
+        if self._plan:
+            _lib.check(self._L.rlh_fsapply_info(self._plan, None, None, None, ctypes.byref(more)))
+        return int(nb.value) + int(more.value)
 
     def csr(self):
         """G as a SciPy CSR matrix (one copy to the host: rlh_fsai_get)."""
@@ -339,7 +369,13 @@ class ApproximateInverse:
     def algorithmic_bytes(self, m):
         """Entries of G and of G^H (value + 4-byte column index) + one read and one write of a block per product."""
         es = np.dtype(self._dtype).itemsize
-        return 2 * self.nnz * (es + 4) + 4 * self._n * m * es
+        if self.work is None:
+            return 2 * self.nnz * (es + 4) + 4 * self._n * m * es
+        # with a plan: entries at 4 + sizeof V, x read and y written in the matrix type, W written and read in its own
+        cplx = np.dtype(self._dtype).kind == 'c'
+        ev = es if self.work == 'native' else min(es, 8 if cplx else 4)
+        ew = 2 if self.work == 'bf16' else ev
+        return 2 * self.nnz * (ev + 4) + self._n * m * (2 * es + 2 * ew)
 
     def apply(self, x, y):
         """y = G^H (G x) for Vectors windows of equal size (y may be x)."""
@@ -352,7 +388,10 @@ class ApproximateInverse:
             raise ValueError('Matrix and vectors data types differ')
         if x.dimension() != self._n or y.dimension() != self._n:
             raise ValueError('Matrix and vectors dimensions incompatible')
-        _lib.check(self._L.rlh_fsai_apply(self._h, m, x.data_ptr(), x.ld(), y.data_ptr(), y.ld()))
+        if self._plan:
+            _lib.check(self._L.rlh_fsapply_run(self._plan, m, x.data_ptr(), x.ld(), y.data_ptr(), y.ld()))
+        else:
+            _lib.check(self._L.rlh_fsai_apply(self._h, m, x.data_ptr(), x.ld(), y.data_ptr(), y.ld()))
 
 
 def gershgorin_upper_bound(matrix):

@@ -43,8 +43,7 @@
 // create_device check it and run fsai_build inside make_handle.  fsai_build is the one build path: its device arrays are
 // DevBufs (FsaiScratch holds those that pattern_totals works on), pattern_totals is the scan-fetch-wait-check sequence after the level pattern and again after
 // enrichment, and for_each_bin with launch_bin launches the enrichment and the set-up kernels bin by bin.
-#include "device_build.h"
-#include "spmm_data.h"
+#include "fsai.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -584,31 +583,6 @@ struct FsaiScratch {
     if (e1) (void)hipEventDestroy(e1);
   }
 };
-
-}  // namespace
-}  // namespace rlh
-
-struct rlh_fsai {
-  int dtype = 0;
-  int64_t n = 0, nnz = 0, truncated = 0;
-  int longest = 0, levels = 1, steps = 0, step_size = 0;
-  double setup_seconds = 0;
-  rlh_spd_t spd = nullptr;          // G and G^H with their partitions
-  rlh::DevBuf<char> work;           // the n x m block between the two products
-};
-
-namespace rlh {
-namespace {
-
-int exclusive_scan(int64_t n, const int64_t *in, int64_t *bsum, int64_t *out) {
-  hipStream_t st = ctx().stream;
-  const int64_t nb = (n + kScanTile - 1) / kScanTile;
-  hipLaunchKernelGGL(scan_tile_sums, dim3((unsigned)nb), dim3(kBlock), 0, st, n, in, bsum);
-  hipLaunchKernelGGL(scan_of_sums, dim3(1), dim3(kBlock), 0, st, nb, bsum);
-  hipLaunchKernelGGL(scan_tiles, dim3((unsigned)nb), dim3(kBlock), 0, st, n, nb, in, bsum, out);
-  RLH_HIP(hipGetLastError());
-  return 0;
-}
 
 // What the kernels found wrong, as the message of `name`.  cap: the entries the index and value arrays can hold.
 int report(const char *name, const FsaiStatus &s, int64_t cap) {

@@ -1,0 +1,470 @@
+// The approximate inverse's own application Y = G^H (G X) in two kernels (rlh_fsapply_*, include/rlhip.h).
+//
+// Types.  T: the handle's dtype, the type of X and Y and of all arithmetic.  V: the stored values of G and G^H (T, or
+// float / complex float: G rounded once, to nearest).  Wt: the work block W = G X (T, float / complex float, or
+// bfloat16 for real T: rounded once per element, nearest even).
+//
+// Layout, one per product (G for the first, G^H -- values already conjugated -- for the second), built by kernels
+// from the handle's CSR arrays and owned by the plan:
+//   slices   64 consecutive rows each, one wave per slice, lane <-> row; rows are not permuted.  Slice s keeps the
+//            first width[s] entries of its rows position-major: entry p of the row in lane l lies at
+//            off[s] + p * rows(s) + l (rows(s) = 64, fewer in the last slice), so a wave reads consecutive columns and
+//            values per position.  A lane stops at its own length rlen[r] <= width[s]: padding slots are never read
+//            by a product (they hold column 0 and value 0 so that every slot is defined).
+//   width    the largest w with rows(s) * w <= 2 * sum_r min(len_r, w) (2 sum min(len, w) - rows w is concave in w, so
+//            those w are an interval from 0 and a bisection finds its end): the slots of the sliced part are at most
+//            twice its entries WHATEVER the row lengths, which with the 4 n + 8 (n + 1) + 12 (n / 64 + 2) bytes of
+//            rlen, tptr, off and width per layout gives
+//              device_bytes <= 2 (nnz(G) + nnz(G^H)) (4 + sizeof V) + 64 n + 4096
+//            before the first product (the work block comes on top).  A slice of equal rows stores them whole.
+//   tail     what a row has beyond width[s], as CSR (tptr, tcol, tval) in row order: the long rows of G^H (an arrowhead
+//            matrix puts n entries into row 0).  After the sliced part the slice's wave takes its tail rows in
+//            ascending order: lane q sums entries q, q + 64, .. ascending, the 64 partial sums are added by a butterfly
+//            (partners at distance 1, 2, .., 32: the same bits in every lane) and the row's lane adds the total.
+//   check    creation ends with fsap_check over the finished arrays: slice offsets and lengths inside the slot arrays,
+//            row lengths within their slice, tail offsets inside the tail arrays, every column a product will read in
+//            [0, n), the entries counted.  What it finds is a message of rlh_fsapply_create through the status record.
+//
+// Products: grid = (slices / 4) x column tiles of kVT = 8 vectors, 4 waves (slices) per workgroup.  A lane holds kVT
+// accumulators of type T and goes over the positions ascending; a column's sum never sees another column, so the bits
+// of column j do not depend on m or on the tile it falls in.  W is [tile][row][kVT] of Wt (kVT * sizeof Wt is a
+// multiple of 16 bytes): the first product writes, and the second gathers, whole 16-byte pieces; columns past m in
+// the last tile are written as zeros and never stored to Y.  X is gathered and Y written column-major with lanes on
+// consecutive rows, at element alignment.  No atomics, no LDS: the order of every sum is fixed by the layout.
+#include "fsai.h"
+#include "spmm.h"
+
+#include <type_traits>
+
+namespace rlh {
+namespace {
+
+constexpr int kVT = 8;                         // vectors per column tile
+constexpr int kWaves = kBlock / 64;            // slices per workgroup
+constexpr int64_t kMaxTilesY = 65535;          // column tiles per launch (blockIdx.y)
+enum { kErrSlice = 1, kErrLength = 2, kErrColumn = 3, kErrTail = 4 };
+
+struct ApplyStatus : BuildStatus {
+  unsigned long long entries;                  // entries the check kernel counted
+};
+
+struct bf16 { unsigned short u; };
+
+// a stored value or an element of W as T
+__device__ __forceinline__ float up(float a, float) { return a; }
+__device__ __forceinline__ double up(double a, double) { return a; }
+__device__ __forceinline__ double up(float a, double) { return (double)a; }
+__device__ __forceinline__ c32 up(c32 a, c32) { return a; }
+__device__ __forceinline__ c64 up(c64 a, c64) { return a; }
+__device__ __forceinline__ c64 up(c32 a, c64) { return c64{(double)a.re, (double)a.im}; }
+__device__ __forceinline__ float up(bf16 a, float) { return bf16_to_f32(a.u); }
+__device__ __forceinline__ double up(bf16 a, double) { return (double)bf16_to_f32(a.u); }
+// T rounded once to V or Wt (bfloat16: nearest even on the float32 bits, as rlh_bf16_pack)
+__device__ __forceinline__ void down(float a, float *o) { *o = a; }
+__device__ __forceinline__ void down(double a, double *o) { *o = a; }
+__device__ __forceinline__ void down(double a, float *o) { *o = (float)a; }
+__device__ __forceinline__ void down(c32 a, c32 *o) { *o = a; }
+__device__ __forceinline__ void down(c64 a, c64 *o) { *o = a; }
+__device__ __forceinline__ void down(c64 a, c32 *o) { *o = c32{(float)a.re, (float)a.im}; }
+__device__ __forceinline__ void down(float a, bf16 *o) { o->u = f32_to_bf16(a); }
+__device__ __forceinline__ void down(double a, bf16 *o) { o->u = f32_to_bf16((float)a); }
+
+__device__ __forceinline__ int64_t wave_sum(int64_t v) {
+  for (int o = 1; o < 64; o <<= 1) v += (int64_t)__shfl_xor((long long)v, o, 64);
+  return v;
+}
+__device__ __forceinline__ int64_t wave_max(int64_t v) {
+  for (int o = 1; o < 64; o <<= 1) {
+    const int64_t w = (int64_t)__shfl_xor((long long)v, o, 64);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+__device__ __forceinline__ int64_t lane_value(int64_t v, int src) { return (int64_t)__shfl((long long)v, src, 64); }
+
+// the sum over the wave's lanes, partners at distance 1, 2, .., 32: the same bits in every lane
+__device__ __forceinline__ float wave_total(float v) {
+  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_total(double v) {
+  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ c32 wave_total(c32 v) { return c32{wave_total(v.re), wave_total(v.im)}; }
+__device__ __forceinline__ c64 wave_total(c64 v) { return c64{wave_total(v.re), wave_total(v.im)}; }
+
+__device__ __forceinline__ int rows_of(int64_t n, int64_t s) { return (int)(n - s * 64 < 64 ? n - s * 64 : 64); }
+
+// ---------------------------------------------------------------- the layout, built from CSR
+// per slice its width and slots, per row its sliced length and the entries left to the tail (one wave per slice)
+__global__ __launch_bounds__(kBlock) void fsap_widths(int64_t n, int64_t slices, const int64_t *__restrict__ ip,
+                                                      int32_t *__restrict__ width, int64_t *__restrict__ slots,
+                                                      int32_t *__restrict__ rlen, int64_t *__restrict__ tcnt) {
+  const int lane = threadIdx.x & 63;
+  const int64_t waves = (int64_t)gridDim.x * kWaves;
+  for (int64_t s = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6); s < slices; s += waves) {
+    const int64_t r = s * 64 + lane, rows = rows_of(n, s);
+    const int64_t len = r < n ? ip[r + 1] - ip[r] : 0;
+    int64_t lo = 0, hi = wave_max(len);
+    while (lo < hi) {                                  // (lo, hi are the wave's: every lane takes the same turns)
+      const int64_t mid = lo + (hi - lo + 1) / 2;
+      if (rows * mid <= 2 * wave_sum(len < mid ? len : mid)) lo = mid; else hi = mid - 1;
+    }
+    if (r < n) {
+      const int64_t kept = len < lo ? len : lo;
+      rlen[r] = (int32_t)kept;
+      tcnt[r] = len - kept;
+    }
+    if (lane == 0) {
+      width[s] = (int32_t)lo;
+      slots[s] = rows * lo;
+    }
+  }
+}
+
+struct LayoutView {
+  int64_t n, slices, slots, tail;
+  const int64_t *off;            // slices + 1: where a slice begins in col / val
+  const int32_t *width;          // slices
+  const int32_t *rlen;           // n: entries of the row in the sliced part
+  const int64_t *tptr;           // n + 1: the row's entries in tcol / tval
+  const int32_t *col, *tcol;
+  const void *val, *tval;
+};
+
+template <typename T, typename V>
+__global__ __launch_bounds__(kBlock) void fsap_fill(LayoutView L, const int64_t *__restrict__ ip, const int32_t *__restrict__ ix,
+                                                    const T *__restrict__ va, int32_t *__restrict__ col, V *__restrict__ val,
+                                                    int32_t *__restrict__ tcol, V *__restrict__ tval) {
+  const int lane = threadIdx.x & 63;
+  const int64_t waves = (int64_t)gridDim.x * kWaves;
+  for (int64_t s = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6); s < L.slices; s += waves) {
+    const int64_t r = s * 64 + lane, rows = rows_of(L.n, s), base = L.off[s];
+    const bool live = r < L.n;
+    const int64_t w = L.width[s], my = live ? L.rlen[r] : 0, k0 = live ? ip[r] : 0;
+    if (live) {
+      for (int64_t p = 0; p < w; ++p) {
+        const int64_t slot = base + p * rows + lane;
+        V v{};
+        if (p < my) down(va[k0 + p], &v);
+        col[slot] = p < my ? ix[k0 + p] : 0;
+        val[slot] = v;
+      }
+    }
+    // the tails of the slice's rows, each copied by the whole wave
+    const int64_t t0 = live ? L.tptr[r] : 0, tc = live ? ip[r + 1] - k0 - my : 0;
+    unsigned long long todo = __ballot(tc > 0);
+    while (todo) {
+      const int t = __ffsll(todo) - 1;
+      todo &= todo - 1;
+      const int64_t src = lane_value(k0 + my, t), dst = lane_value(t0, t), cnt = lane_value(tc, t);
+      for (int64_t e = lane; e < cnt; e += 64) {
+        tcol[dst + e] = ix[src + e];
+        down(va[src + e], &tval[dst + e]);
+      }
+    }
+  }
+}
+
+// The finished layout as a product will walk it: nothing is read before the offsets that lead to it are known to lie
+// inside the arrays (slots and tail are the sizes the arrays were allocated with).
+__global__ __launch_bounds__(kBlock) void fsap_check(LayoutView L, ApplyStatus *st) {
+  const int lane = threadIdx.x & 63;
+  const int64_t waves = (int64_t)gridDim.x * kWaves;
+  for (int64_t s = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6); s < L.slices; s += waves) {
+    const int64_t r = s * 64 + lane, rows = rows_of(L.n, s), base = L.off[s], next = L.off[s + 1], w = L.width[s];
+    const bool live = r < L.n;
+    if (base < 0 || w < 0 || next - base != rows * w || next > L.slots || (s == 0 && base != 0) ||
+        (s == L.slices - 1 && next != L.slots)) {
+      if (lane == 0) build_error(st, kErrSlice, s);
+      continue;                                        // (the wave's decision: the operands are the slice's)
+    }
+    int64_t my = live ? L.rlen[r] : 0;
+    if (my < 0 || my > w) {
+      build_error(st, kErrLength, r);
+      my = 0;
+    }
+    for (int64_t p = 0; p < my; ++p) {
+      const int64_t c = L.col[base + p * rows + lane];
+      if (c < 0 || c >= L.n) build_error(st, kErrColumn, r);
+    }
+    int64_t t0 = live ? L.tptr[r] : 0, tc = live ? L.tptr[r + 1] - t0 : 0;
+    if (t0 < 0 || tc < 0 || t0 + tc > L.tail || (r == 0 && t0 != 0) || (r == L.n - 1 && t0 + tc != L.tail)) {
+      build_error(st, kErrTail, r);
+      tc = 0;
+    }
+    unsigned long long todo = __ballot(tc > 0);
+    while (todo) {
+      const int t = __ffsll(todo) - 1;
+      todo &= todo - 1;
+      const int64_t b = lane_value(t0, t), cnt = lane_value(tc, t);
+      for (int64_t e = lane; e < cnt; e += 64) {
+        const int64_t c = L.tcol[b + e];
+        if (c < 0 || c >= L.n) build_error(st, kErrColumn, s * 64 + t);
+      }
+    }
+    const int64_t held = wave_sum(my + tc);
+    if (lane == 0) atomicAdd(&st->entries, (unsigned long long)held);
+  }
+}
+
+// ---------------------------------------------------------------- the products
+template <typename Wt> struct alignas(16) WRow { Wt e[kVT]; };
+
+// acc[k] += v * (column j0 + k of the operand at row c): the first product gathers X column-major, the second a row of W
+template <typename T, typename Wt, bool FIRST>
+__device__ __forceinline__ void gather(T (&acc)[kVT], T v, int64_t c, int mt, const T *__restrict__ X, int64_t ldx,
+                                       const WRow<Wt> *__restrict__ W) {
+  if constexpr (FIRST) {
+#pragma unroll
+    for (int k = 0; k < kVT; ++k)
+      if (k < mt) fma_acc(acc[k], v, X[c + k * ldx]);
+  } else {
+    const WRow<Wt> w = W[c];
+#pragma unroll
+    for (int k = 0; k < kVT; ++k) fma_acc(acc[k], v, up(w.e[k], T()));
+  }
+}
+
+// FIRST: Wout = G X (X: the block from column tile0 * kVT on, mt valid columns in a tile); else Y = G^H Win.
+// Wout / Win: the rows of tile tile0 on.
+template <typename T, typename V, typename Wt, bool FIRST>
+__global__ __launch_bounds__(kBlock) void fsap_product(LayoutView L, int64_t m, const T *__restrict__ X, int64_t ldx,
+                                                       const WRow<Wt> *__restrict__ Win, WRow<Wt> *__restrict__ Wout,
+                                                       T *__restrict__ Y, int64_t ldy) {
+  const int lane = threadIdx.x & 63;
+  const int64_t s = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
+  if (s >= L.slices) return;
+  const int64_t tile = blockIdx.y, j0 = tile * kVT;
+  const int mt = (int)(m - j0 < kVT ? m - j0 : kVT);
+  const int64_t r = s * 64 + lane, rows = rows_of(L.n, s);
+  const bool live = r < L.n;
+  const int w = L.width[s], my = live ? L.rlen[r] : 0;
+  const int32_t *col = L.col + L.off[s] + lane;
+  const V *val = (const V *)L.val + L.off[s] + lane;
+  const T *x = FIRST ? X + j0 * ldx : nullptr;
+  const WRow<Wt> *win = FIRST ? nullptr : Win + tile * L.n;
+  T acc[kVT];
+#pragma unroll
+  for (int k = 0; k < kVT; ++k) acc[k] = zero_of(T());
+  for (int p = 0; p < w; ++p)
+    if (p < my) gather<T, Wt, FIRST>(acc, up(val[p * rows], T()), (int64_t)col[p * rows], mt, x, ldx, win);
+  // the tail rows of the slice in ascending order, each by the whole wave
+  const int64_t t0 = live ? L.tptr[r] : 0, tc = live ? L.tptr[r + 1] - t0 : 0;
+  unsigned long long todo = __ballot(tc > 0);
+  while (todo) {
+    const int t = __ffsll(todo) - 1;
+    todo &= todo - 1;
+    const int64_t b = lane_value(t0, t), cnt = lane_value(tc, t);
+    T part[kVT];
+#pragma unroll
+    for (int k = 0; k < kVT; ++k) part[k] = zero_of(T());
+    for (int64_t e = lane; e < cnt; e += 64)
+      gather<T, Wt, FIRST>(part, up(((const V *)L.tval)[b + e], T()), (int64_t)L.tcol[b + e], mt, x, ldx, win);
+#pragma unroll
+    for (int k = 0; k < kVT; ++k) {
+      const T total = wave_total(part[k]);
+      if (lane == t) acc[k] = add_of(acc[k], total);
+    }
+  }
+  if (!live) return;
+  if constexpr (FIRST) {
+    WRow<Wt> out;
+#pragma unroll
+    for (int k = 0; k < kVT; ++k) down(acc[k], &out.e[k]);
+    Wout[tile * L.n + r] = out;
+  } else {
+#pragma unroll
+    for (int k = 0; k < kVT; ++k)
+      if (k < mt) Y[r + (j0 + k) * ldy] = acc[k];
+  }
+}
+
+// ---------------------------------------------------------------- the host side
+struct Layout {
+  int64_t n = 0, slices = 0, slots = 0, tail = 0;
+  DevBuf<int64_t> off, tptr;
+  DevBuf<int32_t> width, rlen, col, tcol;
+  DevBuf<void> val, tval;
+  LayoutView view() const { return LayoutView{n, slices, slots, tail, off, width, rlen, tptr, col, tcol, val, tval}; }
+  int64_t bytes() const {
+    return (int64_t)(off.bytes() + tptr.bytes() + width.bytes() + rlen.bytes() + col.bytes() + tcol.bytes() + val.bytes() +
+                     tval.bytes());
+  }
+};
+
+constexpr const char *kCreate = "rlh_fsapply_create";
+
+int report(const ApplyStatus &s, const char *which, int64_t nnz) {
+  const int code = (int)(s.err >> 56);
+  const long long pos = (long long)(s.err & (((unsigned long long)1 << 56) - 1));
+  switch (code) {
+    case kErrSlice: set_error("%s: broken layout of %s: slice %lld does not lie inside its array", kCreate, which, pos); break;
+    case kErrLength: set_error("%s: broken layout of %s: row %lld is longer than its slice", kCreate, which, pos); break;
+    case kErrColumn: set_error("%s: broken layout of %s: column index out of range in row %lld", kCreate, which, pos); break;
+    case kErrTail: set_error("%s: broken layout of %s: the tail of row %lld does not lie inside its array", kCreate, which, pos); break;
+    default:
+      set_error("%s: broken layout of %s: it holds %llu entries, the matrix %lld", kCreate, which, s.entries, (long long)nnz);
+  }
+  return 1;
+}
+
+// The layout of one orientation (a: its CSR arrays in device memory, `which` names it in messages).
+template <typename T, typename V> int build_layout(Layout &L, const SpdArrays &a, const char *which) {
+  hipStream_t st = ctx().stream;
+  const dim3 blk(kBlock);
+  const int64_t n = a.rows, slices = (n + 63) / 64;
+  const unsigned grid = blocks_for(slices, kWaves, 1 << 20);
+  L.n = n;
+  L.slices = slices;
+  if (int rc = L.off.alloc(slices + 1)) return rc;
+  if (int rc = L.width.alloc(slices)) return rc;
+  if (int rc = L.rlen.alloc(n)) return rc;
+  if (int rc = L.tptr.alloc(n + 1)) return rc;
+  DevBuf<int64_t> slots, tcnt, bsum;
+  DevBuf<ApplyStatus> status;
+  if (int rc = slots.alloc(slices)) return rc;
+  if (int rc = tcnt.alloc(n)) return rc;
+  if (int rc = bsum.alloc((n + kScanTile - 1) / kScanTile + 1)) return rc;
+  if (int rc = status.alloc(1)) return rc;
+  hipLaunchKernelGGL(fsap_widths, dim3(grid), blk, 0, st, n, slices, a.indptr, L.width.get(), slots.get(), L.rlen.get(), tcnt.get());
+  RLH_HIP(hipGetLastError());
+  if (int rc = exclusive_scan(slices, slots, bsum, L.off)) return rc;
+  if (int rc = exclusive_scan(n, tcnt, bsum, L.tptr)) return rc;
+  RLH_HIP(hipMemcpyAsync(&L.slots, L.off + slices, 8, hipMemcpyDeviceToHost, st));
+  RLH_HIP(hipMemcpyAsync(&L.tail, L.tptr + n, 8, hipMemcpyDeviceToHost, st));
+  RLH_HIP(hipStreamSynchronize(st));
+  RLH_REQUIRE(L.slots >= 0 && L.tail >= 0 && L.tail <= a.nnz && L.slots <= 2 * (a.nnz - L.tail),
+              "%s: inconsistent slot counts of %s", kCreate, which);
+  if (L.slots) {
+    if (int rc = L.col.alloc(L.slots)) return rc;
+    if (int rc = L.val.alloc((size_t)L.slots * sizeof(V))) return rc;
+  }
+  if (L.tail) {
+    if (int rc = L.tcol.alloc(L.tail)) return rc;
+    if (int rc = L.tval.alloc((size_t)L.tail * sizeof(V))) return rc;
+  }
+  hipLaunchKernelGGL((fsap_fill<T, V>), dim3(grid), blk, 0, st, L.view(), a.indptr, a.idx, (const T *)a.val, L.col.get(),
+                     (V *)L.val.get(), L.tcol.get(), (V *)L.tval.get());
+  ApplyStatus hs{};
+  hs.err = kNoError;
+  RLH_HIP(hipMemcpyAsync(status, &hs, sizeof hs, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(fsap_check, dim3(grid), blk, 0, st, L.view(), status.get());
+  RLH_HIP(hipGetLastError());
+  RLH_HIP(hipMemcpyAsync(&hs, status, sizeof hs, hipMemcpyDeviceToHost, st));
+  RLH_HIP(hipStreamSynchronize(st));           // the handle's arrays and the scratch are not referenced after the return
+  if (hs.err != kNoError || (int64_t)hs.entries != a.nnz) return report(hs, which, a.nnz);
+  return 0;
+}
+
+}  // namespace
+}  // namespace rlh
+
+struct rlh_fsapply {
+  int dtype = 0, work = 0;
+  int64_t n = 0;
+  rlh::Layout g, gh;                // G for the first product, G^H for the second
+  rlh::DevBuf<char> w;              // W = G X as [tile][row][kVT]
+};
+
+namespace rlh {
+namespace {
+
+template <typename T, typename V> int build_both(rlh_fsapply *p, const rlh_fsai *h) {
+  if (int rc = build_layout<T, V>(p->g, spd_arrays(h->spd, 0), "G")) return rc;
+  return build_layout<T, V>(p->gh, spd_arrays(h->spd, 1), "G^H");
+}
+
+template <typename T, typename V, typename Wt>
+int run_typed(rlh_fsapply *p, int64_t m, const void *X, int64_t ldx, void *Y, int64_t ldy) {
+  const int64_t tiles = (m + kVT - 1) / kVT;
+  if (int rc = p->w.reserve((size_t)tiles * (size_t)p->n * sizeof(WRow<Wt>))) return rc;   // grows once per wider block
+  WRow<Wt> *W = (WRow<Wt> *)p->w.get();
+  const dim3 blk(kBlock);
+  const unsigned gx = (unsigned)((p->g.slices + kWaves - 1) / kWaves);
+  hipStream_t st = ctx().stream;
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int64_t t0 = 0; t0 < tiles; t0 += kMaxTilesY) {
+      const int64_t nt = tiles - t0 < kMaxTilesY ? tiles - t0 : kMaxTilesY, j0 = t0 * kVT;
+      const dim3 grid(gx, (unsigned)nt);
+      if (pass == 0)
+        hipLaunchKernelGGL((fsap_product<T, V, Wt, true>), grid, blk, 0, st, p->g.view(), m - j0, (const T *)X + j0 * ldx, ldx,
+                           (const WRow<Wt> *)nullptr, W + t0 * p->n, (T *)nullptr, (int64_t)0);
+      else
+        hipLaunchKernelGGL((fsap_product<T, V, Wt, false>), grid, blk, 0, st, p->gh.view(), m - j0, (const T *)nullptr, (int64_t)0,
+                           (const WRow<Wt> *)(W + t0 * p->n), (WRow<Wt> *)nullptr, (T *)Y + j0 * ldy, ldy);
+    }
+  }
+  RLH_HIP(hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+}  // namespace rlh
+
+using namespace rlh;
+
+extern "C" int rlh_fsapply_create(rlh_fsapply_t *pp, rlh_fsai_t h, int work) {
+  if (int rc = require_ready()) return rc;
+  RLH_REQUIRE(pp != nullptr, "rlh_fsapply_create: null plan pointer");
+  *pp = nullptr;
+  RLH_REQUIRE(h != nullptr, "rlh_fsapply_create: null handle");
+  RLH_REQUIRE(work >= 0 && work <= 2, "rlh_fsapply_create: work must be 0 (native), 1 (float32) or 2 (bf16), got %d", work);
+  RLH_REQUIRE(work != 2 || h->dtype == RLH_S || h->dtype == RLH_D, "rlh_fsapply_create: bfloat16 work blocks are for real types only");
+  rlh_fsapply *p = new rlh_fsapply();
+  p->dtype = h->dtype;
+  p->work = work;
+  p->n = h->n;
+  int rc = 0;
+  if (h->n > 0 && h->spd) {
+    switch (h->dtype) {
+      case RLH_S: rc = build_both<float, float>(p, h); break;
+      case RLH_D: rc = work ? build_both<double, float>(p, h) : build_both<double, double>(p, h); break;
+      case RLH_C: rc = build_both<c32, c32>(p, h); break;
+      default: rc = work ? build_both<c64, c32>(p, h) : build_both<c64, c64>(p, h);
+    }
+  }
+  if (rc) {
+    rlh_fsapply_destroy(p);
+    return rc;
+  }
+  *pp = p;
+  return 0;
+}
+
+extern "C" int rlh_fsapply_run(rlh_fsapply_t p, int64_t m, const void *X, int64_t ldx, void *Y, int64_t ldy) {
+  if (int rc = require_ready()) return rc;
+  RLH_REQUIRE(p, "rlh_fsapply_run: null plan");
+  RLH_REQUIRE(m >= 0, "rlh_fsapply_run: negative number of vectors");
+  if (m == 0 || p->n == 0) return 0;
+  RLH_REQUIRE(X && Y, "rlh_fsapply_run: null pointer");
+  RLH_REQUIRE(ldx >= p->n && ldy >= p->n, "rlh_fsapply_run: Matrix and vectors dimensions incompatible");
+  switch (p->dtype) {
+    case RLH_S:
+      return p->work == 2 ? run_typed<float, float, bf16>(p, m, X, ldx, Y, ldy) : run_typed<float, float, float>(p, m, X, ldx, Y, ldy);
+    case RLH_D:
+      return p->work == 2   ? run_typed<double, float, bf16>(p, m, X, ldx, Y, ldy)
+             : p->work == 1 ? run_typed<double, float, float>(p, m, X, ldx, Y, ldy)
+                            : run_typed<double, double, double>(p, m, X, ldx, Y, ldy);
+    case RLH_C: return run_typed<c32, c32, c32>(p, m, X, ldx, Y, ldy);
+    default:
+      return p->work ? run_typed<c64, c32, c32>(p, m, X, ldx, Y, ldy) : run_typed<c64, c64, c64>(p, m, X, ldx, Y, ldy);
+  }
+}
+
+extern "C" int rlh_fsapply_info(rlh_fsapply_t p, int *work, int64_t *stored_slots, int64_t *tail_entries, int64_t *device_bytes) {
+  RLH_REQUIRE(p, "rlh_fsapply_info: null plan");
+  if (work) *work = p->work;
+  if (stored_slots) *stored_slots = p->g.slots + p->gh.slots;
+  if (tail_entries) *tail_entries = p->g.tail + p->gh.tail;
+  if (device_bytes) *device_bytes = p->g.bytes() + p->gh.bytes() + (int64_t)p->w.bytes();
+  return 0;
+}
+
+extern "C" int rlh_fsapply_destroy(rlh_fsapply_t p) {
+  if (!p) return 0;
+  if (ctx().ready) (void)hipStreamSynchronize(ctx().stream);
+  delete p;
+  return 0;
+}

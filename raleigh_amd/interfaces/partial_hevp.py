@@ -43,7 +43,9 @@ def partial_hevp(A, B=None, T=None, buckling=False, sigma=0, which=6, tol=1e-4, 
     on the pattern of that power of the lower triangle: fewer iterations on stencil-like operators, whose rows store
     only a few entries, for a longer set-up; ``steps=`` and ``step_size=`` then let every row take, step by step,
     the further columns that lower its Kaporin functional most: a pattern chosen by value on the GPU, for matrices
-    whose level patterns ``max_row`` cuts), as `ChebyshevPreconditioner`
+    whose level patterns ``max_row`` cuts; ``work='native'``, ``'float32'`` or ``'bf16'`` applies it by its own two
+    kernels with the block between the two products kept in the matrix type, float32 or bfloat16 -- the same
+    preconditioner up to the rounding of that block, a few iterations more or fewer), as `ChebyshevPreconditioner`
     is from the operator; an IncompleteLU preconditioner is a host factorisation and is set up from a SciPy matrix
     only.  A CPU tensor is taken as the SciPy matrix of its arrays (ndarrays come back).
 

@@ -16,13 +16,17 @@
   application  milliseconds per call at m = 16: HIP events (rlh_timer_start / rlh_timer_stop) around --calls calls, the
                two preconditioners taking turns inside each of --repeats repeats; algorithmic GB/s at the fastest
   solve        partial_hevp(which=10, tol=1e-6) with T = ApproximateInverse, IncompleteLU, True: iterations and seconds
+  work         --work native,float32,bf16: every ApproximateInverse above once more with each `work` (its own two-kernel
+               application, W = G X kept in the matrix type, float32 or bfloat16), application and solve timed in the same
+               run against the same build with work=None: "beats", "loses to" or "no winner" per line
 
 Every timing is repeated --repeats times and reported as fastest .. slowest; "A beats B" means A's slowest repeat is
 faster than B's fastest, anything else is "no winner".  Nothing here is a threshold.  --setup-only stops after the
 set-up lines (for comparing two builds of the library on one machine).
 
     python tools/approx_inverse_bench.py [--out profiles/r11_approx_inverse_levels.txt] [--levels 1,2,3]
-                                         [--adaptive 1:4:4,1:4:8,2:2:4] [--m 16] [--calls 20] [--repeats 5] [--setup-only]
+                                         [--adaptive 1:4:4,1:4:8,2:2:4] [--work native,float32,bf16] [--m 16] [--calls 20]
+                                         [--repeats 5] [--setup-only]
 """
 import argparse
 import ctypes
@@ -38,8 +42,9 @@ sys.path.insert(0, ROOT)
 
 
 def resource_lines():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'kernel_resources.py'), 'fsai'], capture_output=True, text=True)
-    out = ['== tools/kernel_resources.py fsai (-Rpass-analysis=kernel-resource-usage; scr = scratch bytes per lane)']
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'kernel_resources.py'), 'fsai', 'fsai_apply'], capture_output=True,
+                       text=True)
+    out = ['== tools/kernel_resources.py fsai fsai_apply (-Rpass-analysis=kernel-resource-usage; scr = scratch bytes per lane)']
     return out + ['   ' + ln for ln in (r.stdout.strip().splitlines() or ['(no compiler here: %s)' % r.stderr.strip()[-200:]])]
 
 
@@ -48,6 +53,7 @@ def main():
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'r11_approx_inverse_levels.txt'))
     ap.add_argument('--levels', default='1,2,3', help='levels of fill of ApproximateInverse, comma separated')
     ap.add_argument('--adaptive', default='', help='adaptive patterns as LEVELS:STEPS:SIZE, comma separated')
+    ap.add_argument('--work', default='', help="work forms of the application ('native', 'float32', 'bf16'), comma separated")
     ap.add_argument('--setup-only', action='store_true', help='set-up timings only')
     ap.add_argument('--m', type=int, default=16)
     ap.add_argument('--calls', type=int, default=20)
@@ -58,6 +64,7 @@ def main():
     levels = [int(v) for v in args.levels.split(',')]
     adaptive = [tuple(int(v) for v in spec.split(':')) for spec in args.adaptive.split(',') if spec]
     assert all(len(spec) == 3 for spec in adaptive), '--adaptive takes LEVELS:STEPS:SIZE'
+    works = [w for w in args.work.split(',') if w]
     import torch
     import scipy.sparse as sp
     from raleigh_amd import _lib
@@ -84,6 +91,13 @@ def main():
             return '%s beats %s (slowest %.4g < fastest %.4g)' % (a, b, max(ta), min(tb))
         if max(tb) < min(ta):
             return '%s beats %s (slowest %.4g < fastest %.4g)' % (b, a, max(tb), min(ta))
+        return 'no winner between %s and %s (the ranges overlap)' % (a, b)
+
+    def verdict(a, b, ta, tb):
+        if max(ta) < min(tb):
+            return '%s beats %s (slowest %.4g < fastest %.4g)' % (a, b, max(ta), min(tb))
+        if max(tb) < min(ta):
+            return '%s loses to %s (fastest %.4g > slowest %.4g)' % (a, b, min(ta), max(tb))
         return 'no winner between %s and %s (the ranges overlap)' % (a, b)
 
     say('# ApproximateInverse against IncompleteLU and no preconditioner, float64, m = %d' % m)
@@ -131,6 +145,15 @@ def main():
             say()
             del T, Ts, t
             continue
+        # ---- the same builds with a plan of their own application
+        work_names = []                                     # (name with work, name without)
+        for kw, name in zip(kwargs, names):
+            for w in works:
+                wname = '%s work=%s' % (name, w)
+                Ts[wname] = ApproximateInverse(t, work=w, **kw)
+                work_names.append((wname, name))
+                say('   plan    %-42s %.1f MB held with the plan (%.1f MB without)'
+                    % (wname, Ts[wname].device_bytes() / 1e6, Ts[name].device_bytes() / 1e6))
         ilu, ilu_s = None, []
         for _ in range(args.repeats):
             ilu = None
@@ -146,7 +169,7 @@ def main():
         # ---- application
         B, X = Vectors(n, m), Vectors(n, m)
         B.fill_random()
-        ops = [(name, Ts[name], Ts[name].algorithmic_bytes(m)) for name in names]
+        ops = [(name, Ts[name], Ts[name].algorithmic_bytes(m)) for name in names + [wn for wn, _ in work_names]]
         ops.append(('IncompleteLU', ilu, ilu.chain().algorithmic_bytes(m)))
         for _, op, _ in ops:
             for _ in range(3):
@@ -162,13 +185,16 @@ def main():
                 _lib.check(L.rlh_timer_stop(ctypes.byref(ms)))
                 times[name].append(ms.value / args.calls)
         for name, op, nb in ops:
-            say('   apply   %-29s %s ms per call; %.1f MB algorithmic -> %.0f GB/s at the fastest'
+            say('   apply   %-42s %s ms per call; %.1f MB algorithmic -> %.0f GB/s at the fastest'
                 % (name, span(times[name], fmt='%.4f'), nb / 1e6, nb / min(times[name]) / 1e6))
         for name in names:
             say('           ' + beats(name, 'IncompleteLU', times[name], times['IncompleteLU']))
+        for wname, name in work_names:
+            say('           ' + verdict(wname, name, times[wname], times[name]))
         # ---- solve
         solves = {}
-        for name, prec in [(name, Ts[name]) for name in names] + [('IncompleteLU', ilu), ('True (none)', True)]:
+        for name, prec in ([(name, Ts[name]) for name in names + [wn for wn, _ in work_names]]
+                           + [('IncompleteLU', ilu), ('True (none)', True)]):
             ts, its, status = [], None, None
             for _ in range(args.repeats):
                 np.random.seed(1)
@@ -181,11 +207,13 @@ def main():
                 ts.append(time.perf_counter() - t0)
                 its = partial_hevp.last['iterations'] if status is not None and status >= 0 else -1
             solves[name] = ts
-            say('   solve   T = %-29s %s s, %d iterations, status %d, smallest eigenvalue %.10g'
+            say('   solve   T = %-42s %s s, %d iterations, status %d, smallest eigenvalue %.10g'
                 % (name, span(ts, fmt='%.4f'), its, status, lmd[0] if lmd is not None and len(lmd) else float('nan')))
         for name in names:
             say('           ' + beats(name, 'IncompleteLU', solves[name], solves['IncompleteLU']))
             say('           ' + beats(name, 'no preconditioner', solves[name], solves['True (none)']))
+        for wname, name in work_names:
+            say('           ' + verdict(wname, name, solves[wname], solves[name]))
         for name in level_names[1:]:
             say('           ' + beats(name, names[0], solves[name], solves[names[0]]))
         for name in adaptive_names:
