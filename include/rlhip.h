@@ -529,6 +529,32 @@ int rlh_fsai_create_adaptive(rlh_fsai_t *h, int dtype, int64_t n, const int64_t 
                              const void *values, int max_row, int levels, int steps, int step_size);
 /* the enrichment a handle was built with (0, 0: none) */
 int rlh_fsai_adaptive(rlh_fsai_t h, int *steps, int *step_size);
+/* ---- post-filtration by value: rlh_fsfilter_create and rlh_fsfilter_create_device make a handle of the same kind
+ *      (rlh_fsai_t: every rlh_fsai_* and rlh_fsapply_* call takes it); they build G as above, drop its small entries
+ *      and solve every row once more on what is left.
+ * Let G0 be the G, rounded to the dtype, that the forms above build for the same max_row, levels, steps
+ * and step_size (steps == 0: no enrichment, step_size is then ignored; otherwise both as for the _adaptive forms), and
+ * a_jj the real diagonal of A in double.  For row i and a stored column j < i the scaled size is
+ *   r_ij = |g0_ij| sqrt(a_jj) / (g0_ii sqrt(a_ii));
+ * the entry is kept iff r_ij >= drop, the diagonal always.  The decision is formed without a division or a square
+ * root, in double: |g0_ij|^2 * a_jj >= ((drop * drop) * (g0_ii * g0_ii)) * a_ii, with |z|^2 = fma(re, re, im * im).
+ * The final row i is the row of the forms above on the kept columns: the same local solve in double / complex double
+ * and the same single rounding at the store.  A principal sub-block of a positive definite block is positive definite,
+ * so the second solve cannot fail where the first did not.  One pass: filter once, solve once.
+ * Every decision reads row i of G0 and the diagonal of A only: nothing depends on scheduling, the filtered G is the same
+ * bits in every run, for both index widths, from host or device arrays and for both settings of RLH_FSAI_BINS (rows go
+ * to the bins of their NEW lengths for the second solve).  r_ij does not change under A -> D A D, D diagonal positive;
+ * with every d_i a power of two the whole build is exact: equal patterns and G' = G D^-1 bit for bit.
+ * drop must be finite with 0 < drop < 1.  nnz, longest_row, device_bytes, rlh_fsai_get, rlh_fsai_apply and a plan
+ * made from the handle describe the filtered G; truncated_rows keeps its meaning (what max_row held back before
+ * filtering); setup_seconds covers the whole build. */
+int rlh_fsfilter_create_device(rlh_fsai_t *h, int dtype, int64_t n, int index_bits, const void *d_indptr,
+                                    const void *d_indices, const void *d_values, int max_row, int levels, int steps,
+                                    int step_size, double drop);
+int rlh_fsfilter_create(rlh_fsai_t *h, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
+                             const void *values, int max_row, int levels, int steps, int step_size, double drop);
+/* the threshold a handle was filtered with and the entries that removed (0, 0: a handle of the other forms) */
+int rlh_fsfilter_info(rlh_fsai_t h, double *drop, int64_t *removed);
 /* Y = G^H (G X) for column-major DEVICE blocks of m vectors (leading dimensions >= n; Y may be X): two sparse
  * products (the kernels of rlh_spd_apply, bit-identical from call to call) through an n x m workspace of the handle,
  * which grows when a wider block than before arrives (that call synchronises the stream once); otherwise

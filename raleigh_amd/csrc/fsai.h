@@ -10,6 +10,8 @@ struct rlh_fsai {
   int64_t n = 0, nnz = 0, truncated = 0;
   int longest = 0, levels = 1, steps = 0, step_size = 0;
   double setup_seconds = 0;
+  double drop = 0;                  // post-filtration: the threshold (0: none) and the entries it removed
+  int64_t removed = 0;
   rlh_spd_t spd = nullptr;          // G and G^H with their partitions
   rlh::DevBuf<char> work;           // the n x m block between the two products
 };

@@ -32,6 +32,10 @@
 //                   workgroups fit the 160 KB of a CU.  Lane q owns column q and every sum runs over t in order, so
 //                   a row's bits do not depend on its bin.  The pattern is read from G's own column array;
 //                   S is gathered by a binary search for column P[q] in the sorted row P[p], p <= q.
+//   post-filtration (the rlh_fsfilter_* entry points only) fsai_filter<T>, 8 lanes per row: the entries of the computed G
+//                   that are small against drop in a scaling-invariant measure leave the row; the kept columns go to
+//                   a slab at the row's old offset, counts, keys and scans are made again, fsai_fill compacts and
+//                   fsai_setup solves every row once more in the bin of its new length.
 //   operators       G and G^H as the two orientations of one sparse data operator (rlh_spd_create_device), which
 //                   copies G's arrays; the build's own are scratch and released.
 // A row is one lane group's work from the gather to the store: no floating-point atomics, no order that depends on
@@ -64,6 +68,8 @@ struct FsaiStatus : BuildStatus {
   unsigned long long truncated;                // rows cut to max_row
   int longest;                                 // longest row of G
   unsigned long long limited;                  // adaptive build: rows max_row held back (those cut are among them)
+  unsigned long long removed;                  // post-filtration: entries of G dropped
+  int kept_longest;                            // post-filtration: longest row of the filtered G
 };
 
 __device__ __forceinline__ bool failed(const BuildStatus *st) { return *(const volatile unsigned long long *)&st->err != kNoError; }
@@ -554,6 +560,62 @@ __global__ __launch_bounds__(kBlock) void fsai_capacity(int64_t n, int max_row, 
     cap[i] = cnt[i] + grow < max_row ? cnt[i] + grow : max_row;
 }
 
+// ---------------------------------------------------------------- post-filtration by value
+constexpr int kFilterLanes = 8;                // lanes per row of fsai_filter: 32 rows per workgroup
+
+// the real diagonal of A in double (fsai_count saw it stored)
+template <typename T>
+__global__ __launch_bounds__(kBlock) void fsai_diagonal(int64_t n, const int64_t *__restrict__ ip, const int32_t *__restrict__ ix,
+                                                        const T *__restrict__ va, double *__restrict__ diag) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+    const int64_t ke = ip[i + 1], d = lower_bound_col(ix, ip[i], ke, i);
+    diag[i] = (d < ke && (int64_t)ix[d] == i) ? real_of(widen(va[d])) : 0.0;
+  }
+}
+
+// Row i of the computed G (k entries from gp[i] on, the diagonal last) by a group of kFilterLanes lanes: entry (i, j)
+// stays iff |g_ij|^2 a_jj >= drop^2 g_ii^2 a_ii -- drop2 = drop * drop, the right-hand side formed as (drop2 * (g_ii *
+// g_ii)) * a_ii, the left as |g_ij|^2 * a_jj, all in double, no division and no square root; the diagonal always stays.
+// The kept columns go to slab[gp[i] ..) in their order (ranks from the group's ballot), their number and the keys of its
+// bin to cnt, ka, kb.  The decision reads row i of G and the diagonal of A only.  The groups of a wave run different
+// trip counts: nothing but the ballot crosses lanes, and a group reads only its own bits of it.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void fsai_filter(int64_t n, double drop2, int four, const int64_t *__restrict__ gp,
+                                                      const int32_t *__restrict__ gi, const T *__restrict__ gv,
+                                                      const double *__restrict__ diag, int32_t *__restrict__ slab,
+                                                      int64_t *__restrict__ cnt, int64_t *__restrict__ ka,
+                                                      int64_t *__restrict__ kb, FsaiStatus *st) {
+  constexpr int kRows = kBlock / kFilterLanes;
+  const int lane = threadIdx.x % kFilterLanes;
+  const int base = (threadIdx.x & 63) - lane;          // the group's first lane within its wave
+  for (int64_t i = (int64_t)blockIdx.x * kRows + threadIdx.x / kFilterLanes; i < n; i += (int64_t)gridDim.x * kRows) {
+    const int64_t g0 = gp[i];
+    const int k = (int)(gp[i + 1] - g0);               // 1 <= k <= max_row
+    const double gii = k > 0 ? real_of(widen(gv[g0 + k - 1])) : 0.0;
+    const double bar = (drop2 * (gii * gii)) * diag[i];
+    int kept = 0;
+    for (int t0 = 0; t0 < k; t0 += kFilterLanes) {
+      const int t = t0 + lane;
+      bool keep = false;
+      int32_t c = 0;
+      if (t < k) {
+        c = gi[g0 + t];
+        keep = t == k - 1 || abs2_of(widen(gv[g0 + t])) * diag[c] >= bar;
+      }
+      const unsigned mine = (unsigned)(__ballot(keep) >> base) & ((1u << kFilterLanes) - 1);
+      if (keep) slab[g0 + kept + __popc(mine & ((1u << lane) - 1))] = c;
+      kept += __popc(mine);
+    }
+    if (lane == 0) {
+      cnt[i] = kept;
+      bin_keys(kept, four, &ka[i], &kb[i]);
+      if (kept < k) atomicAdd(&st->removed, (unsigned long long)(k - kept));
+      atomicMax(&st->kept_longest, kept);
+    }
+  }
+}
+
 // ---------------------------------------------------------------- the host side
 // RLH_FSAI_BINS=0: the two bins of 8 and 64 lanes per row
 int four_bins() {
@@ -561,12 +623,15 @@ int four_bins() {
   return (e && e[0] == '0' && e[1] == 0) ? 0 : 1;
 }
 
-// What a build is asked to do, made by the entry points.  adaptive: one of the _adaptive entry points, whose steps and
-// step_size are checked; the others leave both 0.  four: read from the environment by every create call.
+// What a build is asked to do, made by the entry points.  adaptive: steps and step_size are checked (the _adaptive entry
+// points, rlh_fsfilter_create* with steps != 0); the others leave both 0.  filtered: rlh_fsfilter_create*,
+// whose drop is checked; the others leave it 0.  four: read from the environment by every create call.
 struct FsaiPlan {
   int max_row, levels;
   bool adaptive;
   int steps, step_size;
+  double drop = 0.0;
+  bool filtered = false;
   int four = four_bins();
   int grow() const { return steps * step_size; }       // what enrichment can add to a row
 };
@@ -756,15 +821,47 @@ int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T 
   h->longest = hs.longest;
   DevBuf<T> gv;
   if (int rc = gv.alloc(gnnz)) return rc;
-  // ---- the rows, bin by bin
-  for_each_bin(bins, n, [&](auto lanes, int64_t count, const int32_t *list) {
-    constexpr int kLanes = decltype(lanes)::value;
-    launch_bin<T, kLanes>(fsai_setup<T, kLanes>, count, list, ip64, ix32, va, w.gp.get(), gi.get(), gv.get(), w.status.get());
-  });
-  RLH_HIP(hipGetLastError());
-  RLH_HIP(hipMemcpyAsync(&hs, w.status, sizeof hs, hipMemcpyDeviceToHost, st));
-  RLH_HIP(hipStreamSynchronize(st));
-  if (hs.err != kNoError) return report(name, hs, cap);
+  // ---- the rows, bin by bin (the pattern of w.gp and `columns`, the bins as they stand); the host waits and reports
+  auto solve_rows = [&](const int32_t *columns, T *values) -> int {
+    for_each_bin(bins, n, [&](auto lanes, int64_t count, const int32_t *list) {
+      constexpr int kLanes = decltype(lanes)::value;
+      launch_bin<T, kLanes>(fsai_setup<T, kLanes>, count, list, ip64, ix32, va, w.gp.get(), columns, values, w.status.get());
+    });
+    RLH_HIP(hipGetLastError());
+    RLH_HIP(hipMemcpyAsync(&hs, w.status, sizeof hs, hipMemcpyDeviceToHost, st));
+    RLH_HIP(hipStreamSynchronize(st));
+    return hs.err != kNoError ? report(name, hs, cap) : 0;
+  };
+  if (int rc = solve_rows(gi, gv)) return rc;
+  if (plan.drop > 0) {
+    // ---- post-filtration: the kept columns of every row go to a slab at the row's old offset; counts, keys and scans
+    // are made again, the slab is compacted (fsai_fill again) and every row is solved once more on what is left, in
+    // the bin of its new length.  A principal sub-block of a positive definite block is positive definite.
+    DevBuf<double> diag;
+    DevBuf<int32_t> kept_cols, gi_kept;
+    DevBuf<T> gv_kept;
+    if (int rc = diag.alloc(n)) return rc;
+    if (int rc = kept_cols.alloc(gnnz)) return rc;
+    hipLaunchKernelGGL(fsai_diagonal<T>, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, ip64, ix32, va, diag.get());
+    hipLaunchKernelGGL(fsai_filter<T>, dim3(blocks_for(n, kBlock / kFilterLanes, most)), blk, 0, st, n, plan.drop * plan.drop, four,
+                       (const int64_t *)w.gp, (const int32_t *)gi, (const T *)gv, (const double *)diag, kept_cols.get(),
+                       w.cnt.get(), w.ka.get(), w.kb.get(), w.status.get());
+    RLH_HIP(hipGetLastError());
+    DevBuf<int64_t> old_gp = std::move(w.gp);      // (where the rows lie in the slab; the scans write a new w.gp)
+    if (int rc = w.gp.alloc(n + 1)) return rc;
+    const int64_t before = gnnz;
+    if (int rc = pattern_totals(name, n, w, cap, n, before, &hs, &gnnz, &bins)) return rc;
+    RLH_REQUIRE((int64_t)hs.removed == before - gnnz, "%s: inconsistent row counts of the pattern", name);
+    if (int rc = gi_kept.alloc(gnnz)) return rc;
+    if (int rc = gv_kept.alloc(gnnz)) return rc;
+    hipLaunchKernelGGL(fsai_fill, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, kept_cols, old_gp, w.gp, gi_kept, bins);
+    if (int rc = solve_rows(gi_kept, gv_kept)) return rc;
+    gi = std::move(gi_kept);                       // (the stream is idle: nothing reads the unfiltered G any more)
+    gv = std::move(gv_kept);
+    h->nnz = gnnz;
+    h->longest = hs.kept_longest;
+    h->removed = (int64_t)hs.removed;
+  }
   // ---- G and G^H as one sparse data operator (it copies the arrays: 32-bit row pointers where they can hold nnz)
   int rc;
   DevBuf<int32_t> gp32;
@@ -814,6 +911,7 @@ int check_create_args(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, co
     RLH_REQUIRE(plan.step_size >= 1 && plan.step_size <= kMaxStepSize, "%s: step_size must lie in [1, %d], got %d", name,
                 kMaxStepSize, plan.step_size);
   }
+  if (plan.filtered) RLH_REQUIRE(plan.drop > 0.0 && plan.drop < 1.0, "%s: drop must lie in (0, 1), got %g", name, plan.drop);
   RLH_REQUIRE(indptr, "%s: null indptr", name);
   return 0;
 }
@@ -826,6 +924,7 @@ template <typename Build> int make_handle(rlh_fsai_t *ph, int dtype, int64_t n, 
   h->levels = plan.levels;
   h->steps = plan.steps;
   h->step_size = plan.step_size;
+  h->drop = plan.drop;
   if (int rc = n > 0 ? build(h) : 0) {
     rlh_fsai_destroy(h);
     return rc;
@@ -901,6 +1000,34 @@ extern "C" int rlh_fsai_create_adaptive_device(rlh_fsai_t *ph, int dtype, int64_
 extern "C" int rlh_fsai_create_adaptive(rlh_fsai_t *ph, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
                                         const void *values, int max_row, int levels, int steps, int step_size) {
   return create_host("rlh_fsai_create_adaptive", ph, dtype, n, indptr, indices, values, {max_row, levels, true, steps, step_size});
+}
+
+// steps == 0: no enrichment, step_size is not looked at
+static FsaiPlan filtered_plan(int max_row, int levels, int steps, int step_size, double drop) {
+  FsaiPlan plan{max_row, levels, steps != 0, steps, steps != 0 ? step_size : 0};
+  plan.drop = drop;
+  plan.filtered = true;
+  return plan;
+}
+
+extern "C" int rlh_fsfilter_create_device(rlh_fsai_t *ph, int dtype, int64_t n, int index_bits, const void *d_indptr,
+                                               const void *d_indices, const void *d_values, int max_row, int levels, int steps,
+                                               int step_size, double drop) {
+  return create_device("rlh_fsfilter_create_device", ph, dtype, n, index_bits, d_indptr, d_indices, d_values,
+                       filtered_plan(max_row, levels, steps, step_size, drop));
+}
+
+extern "C" int rlh_fsfilter_create(rlh_fsai_t *ph, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
+                                        const void *values, int max_row, int levels, int steps, int step_size, double drop) {
+  return create_host("rlh_fsfilter_create", ph, dtype, n, indptr, indices, values,
+                     filtered_plan(max_row, levels, steps, step_size, drop));
+}
+
+extern "C" int rlh_fsfilter_info(rlh_fsai_t h, double *drop, int64_t *removed) {
+  RLH_REQUIRE(h && drop && removed, "rlh_fsfilter_info: null handle or output");
+  *drop = h->drop;
+  *removed = h->removed;
+  return 0;
 }
 
 extern "C" int rlh_fsai_adaptive(rlh_fsai_t h, int *steps, int *step_size) {

@@ -45,7 +45,9 @@ def partial_hevp(A, B=None, T=None, buckling=False, sigma=0, which=6, tol=1e-4, 
     the further columns that lower its Kaporin functional most: a pattern chosen by value on the GPU, for matrices
     whose level patterns ``max_row`` cuts; ``work='native'``, ``'float32'`` or ``'bf16'`` applies it by its own two
     kernels with the block between the two products kept in the matrix type, float32 or bfloat16 -- the same
-    preconditioner up to the rounding of that block, a few iterations more or fewer), as `ChebyshevPreconditioner`
+    preconditioner up to the rounding of that block, a few iterations more or fewer; ``drop=`` removes the entries
+    of the computed G that are small in a scaling-invariant measure and solves every row again on what is left: a
+    cheaper application for a few more iterations), as `ChebyshevPreconditioner`
     is from the operator; an IncompleteLU preconditioner is a host factorisation and is set up from a SciPy matrix
     only.  A CPU tensor is taken as the SciPy matrix of its arrays (ndarrays come back).
 

@@ -20,13 +20,18 @@
                application, W = G X kept in the matrix type, float32 or bfloat16), application and solve timed in the same
                run against the same build with work=None: "beats", "loses to" or "no winner" per line
 
+  drop         --drop 0.01,0.02,...: every --levels and --adaptive build once more with each `drop` (post-filtration of the
+               computed G by value, every row solved again on what is left), set-up, application and solve timed in the
+               same run against the unfiltered build of the same pattern arguments -- and, with --work, each filtered
+               build's plan against the unfiltered build's plan of the same work form
+
 Every timing is repeated --repeats times and reported as fastest .. slowest; "A beats B" means A's slowest repeat is
 faster than B's fastest, anything else is "no winner".  Nothing here is a threshold.  --setup-only stops after the
 set-up lines (for comparing two builds of the library on one machine).
 
     python tools/approx_inverse_bench.py [--out profiles/r11_approx_inverse_levels.txt] [--levels 1,2,3]
-                                         [--adaptive 1:4:4,1:4:8,2:2:4] [--work native,float32,bf16] [--m 16] [--calls 20]
-                                         [--repeats 5] [--setup-only]
+                                         [--adaptive 1:4:4,1:4:8,2:2:4] [--work native,float32,bf16] [--drop 0.01,0.02,0.05]
+                                         [--m 16] [--calls 20] [--repeats 5] [--setup-only]
 """
 import argparse
 import ctypes
@@ -54,6 +59,7 @@ def main():
     ap.add_argument('--levels', default='1,2,3', help='levels of fill of ApproximateInverse, comma separated')
     ap.add_argument('--adaptive', default='', help='adaptive patterns as LEVELS:STEPS:SIZE, comma separated')
     ap.add_argument('--work', default='', help="work forms of the application ('native', 'float32', 'bf16'), comma separated")
+    ap.add_argument('--drop', default='', help='post-filtration thresholds in (0, 1), comma separated')
     ap.add_argument('--setup-only', action='store_true', help='set-up timings only')
     ap.add_argument('--m', type=int, default=16)
     ap.add_argument('--calls', type=int, default=20)
@@ -65,6 +71,7 @@ def main():
     adaptive = [tuple(int(v) for v in spec.split(':')) for spec in args.adaptive.split(',') if spec]
     assert all(len(spec) == 3 for spec in adaptive), '--adaptive takes LEVELS:STEPS:SIZE'
     works = [w for w in args.work.split(',') if w]
+    drops = [float(v) for v in args.drop.split(',') if v]
     import torch
     import scipy.sparse as sp
     from raleigh_amd import _lib
@@ -121,6 +128,13 @@ def main():
         names = level_names + adaptive_names
         kwargs = [dict(levels=lv) if lv != 1 else {} for lv in levels]
         kwargs += [dict(levels=lv, steps=steps, step_size=size) for lv, steps, size in adaptive]
+        plain_names = list(names)
+        drop_names = []                                     # (name with drop, name of the unfiltered build)
+        for kw, name in list(zip(kwargs, names)):
+            for d in drops:
+                kwargs.append(dict(kw, drop=d))
+                names.append('%s drop=%g' % (name, d))
+                drop_names.append((names[-1], name))
         Ts, walls, devs = {}, {}, {}
         for kw, name in zip(kwargs, names):
             dev_s, wall_s = [], []
@@ -134,8 +148,11 @@ def main():
                 dev_s.append(T.setup_seconds)
             Ts[name], walls[name], devs[name] = T, wall_s, dev_s
             say('   set-up  %-29s device %s s, host wall %s s; nnz(G) = %d (%.1f per row, fill %.2f, longest row %d, '
-                '%d rows cut), %.1f MB held' % (name, span(dev_s, fmt='%.4f'), span(wall_s, fmt='%.4f'), T.nnz, T.nnz / n, T.fill,
-                                                T.longest_row, T.truncated_rows, T.device_bytes() / 1e6))
+                '%d rows cut%s), %.1f MB held' % (name, span(dev_s, fmt='%.4f'), span(wall_s, fmt='%.4f'), T.nnz, T.nnz / n, T.fill,
+                                                  T.longest_row, T.truncated_rows,
+                                                  ', %d entries dropped' % T.dropped_entries if T.drop else '', T.device_bytes() / 1e6))
+        for dname, name in drop_names:
+            say('           ' + verdict(dname, name, devs[dname], devs[name]) + ' [set-up, device]')
         for (lv, steps, size), name in zip(adaptive, adaptive_names):
             if lv in levels:
                 plain = min(devs[level_names[levels.index(lv)]])
@@ -164,7 +181,7 @@ def main():
             ilu_s.append(time.perf_counter() - t0)
         say('   set-up  IncompleteLU.factorize        host wall %s s; fill %.2f, levels %s'
             % (span(ilu_s, fmt='%.4f'), ilu.fill, ilu.levels))
-        for name in names:
+        for name in plain_names:
             say('           ' + beats(name, 'IncompleteLU', walls[name], ilu_s))
         # ---- application
         B, X = Vectors(n, m), Vectors(n, m)
@@ -187,10 +204,15 @@ def main():
         for name, op, nb in ops:
             say('   apply   %-42s %s ms per call; %.1f MB algorithmic -> %.0f GB/s at the fastest'
                 % (name, span(times[name], fmt='%.4f'), nb / 1e6, nb / min(times[name]) / 1e6))
-        for name in names:
+        for name in plain_names:
             say('           ' + beats(name, 'IncompleteLU', times[name], times['IncompleteLU']))
         for wname, name in work_names:
             say('           ' + verdict(wname, name, times[wname], times[name]))
+        # a filtered build against the unfiltered build of the same pattern arguments, for each form of the application
+        filtered_pairs = list(drop_names) + [('%s work=%s' % (dname, w), '%s work=%s' % (name, w)) for dname, name in drop_names
+                                             for w in works]
+        for dname, name in filtered_pairs:
+            say('           ' + verdict(dname, name, times[dname], times[name]))
         # ---- solve
         solves = {}
         for name, prec in ([(name, Ts[name]) for name in names + [wn for wn, _ in work_names]]
@@ -209,11 +231,13 @@ def main():
             solves[name] = ts
             say('   solve   T = %-42s %s s, %d iterations, status %d, smallest eigenvalue %.10g'
                 % (name, span(ts, fmt='%.4f'), its, status, lmd[0] if lmd is not None and len(lmd) else float('nan')))
-        for name in names:
+        for name in plain_names:
             say('           ' + beats(name, 'IncompleteLU', solves[name], solves['IncompleteLU']))
             say('           ' + beats(name, 'no preconditioner', solves[name], solves['True (none)']))
         for wname, name in work_names:
             say('           ' + verdict(wname, name, solves[wname], solves[name]))
+        for dname, name in filtered_pairs:
+            say('           ' + verdict(dname, name, solves[dname], solves[name]))
         for name in level_names[1:]:
             say('           ' + beats(name, names[0], solves[name], solves[names[0]]))
         for name in adaptive_names:
