@@ -375,7 +375,13 @@ int rlh_shm_destroy(rlh_shm_t s);
  * A: DEVICE, M x N, row-major (order 0, numpy C_CONTIGUOUS, lda >= N) or
  * column-major (order 1, F_CONTIGUOUS, lda >= M).
  * transp 0: Y[:, j] = A   * X[:, j]   (X: N rows, Y: M rows)
- * transp 1: Y[:, j] = A^H * X[:, j]   (X: M rows, Y: N rows) */
+ * transp 1: Y[:, j] = A^H * X[:, j]   (X: M rows, Y: N rows)
+ * What is read.  A as stored is R lines of len elements, lda apart (row-major: R = M, len = N; column-major: R = N,
+ * len = M).  The library reads (R - 1) * lda + len elements from A, where the matrix-core kernels (A and X 16-byte
+ * aligned, lda and ldx multiples of 16 bytes) round len up to a multiple of 16 bytes, never beyond lda; of a vector of
+ * X likewise its rows rounded up to 16 bytes, never beyond ldx.  What is read past len reaches no result.  So A may be a
+ * window of a wider parent (A + j0 with the parent's lda): with j0 * element size a multiple of 16 bytes the rounded
+ * window ends inside the parent's line, because j0, lda and the rounded len are all multiples of the 16-byte unit. */
 int rlh_dense_apply(int dtype, int64_t M, int64_t N, const void *A, int64_t lda,
                     int order, int transp, int64_t m, const void *X,
                     int64_t ldx, void *Y, int64_t ldy);

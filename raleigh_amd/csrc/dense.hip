@@ -31,6 +31,10 @@ struct DenseArgs {
   // store / the split-K reduction: the mean-shift corrections of the PCA operator
   // (raleigh/interfaces/partial_svd.py:258-291) without a further pass over the block
   const void *r1_u, *r1_c;
+  // read limits of the 16-byte pieces of the matrix-core kernels, in elements along the contiguous direction:
+  // min(ld, extent rounded up to a piece).  A piece that would end past the limit is re-read at 0 (every element of
+  // it lies past the K range or the rows stored), so a window of a wider parent is never read past its rounded extent
+  int64_t alim, xlim;
 };
 
 // y - u c for the element types (real: plain product; complex: u[i] * c[v], no conjugation)
@@ -92,7 +96,7 @@ __global__ __launch_bounds__(256) void dense_mfma_f32_kernel(DenseArgs a, float 
         int64_t i = i0 + r;
         i = i < a.ny ? i : a.ny - 1;                 // clamped rows are computed but never stored
         int64_t k = k0 + kq;
-        const int64_t kc = (k + 3 < a.lda) ? k : 0;
+        const int64_t kc = (k + 3 < a.alim) ? k : 0;
         v = *(const float4 *)(A + i * a.lda + kc);
         if (tail) {
           if (k + 0 >= kend) v.x = 0.f;
@@ -103,7 +107,7 @@ __global__ __launch_bounds__(256) void dense_mfma_f32_kernel(DenseArgs a, float 
       } else {                     // unit = 4 consecutive output rows at one k
         const int kk = u / (MR / 4), rq = (u % (MR / 4)) * 4;
         int64_t i = i0 + rq;
-        i = (i + 3 < a.lda) ? i : 0;
+        i = (i + 3 < a.alim) ? i : 0;
         const int64_t k = k0 + kk;
         const int64_t kc = k < kend ? k : kbeg;
         v = *(const float4 *)(A + kc * a.lda + i);
@@ -118,7 +122,7 @@ __global__ __launch_bounds__(256) void dense_mfma_f32_kernel(DenseArgs a, float 
       int vc = v0 + c;
       vc = vc < a.m ? vc : a.m - 1;
       const int64_t k = k0 + kq;
-      const int64_t kc = (k + 3 < a.ldx) ? k : 0;
+      const int64_t kc = (k + 3 < a.xlim) ? k : 0;
       float4 v = *(const float4 *)(X + (int64_t)vc * a.ldx + kc);
       if (tail) {
         if (k + 0 >= kend) v.x = 0.f;
@@ -274,7 +278,7 @@ __global__ __launch_bounds__(256, (BK == 16 ? 3 : 2)) void dense_mfma2_f32_kerne
         int64_t i = i0 + r;
         i = i < a.ny ? i : a.ny - 1;                 // clamped rows are computed but never stored
         const int64_t k = k0 + kq;
-        f4 v = *(const f4 *)(A + i * a.lda + ((!tail || k + 3 < a.lda) ? k : 0));
+        f4 v = *(const f4 *)(A + i * a.lda + ((!tail || k + 3 < a.alim) ? k : 0));
         if (tail) {
           if (k + 0 >= kend) v[0] = 0.f;
           if (k + 1 >= kend) v[1] = 0.f;
@@ -289,7 +293,7 @@ __global__ __launch_bounds__(256, (BK == 16 ? 3 : 2)) void dense_mfma2_f32_kerne
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         int64_t i = i0 + rq;
-        i = (i + 3 < a.lda) ? i : 0;
+        i = (i + 3 < a.alim) ? i : 0;
         const int64_t k = k0 + kq + q;
         f4 v = *(const f4 *)(A + ((!tail || k < kend) ? k : kbeg) * a.lda + i);
         if (tail && k >= kend) v = f4{0.f, 0.f, 0.f, 0.f};
@@ -303,7 +307,7 @@ __global__ __launch_bounds__(256, (BK == 16 ? 3 : 2)) void dense_mfma2_f32_kerne
       int vc = v0 + c;
       vc = vc < a.m ? vc : a.m - 1;
       const int64_t k = k0 + kq;
-      f4 v = *(const f4 *)(X + (int64_t)vc * a.ldx + ((!tail || k + 3 < a.ldx) ? k : 0));
+      f4 v = *(const f4 *)(X + (int64_t)vc * a.ldx + ((!tail || k + 3 < a.xlim) ? k : 0));
       if (tail) {
         if (k + 0 >= kend) v[0] = 0.f;
         if (k + 1 >= kend) v[1] = 0.f;
@@ -543,7 +547,7 @@ __global__ __launch_bounds__(256, 2) void dense_mfma16_kernel(DenseArgs a, T *__
         int64_t i = i0 + r;
         i = i < a.ny ? i : a.ny - 1;                // clamped rows are computed but never stored
         const int64_t k = k0 + kq;
-        const int64_t kc = (!MASK || k + EPU <= a.lda) ? k : 0;
+        const int64_t kc = (!MASK || k + EPU <= a.alim) ? k : 0;
         ra[q] = *reinterpret_cast<const Unit *>(A + i * a.lda + kc);
         if constexpr (MASK) {
 #pragma unroll
@@ -553,7 +557,7 @@ __global__ __launch_bounds__(256, 2) void dense_mfma16_kernel(DenseArgs a, T *__
       } else {                                      // EPU consecutive output rows at one k
         const int kk = u / (MR / EPU), rq = (u % (MR / EPU)) * EPU;
         int64_t i = i0 + rq;
-        i = (i + EPU <= a.lda) ? i : 0;
+        i = (i + EPU <= a.alim) ? i : 0;
         const int64_t k = k0 + kk;
         const int64_t kc = (!MASK || k < kend) ? k : 0;
         ra[q] = *reinterpret_cast<const Unit *>(A + kc * a.lda + i);
@@ -567,7 +571,7 @@ __global__ __launch_bounds__(256, 2) void dense_mfma16_kernel(DenseArgs a, T *__
       int vc = v0 + c;
       vc = vc < a.m ? vc : a.m - 1;
       const int64_t k = k0 + kq;
-      const int64_t kc = (!MASK || k + EPU <= a.ldx) ? k : 0;
+      const int64_t kc = (!MASK || k + EPU <= a.xlim) ? k : 0;
       rb[q] = *reinterpret_cast<const Unit *>(X + (int64_t)vc * a.ldx + kc);
       if constexpr (MASK) {
 #pragma unroll
@@ -921,6 +925,10 @@ extern "C" int rlh_dense_apply_r1(int dtype, int64_t M, int64_t N, const void *A
   a.conj_a = (transp == 1 && (dtype == RLH_C || dtype == RLH_Z)) ? 1 : 0;
   a.ny = ny; a.nx = nx; a.X = X; a.ldx = ldx; a.Y = Y; a.ldy = ldy; a.m = (int)m;
   a.r1_u = d_u; a.r1_c = d_c;
+  const int64_t epu = 16 / (int64_t)dtype_size(dtype), alen = a.a_kcontig ? nx : ny;
+  const int64_t aup = (alen + epu - 1) / epu * epu, xup = (nx + epu - 1) / epu * epu;
+  a.alim = aup < lda ? aup : lda;
+  a.xlim = xup < ldx ? xup : ldx;
   switch (dtype) {
     case RLH_S: return dense_impl<RLH_S>(a);
     case RLH_D: return dense_impl<RLH_D>(a);
