@@ -599,6 +599,45 @@ int rlh_fsapply_run(rlh_fsapply_t p, int64_t m, const void *X, int64_t ldx, void
 int rlh_fsapply_info(rlh_fsapply_t p, int *work, int64_t *stored_slots, int64_t *tail_entries, int64_t *device_bytes);
 int rlh_fsapply_destroy(rlh_fsapply_t p);
 
+/* ---- the same application on a ROW SHARD of G: rank r owns the rows [r0, r1) of the vectors, G_loc = the rows
+ *      [r0, r1) of G and GH_loc = the rows [r0, r1) of G^H (the own COLUMNS of G, values conjugated by the caller).
+ * rlh_fsshard_create: HOST CSR arrays of the two matrices, n_own rows each.  A column c of G_loc is own row c for
+ * c < n_own and row c - n_own of the x-halo block (n_xhalo rows, of lower ranks) otherwise; the columns of GH_loc
+ * number the rows of W the same way (n_whalo halo rows, of higher ranks).  The entries of a row are multiplied in
+ * the order given.  dtype, work, the rounding of the values to V, the layout, its memory condition (with the entries
+ * of G_loc and GH_loc) and the checking pass are those of rlh_fsapply_create; null pointers, negative sizes, an indptr
+ * that does not start at 0 or decreases, and a column outside [0, n_own + halo rows) return non-zero, a message that
+ * names the entry point, and a null plan.  n_own = 0 gives a valid empty plan.
+ * One application is
+ *   rlh_fsshard_first   W[own rows] = G_loc [X ; XH]: X the own rows (column-major DEVICE block, ldx >= n_own), XH the
+ *                       x-halo block (ldxh >= n_xhalo; may be null iff n_xhalo == 0); a halo row that no entry
+ *                       references is never read.  Starts a new application: the count of placed halo rows is reset.
+ *   rlh_fsshard_pack    out[tile][i][8] = W[tile][d_idx[i]][8], i < nidx: the rows of W a peer needs, whole 16-byte
+ *                       pieces; d_idx: DEVICE int64 (as for rlh_gather_rows), every index in [0, n_own) -- the
+ *                       caller's contract (the indices are in device memory; an index outside is not followed, its
+ *                       row arrives as zeros); out: ((m + 7) / 8) * nidx * w_row_bytes bytes.
+ *   rlh_fsshard_halo    places a received packed block [tile][count][8] into the halo rows first .. first + count of
+ *                       W; the plan counts the rows placed since the last rlh_fsshard_first.
+ *   rlh_fsshard_second  Y[own rows] = GH_loc W over all n_own + n_whalo rows of W (ldy >= n_own; Y may be X).  Refused
+ *                       when no rlh_fsshard_first with the same m came before or fewer than n_whalo halo rows have
+ *                       been placed ("halo rows missing"): a forgotten exchange is a message, not a read of
+ *                       undefined memory.
+ * All four are asynchronous on the library stream (rlh_fsshard_first synchronises once when W grows); the order of
+ * every sum is fixed by the layout, as for rlh_fsapply_run.
+ * rlh_fsshard_info: as rlh_fsapply_info, and the bytes of one row of W in a tile, w_row_bytes = 8 * sizeof(Wt)
+ * (16, 32, 64 or 128): what a row costs in a message. */
+typedef struct rlh_fsshard *rlh_fsshard_t;
+int rlh_fsshard_create(rlh_fsshard_t *p, int dtype, int work, int64_t n_own, int64_t n_xhalo, int64_t n_whalo,
+                       const int64_t *g_indptr, const int32_t *g_indices, const void *g_values,
+                       const int64_t *gh_indptr, const int32_t *gh_indices, const void *gh_values);
+int rlh_fsshard_first(rlh_fsshard_t p, int64_t m, const void *X, int64_t ldx, const void *XH, int64_t ldxh);
+int rlh_fsshard_pack(rlh_fsshard_t p, int64_t m, int64_t nidx, const int64_t *d_idx, void *out);
+int rlh_fsshard_halo(rlh_fsshard_t p, int64_t m, int64_t first, int64_t count, const void *src);
+int rlh_fsshard_second(rlh_fsshard_t p, int64_t m, void *Y, int64_t ldy);
+int rlh_fsshard_info(rlh_fsshard_t p, int *work, int64_t *stored_slots, int64_t *tail_entries, int64_t *device_bytes,
+                     int64_t *w_row_bytes);
+int rlh_fsshard_destroy(rlh_fsshard_t p);
+
 /* ---- profiling aid: HIP-event time of the last `count` kernels ---- */
 int rlh_timer_start(void);
 int rlh_timer_stop(float *milliseconds);

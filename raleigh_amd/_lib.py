@@ -138,6 +138,14 @@ SIGNATURES = {
     'rlh_fsapply_run': [_p, _i64, _p, _i64, _p, _i64],
     'rlh_fsapply_info': [_p, ctypes.POINTER(_int), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
     'rlh_fsapply_destroy': [_p],
+    'rlh_fsshard_create': [ctypes.POINTER(_p), _int, _int, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p],
+    'rlh_fsshard_first': [_p, _i64, _p, _i64, _p, _i64],
+    'rlh_fsshard_pack': [_p, _i64, _i64, _p, _p],
+    'rlh_fsshard_halo': [_p, _i64, _i64, _i64, _p],
+    'rlh_fsshard_second': [_p, _i64, _p, _i64],
+    'rlh_fsshard_info': [_p, ctypes.POINTER(_int), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                         ctypes.POINTER(_i64)],
+    'rlh_fsshard_destroy': [_p],
     'rlh_timer_start': [],
     'rlh_timer_stop': [ctypes.POINTER(ctypes.c_float)],
 }

@@ -612,6 +612,308 @@ class ShardedSparseMatrix:
         self._op.cheb_step_ptr(y.nvec(), y, p, b, cy, cp, cb, halo_ptr, ldh, part=2)
 
 
+class ShardedApproximateInverse:
+    """The factorised sparse approximate inverse T = G^H G (precond.ApproximateInverse) for row-sharded blocks: rank r,
+    owner of the rows [r0, r1), builds and keeps the rows [r0, r1) of G and the rows [r0, r1) of G^H (its own COLUMNS
+    of G), and applies T by the two kernels of the library's plan for a shard (rlh_fsshard_*).
+
+    The two constructors take what those of ShardedSparseMatrix take: the same global SciPy matrix on every rank
+    (upper triangle significant), or with ``from_local_rows`` this rank's rows of the full matrix with global columns.
+    max_row, levels, steps, step_size and drop are the arguments of ApproximateInverse; work is 'native', 'float32' or
+    'bf16' as there (there is no None: the sharded form has only the plan).
+
+    Set-up (host SciPy, the device builder, object collectives -- nothing of it runs per application).  With H the
+    global columns below r0 that the rank's rows of A store and E = H + [r0, r1) ascending, the rank runs
+    ApproximateInverse on A[E, E] and keeps the last r1 - r0 rows; the rows H of A come from their owners.  At
+    ``levels=1, steps=0`` (any drop) every pattern lies inside E, and the rows are those of the single-GPU G bit for
+    bit.  With more levels or enrichment steps the pattern is the one the builder finds INSIDE A[E, E]: G is still
+    lower triangular with a positive diagonal, every row the Kaporin minimiser on its pattern, T Hermitian positive
+    definite -- but the pattern depends on the partition (level patterns that reach through deeper halos are not
+    built).  The entries g_ij whose column j belongs to a lower rank are sent to that rank once.
+
+    Application, ``apply(x, y)`` on ShardedVectors (y may be x): the rows of x that G's rows reference on lower ranks
+    are packed, exchanged and assembled into a halo block; W = G_loc [x ; x_halo]; the rows of W that higher ranks'
+    entries reference are packed from the plan, exchanged (in the type of W: bfloat16 halves the float32 bytes) and
+    placed behind the own rows; y = GH_loc W.  Both products gather: nothing is scatter-added, the order of every sum
+    is fixed.  Neither exchange is overlapped with rows that do not need it.
+
+    With one rank and forced collectives the shard is cut into two virtual ranks at the row where ShardedSparseMatrix
+    cuts it: G is the single-GPU one, the columns below the cut are x-halo columns for the rows from the cut on, the
+    columns from the cut on W-halo columns for the rows of G^H below it, and both exchanges run as sends to self.
+
+    nnz, longest_row and fill are global (one all-reduce at set-up); dropped_entries covers this rank's rows;
+    setup_seconds is the host wall time of the whole set-up on this rank."""
+
+    WORK = {'native': 0, 'float32': 1, 'bf16': 2}
+
+    def __init__(self, matrix, comm, offsets=None, max_row=64, levels=1, steps=0, step_size=1, work='native', drop=0.0):
+        self._plan = None
+        self._check_work(work, matrix.dtype)
+        full = full_from_upper(matrix)
+        n = full.shape[0]
+        off = partition(n, comm.size) if offsets is None else offsets
+        r0, r1 = int(off[comm.rank]), int(off[comm.rank + 1])
+        self._setup(scs.csr_matrix(full[r0:r1, :]), r0, n, comm, off, lambda ids: scs.csr_matrix(full[ids, :]),
+                    dict(max_row=max_row, levels=levels, steps=steps, step_size=step_size, drop=drop), work)
+
+    @classmethod
+    def from_local_rows(cls, rows, row0, n, comm, offsets, max_row=64, levels=1, steps=0, step_size=1, work='native',
+                        drop=0.0):
+        """From this rank's rows [row0, row0 + rows.shape[0]) of the FULL (both triangles) matrix with global column
+        indices; the rows of lower ranks that the build needs come from their owners."""
+        self = cls.__new__(cls)
+        self._plan = None
+        rows = scs.csr_matrix(rows)
+        self._check_work(work, rows.dtype)
+        assert rows.shape[1] == n and row0 == int(offsets[comm.rank])
+
+        def rows_of(ids):
+            # two rounds of object collectives: who needs which rows, then the rows themselves
+            owner = np.searchsorted(offsets, ids, side='right') - 1
+            ask = {int(p): ids[owner == p] for p in np.unique(owner)}
+            asks, reply = [None] * comm.size, {}
+            comm.dist.all_gather_object(asks, ask, group=comm.group)
+            for q in range(comm.size):
+                if asks[q] and comm.rank in asks[q]:
+                    sub = scs.csr_matrix(rows[asks[q][comm.rank] - row0, :])
+                    reply[q] = (sub.indptr, sub.indices, sub.data)
+            replies = [None] * comm.size
+            comm.dist.all_gather_object(replies, reply, group=comm.group)
+            parts = []
+            for p in sorted(ask):                              # ascending owner: ascending rows
+                ip, ix, va = replies[p][comm.rank]
+                parts.append(scs.csr_matrix((va, ix, ip), shape=(len(ask[p]), n)))
+            return scs.vstack(parts, format='csr') if parts else scs.csr_matrix((0, n), dtype=rows.dtype)
+        self._setup(rows, row0, n, comm, offsets, rows_of,
+                    dict(max_row=max_row, levels=levels, steps=steps, step_size=step_size, drop=drop), work)
+        return self
+
+    @classmethod
+    def _check_work(cls, work, dtype):
+        if work not in cls.WORK:
+            raise ValueError("work must be 'native', 'float32' or 'bf16', got %r" % (work,))
+        if work == 'bf16' and np.dtype(dtype).kind == 'c':
+            raise ValueError("work='bf16' is for real matrices only")
+
+    def _setup(self, loc, r0, n, comm, off, rows_of, build, work):
+        import time
+        from .precond import ApproximateInverse
+        t_start = time.perf_counter()
+        L = self._L = _lib.lib()
+        self._comm, self._n, self._offsets, self.work = comm, n, off, work
+        self._dtype = loc.data.dtype.type
+        loc.sort_indices()
+        r1 = r0 + loc.shape[0]
+        assert r1 == int(off[comm.rank + 1])
+        n_own = self._n_own = r1 - r0
+        self._r0 = r0
+        # ---- the own rows of G: the builder on A[E, E]
+        cols = loc.indices.astype(np.int64)
+        below = np.unique(cols[cols < r0])
+        lower_rows = rows_of(below)
+        if below.size:
+            ext_ids = np.concatenate([below, np.arange(r0, r1, dtype=np.int64)])
+            a_ext = scs.csr_matrix(scs.vstack([lower_rows, loc], format='csc')[:, ext_ids])
+        else:
+            ext_ids = np.arange(r0, r1, dtype=np.int64)
+            a_ext = scs.csr_matrix(loc[:, r0:r1])
+        a_ext.sort_indices()
+        T = ApproximateInverse(a_ext, work=None, **build)
+        self.levels, self.steps, self.step_size, self.drop = T.levels, T.steps, T.step_size, T.drop
+        g_own = scs.csr_matrix(T.csr()[below.size:, :])
+        dropped = T.dropped_entries
+        del T
+        if self.drop and below.size:                           # the builder's count includes the rows of lower ranks
+            if self.levels == 1 and self.steps == 0:           # (the unfiltered pattern is known: the stored columns j <= i)
+                rows_a = np.repeat(np.arange(r0, r1, dtype=np.int64), np.diff(loc.indptr))
+                lower = np.bincount(rows_a[cols <= rows_a] - r0, minlength=n_own)
+                dropped = int(np.minimum(lower, int(build['max_row'])).sum()) - int(g_own.nnz)
+            else:                                              # (it is not: the same build unfiltered, for its row lengths)
+                plain = ApproximateInverse(a_ext, work=None, **dict(build, drop=0.0))
+                dropped = int(plain.csr()[below.size:, :].nnz) - int(g_own.nnz)
+                del plain
+        self.dropped_entries = int(dropped)
+        gp = g_own.indptr.astype(np.int64)
+        gi = ext_ids[g_own.indices] if g_own.nnz else np.zeros(0, dtype=np.int64)           # global columns, ascending
+        gv = np.ascontiguousarray(g_own.data, dtype=self._dtype)
+        self._g = (gp, gi, gv)
+        grow = np.repeat(np.arange(r0, r1, dtype=np.int64), np.diff(gp))
+        forced = comm.size == 1 and comm.force
+        cut = r0 + (((r1 - r0) // 2) // 8) * 8                # (the two virtual ranks of ShardedSparseMatrix._setup)
+        own = ((gi >= cut) == (grow >= cut)) if forced else (gi >= r0)
+        x_ids = np.unique(gi[~own])
+        g_idx = np.where(own, gi - r0, n_own + np.searchsorted(x_ids, gi)).astype(np.int32)
+        # ---- the own columns of G: what this rank holds, and what the higher ranks computed
+        owner = np.searchsorted(off, gi, side='right') - 1
+        away = owner != comm.rank
+        out = {int(p): (grow[owner == p], gi[owner == p], gv[owner == p]) for p in np.unique(owner[away])}
+        everyone = [None] * comm.size
+        comm.dist.all_gather_object(everyone, out, group=comm.group)
+        parts = [(grow[~away], gi[~away], gv[~away])] + [everyone[q][comm.rank] for q in range(comm.rank + 1, comm.size)
+                                                         if everyone[q] and comm.rank in everyone[q]]
+        hi = np.concatenate([p[0] for p in parts]).astype(np.int64)         # row of G = column of G^H
+        hj = np.concatenate([p[1] for p in parts]).astype(np.int64)         # own column of G = row of G^H
+        hv = np.conj(np.concatenate([p[2] for p in parts])).astype(self._dtype)
+        order = np.lexsort((hi, hj))
+        hi, hj, hv = hi[order], hj[order], np.ascontiguousarray(hv[order])
+        hp = np.zeros(n_own + 1, dtype=np.int64)
+        np.cumsum(np.bincount(hj - r0, minlength=n_own), out=hp[1:])
+        own = ((hi >= cut) == (hj >= cut)) if forced else (hi < r1)
+        w_ids = np.unique(hi[~own])
+        h_idx = np.where(own, hi - r0, n_own + np.searchsorted(w_ids, hi)).astype(np.int32)
+        self._n_xhalo, self._n_whalo = int(x_ids.size), int(w_ids.size)
+        self._nnz_loc = (int(gi.size), int(hi.size))
+        # ---- the plan and the two exchanges
+        plan = ctypes.c_void_p()
+        _lib.check(L.rlh_fsshard_create(ctypes.byref(plan), _lib.DTYPE_CODE[self._dtype], self.WORK[work], n_own, self._n_xhalo,
+                                        self._n_whalo, _lib.host_ptr(gp), _lib.host_ptr(g_idx), _lib.host_ptr(gv),
+                                        _lib.host_ptr(hp), _lib.host_ptr(h_idx), _lib.host_ptr(hv)))
+        self._plan = plan
+        wrb = ctypes.c_int64()
+        _lib.check(L.rlh_fsshard_info(plan, None, None, None, None, ctypes.byref(wrb)))
+        self._w_row_bytes = int(wrb.value)
+        self._x_recv, self._x_send = self._exchange_plan(x_ids)
+        self._w_recv, self._w_send = self._exchange_plan(w_ids)
+        self._bufs = {}
+        # ---- what describes the whole of G: one all-reduce (a slot per rank carries its longest row)
+        tt = comm.torch
+        t = np.zeros(2 + comm.size, dtype=np.int64)
+        t[0], t[1] = gi.size, loc.nnz
+        t[2 + comm.rank] = int(np.diff(gp).max()) if n_own else 0
+        t = tt.from_numpy(t).to(comm.device)
+        comm.dist.all_reduce(t, group=comm.group)
+        t = t.cpu().numpy()
+        self.nnz, self.longest_row = int(t[0]), int(t[2:].max())
+        self.fill = self.nnz / float(max(int(t[1]), 1))
+        self.setup_seconds = time.perf_counter() - t_start
+
+    def _exchange_plan(self, ids):
+        """For the halo rows `ids` (global, ascending: grouped by owner): the receive runs (peer, first halo row, count)
+        and, from what the peers ask of this rank, the sends (peer, device index list of own rows, count)."""
+        comm, off = self._comm, self._offsets
+        owner = np.searchsorted(off, ids, side='right') - 1
+        recv = []
+        for p in range(comm.size):
+            idx = np.nonzero(owner == p)[0]
+            if idx.size:
+                recv.append((p, int(idx[0]), int(idx.size)))
+        mine = {p: (ids[s:s + c] - off[p]).astype(np.int64) for p, s, c in recv}
+        wants = [None] * comm.size
+        comm.dist.all_gather_object(wants, mine, group=comm.group)
+        send = []
+        for p in range(comm.size):
+            if (p != comm.rank or comm.force) and wants[p] and comm.rank in wants[p]:
+                idx = np.ascontiguousarray(wants[p][comm.rank])
+                assert idx.size == 0 or (idx.min() >= 0 and idx.max() < self._n_own)
+                dbuf = comm.buffer(idx.nbytes)
+                dbuf.copy_(comm.torch.from_numpy(idx.view(np.uint8)))
+                send.append((p, dbuf, int(idx.size)))
+        return recv, send
+
+    def __del__(self):
+        plan, self._plan = getattr(self, '_plan', None), None
+        if plan:
+            try:
+                self._L.rlh_fsshard_destroy(plan)
+            except Exception:
+                pass
+
+    def size(self):
+        return self._n
+
+    def data_type(self):
+        return np.dtype(self._dtype)
+
+    def halo_rows(self):
+        """(rows of x received from lower ranks, rows of W received from higher ranks) per application."""
+        return self._n_xhalo, self._n_whalo
+
+    def csr(self):
+        """This rank's rows of G with global columns, as a SciPy CSR matrix of n_own x n."""
+        gp, gi, gv = self._g
+        return scs.csr_matrix((gv, gi.astype(np.int32), gp), shape=(self._n_own, self._n))
+
+    def device_bytes(self):
+        """Device memory the plan holds on this rank: the two layouts and W."""
+        nb = ctypes.c_int64()
+        _lib.check(self._L.rlh_fsshard_info(self._plan, None, None, None, ctypes.byref(nb), None))
+        return int(nb.value)
+
+    def algorithmic_bytes(self, m):
+        """This rank's share of one application: its entries of G and G^H at 4 + sizeof V, x read (own and halo rows)
+        and y written in the matrix type, W written (own rows) and read (own and halo rows) in its own."""
+        es = np.dtype(self._dtype).itemsize
+        cplx = np.dtype(self._dtype).kind == 'c'
+        ev = es if self.work == 'native' else min(es, 8 if cplx else 4)
+        ew = 2 if self.work == 'bf16' else ev
+        return (sum(self._nnz_loc) * (ev + 4) + m * es * (2 * self._n_own + self._n_xhalo)
+                + m * ew * (2 * self._n_own + self._n_whalo))
+
+    def _buffers(self, m, es):
+        key = (m, es)
+        if key not in self._bufs:
+            c = self._comm
+            per = -(-m // 8) * self._w_row_bytes
+            self._bufs[key] = (c.buffer(sum(cnt for _, _, cnt in self._x_send) * m * es), c.buffer(self._n_xhalo * m * es),
+                               c.buffer(self._n_xhalo * m * es), c.buffer(sum(cnt for _, _, cnt in self._w_send) * per),
+                               c.buffer(self._n_whalo * per))
+        return self._bufs[key]
+
+    def _exchange(self, send, recv, sendbuf, recvbuf, row_bytes, pack):
+        """pack(count, device index list, packed output) per peer, then the sends and receives of count * row_bytes
+        bytes each; returns when they have arrived."""
+        c = self._comm
+        ops, soff, roff = [], 0, 0
+        for p, didx, cnt in send:
+            pack(cnt, didx.data_ptr(), sendbuf.data_ptr() + soff)
+            ops.append(c.dist.P2POp(c.dist.isend, sendbuf[soff:soff + cnt * row_bytes], p, group=c.group))
+            soff += cnt * row_bytes
+        for p, _, cnt in recv:
+            ops.append(c.dist.P2POp(c.dist.irecv, recvbuf[roff:roff + cnt * row_bytes], p, group=c.group))
+            roff += cnt * row_bytes
+        for w in (c.dist.batch_isend_irecv(ops) if ops else []):
+            w.wait()
+
+    def apply(self, x, y):
+        """y = G^H (G x) for ShardedVectors windows of equal size on this partition (y may be x)."""
+        if not (hasattr(x, 'comm') and hasattr(y, 'comm')):
+            raise ValueError('ShardedApproximateInverse takes row-sharded blocks')
+        m = x.nvec()
+        if m != y.nvec():
+            raise ValueError('Numbers of input and output vectors differ')
+        if x.data_type() != self._dtype or y.data_type() != self._dtype:
+            raise ValueError('Matrix and vectors data types differ')
+        if x.dimension() != self._n or y.dimension() != self._n or x.local_dimension() != self._n_own \
+                or y.local_dimension() != self._n_own:
+            raise ValueError('Matrix and vectors dimensions incompatible')
+        if m == 0:
+            return
+        L, plan = self._L, self._plan
+        es, code, xp, ldx = x._es, x._code, x.data_ptr(), x.ld()
+        xsend, xrecv, xhalo, wsend, wrecv = self._buffers(m, es)
+        # the rows of x from lower ranks
+        self._exchange(self._x_send, self._x_recv, xsend, xrecv, m * es,
+                       lambda cnt, idx, out: _lib.check(L.rlh_gather_rows(code, cnt, idx, m, xp, ldx, out, cnt)))
+        nh = self._n_xhalo
+        if len(self._x_recv) == 1:                             # one owner: its packed block is the halo block
+            xhalo = xrecv
+        else:
+            roff = 0
+            for _, hs, cnt in self._x_recv:                    # peer blocks (ld = cnt) -> one halo block (ld = nh)
+                _lib.check(L.rlh_copy2d(xhalo.data_ptr() + hs * es, nh * es, xrecv.data_ptr() + roff, cnt * es, cnt * es, m, 2))
+                roff += cnt * m * es
+        _lib.check(L.rlh_fsshard_first(plan, m, xp, ldx, xhalo.data_ptr() if nh else None, nh))
+        # the rows of W from higher ranks, in the type of W
+        per = -(-m // 8) * self._w_row_bytes
+        self._exchange(self._w_send, self._w_recv, wsend, wrecv, per,
+                       lambda cnt, idx, out: _lib.check(L.rlh_fsshard_pack(plan, m, cnt, idx, out)))
+        roff = 0
+        for _, hs, cnt in self._w_recv:
+            _lib.check(L.rlh_fsshard_halo(plan, m, hs, cnt, wrecv.data_ptr() + roff))
+            roff += cnt * per
+        _lib.check(L.rlh_fsshard_second(plan, m, y.data_ptr(), y.ld()))
+
+
 class ShardedDenseMatrix:
     """Dense operator whose ROWS are distributed over the ranks (BASELINE configs 2/4: the PCA
     data matrix, samples sharded).  Vectors of the row dimension M are row-sharded

@@ -23,7 +23,8 @@
 //            (partners at distance 1, 2, .., 32: the same bits in every lane) and the row's lane adds the total.
 //   check    creation ends with fsap_check over the finished arrays: slice offsets and lengths inside the slot arrays,
 //            row lengths within their slice, tail offsets inside the tail arrays, every column a product will read in
-//            [0, n), the entries counted.  What it finds is a message of rlh_fsapply_create through the status record.
+//            [0, ncol) (ncol = n; on a row shard n + its halo rows), the entries counted.  What it finds is a message
+//            of the creating entry point through the status record.
 //
 // Products: grid = (slices / 4) x column tiles of kVT = 8 vectors, 4 waves (slices) per workgroup.  A lane holds kVT
 // accumulators of type T and goes over the positions ascending; a column's sum never sees another column, so the bits
@@ -31,6 +32,9 @@
 // multiple of 16 bytes): the first product writes, and the second gathers, whole 16-byte pieces; columns past m in
 // the last tile are written as zeros and never stored to Y.  X is gathered and Y written column-major with lanes on
 // consecutive rows, at element alignment.  No atomics, no LDS: the order of every sum is fixed by the layout.
+//
+// Row shards (rlh_fsshard_*, at the end of the file): the same layout and the same two products on a rank's rows of G
+// and of G^H, as the compile-time variant SHARD of fsap_product; the halo rows of W travel between the two products.
 #include "fsai.h"
 #include "spmm.h"
 
@@ -124,7 +128,7 @@ __global__ __launch_bounds__(kBlock) void fsap_widths(int64_t n, int64_t slices,
 }
 
 struct LayoutView {
-  int64_t n, slices, slots, tail;
+  int64_t n, ncol, slices, slots, tail;  // ncol: the columns a product may read, [0, ncol) (n, or n + halo rows on a shard)
   const int64_t *off;            // slices + 1: where a slice begins in col / val
   const int32_t *width;          // slices
   const int32_t *rlen;           // n: entries of the row in the sliced part
@@ -187,7 +191,7 @@ __global__ __launch_bounds__(kBlock) void fsap_check(LayoutView L, ApplyStatus *
     }
     for (int64_t p = 0; p < my; ++p) {
       const int64_t c = L.col[base + p * rows + lane];
-      if (c < 0 || c >= L.n) build_error(st, kErrColumn, r);
+      if (c < 0 || c >= L.ncol) build_error(st, kErrColumn, r);
     }
     int64_t t0 = live ? L.tptr[r] : 0, tc = live ? L.tptr[r + 1] - t0 : 0;
     if (t0 < 0 || tc < 0 || t0 + tc > L.tail || (r == 0 && t0 != 0) || (r == L.n - 1 && t0 + tc != L.tail)) {
@@ -201,7 +205,7 @@ __global__ __launch_bounds__(kBlock) void fsap_check(LayoutView L, ApplyStatus *
       const int64_t b = lane_value(t0, t), cnt = lane_value(tc, t);
       for (int64_t e = lane; e < cnt; e += 64) {
         const int64_t c = L.tcol[b + e];
-        if (c < 0 || c >= L.n) build_error(st, kErrColumn, s * 64 + t);
+        if (c < 0 || c >= L.ncol) build_error(st, kErrColumn, s * 64 + t);
       }
     }
     const int64_t held = wave_sum(my + tc);
@@ -212,11 +216,26 @@ __global__ __launch_bounds__(kBlock) void fsap_check(LayoutView L, ApplyStatus *
 // ---------------------------------------------------------------- the products
 template <typename Wt> struct alignas(16) WRow { Wt e[kVT]; };
 
-// acc[k] += v * (column j0 + k of the operand at row c): the first product gathers X column-major, the second a row of W
-template <typename T, typename Wt, bool FIRST>
+// What a product on a row shard (rlh_fsshard_*) has beyond the whole matrix: columns from L.n on are rows of the
+// x-halo block XH (first product), and W has wstride >= L.n rows per tile, the halo rows behind the own ones.
+struct ShardView {
+  const void *XH;
+  int64_t ldxh, wstride;
+};
+
+// acc[k] += v * (column j0 + k of the operand at row c): the first product gathers X column-major (SHARD: row c - n_own
+// of XH where c >= n_own), the second a row of W
+template <typename T, typename Wt, bool FIRST, bool SHARD>
 __device__ __forceinline__ void gather(T (&acc)[kVT], T v, int64_t c, int mt, const T *__restrict__ X, int64_t ldx,
-                                       const WRow<Wt> *__restrict__ W) {
-  if constexpr (FIRST) {
+                                       const WRow<Wt> *__restrict__ W, int64_t n_own, const T *__restrict__ XH, int64_t ldxh) {
+  if constexpr (FIRST && SHARD) {
+    const bool own = c < n_own;
+    const T *src = own ? X + c : XH + (c - n_own);
+    const int64_t ld = own ? ldx : ldxh;
+#pragma unroll
+    for (int k = 0; k < kVT; ++k)
+      if (k < mt) fma_acc(acc[k], v, src[k * ld]);
+  } else if constexpr (FIRST) {
 #pragma unroll
     for (int k = 0; k < kVT; ++k)
       if (k < mt) fma_acc(acc[k], v, X[c + k * ldx]);
@@ -228,11 +247,11 @@ __device__ __forceinline__ void gather(T (&acc)[kVT], T v, int64_t c, int mt, co
 }
 
 // FIRST: Wout = G X (X: the block from column tile0 * kVT on, mt valid columns in a tile); else Y = G^H Win.
-// Wout / Win: the rows of tile tile0 on.
-template <typename T, typename V, typename Wt, bool FIRST>
+// Wout / Win: the rows of tile tile0 on.  SHARD: the products of a row shard (ShardView); without it sv is not looked at.
+template <typename T, typename V, typename Wt, bool FIRST, bool SHARD = false>
 __global__ __launch_bounds__(kBlock) void fsap_product(LayoutView L, int64_t m, const T *__restrict__ X, int64_t ldx,
                                                        const WRow<Wt> *__restrict__ Win, WRow<Wt> *__restrict__ Wout,
-                                                       T *__restrict__ Y, int64_t ldy) {
+                                                       T *__restrict__ Y, int64_t ldy, ShardView sv) {
   const int lane = threadIdx.x & 63;
   const int64_t s = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
   if (s >= L.slices) return;
@@ -244,12 +263,14 @@ __global__ __launch_bounds__(kBlock) void fsap_product(LayoutView L, int64_t m, 
   const int32_t *col = L.col + L.off[s] + lane;
   const V *val = (const V *)L.val + L.off[s] + lane;
   const T *x = FIRST ? X + j0 * ldx : nullptr;
-  const WRow<Wt> *win = FIRST ? nullptr : Win + tile * L.n;
+  const int64_t wstride = SHARD ? sv.wstride : L.n;
+  const WRow<Wt> *win = FIRST ? nullptr : Win + tile * wstride;
+  const T *xh = SHARD && FIRST && sv.XH ? (const T *)sv.XH + j0 * sv.ldxh : nullptr;
   T acc[kVT];
 #pragma unroll
   for (int k = 0; k < kVT; ++k) acc[k] = zero_of(T());
   for (int p = 0; p < w; ++p)
-    if (p < my) gather<T, Wt, FIRST>(acc, up(val[p * rows], T()), (int64_t)col[p * rows], mt, x, ldx, win);
+    if (p < my) gather<T, Wt, FIRST, SHARD>(acc, up(val[p * rows], T()), (int64_t)col[p * rows], mt, x, ldx, win, L.n, xh, sv.ldxh);
   // the tail rows of the slice in ascending order, each by the whole wave
   const int64_t t0 = live ? L.tptr[r] : 0, tc = live ? L.tptr[r + 1] - t0 : 0;
   unsigned long long todo = __ballot(tc > 0);
@@ -261,7 +282,8 @@ __global__ __launch_bounds__(kBlock) void fsap_product(LayoutView L, int64_t m, 
 #pragma unroll
     for (int k = 0; k < kVT; ++k) part[k] = zero_of(T());
     for (int64_t e = lane; e < cnt; e += 64)
-      gather<T, Wt, FIRST>(part, up(((const V *)L.tval)[b + e], T()), (int64_t)L.tcol[b + e], mt, x, ldx, win);
+      gather<T, Wt, FIRST, SHARD>(part, up(((const V *)L.tval)[b + e], T()), (int64_t)L.tcol[b + e], mt, x, ldx, win, L.n, xh,
+                                  sv.ldxh);
 #pragma unroll
     for (int k = 0; k < kVT; ++k) {
       const T total = wave_total(part[k]);
@@ -273,7 +295,7 @@ __global__ __launch_bounds__(kBlock) void fsap_product(LayoutView L, int64_t m, 
     WRow<Wt> out;
 #pragma unroll
     for (int k = 0; k < kVT; ++k) down(acc[k], &out.e[k]);
-    Wout[tile * L.n + r] = out;
+    Wout[tile * wstride + r] = out;
   } else {
 #pragma unroll
     for (int k = 0; k < kVT; ++k)
@@ -283,11 +305,11 @@ __global__ __launch_bounds__(kBlock) void fsap_product(LayoutView L, int64_t m, 
 
 // ---------------------------------------------------------------- the host side
 struct Layout {
-  int64_t n = 0, slices = 0, slots = 0, tail = 0;
+  int64_t n = 0, ncol = 0, slices = 0, slots = 0, tail = 0;
   DevBuf<int64_t> off, tptr;
   DevBuf<int32_t> width, rlen, col, tcol;
   DevBuf<void> val, tval;
-  LayoutView view() const { return LayoutView{n, slices, slots, tail, off, width, rlen, tptr, col, tcol, val, tval}; }
+  LayoutView view() const { return LayoutView{n, ncol, slices, slots, tail, off, width, rlen, tptr, col, tcol, val, tval}; }
   int64_t bytes() const {
     return (int64_t)(off.bytes() + tptr.bytes() + width.bytes() + rlen.bytes() + col.bytes() + tcol.bytes() + val.bytes() +
                      tval.bytes());
@@ -296,7 +318,7 @@ struct Layout {
 
 constexpr const char *kCreate = "rlh_fsapply_create";
 
-int report(const ApplyStatus &s, const char *which, int64_t nnz) {
+int report(const ApplyStatus &s, const char *which, int64_t nnz, const char *kCreate) {
   const int code = (int)(s.err >> 56);
   const long long pos = (long long)(s.err & (((unsigned long long)1 << 56) - 1));
   switch (code) {
@@ -310,13 +332,16 @@ int report(const ApplyStatus &s, const char *which, int64_t nnz) {
   return 1;
 }
 
-// The layout of one orientation (a: its CSR arrays in device memory, `which` names it in messages).
-template <typename T, typename V> int build_layout(Layout &L, const SpdArrays &a, const char *which) {
+// The layout of one orientation (a: its CSR arrays in device memory, `which` names it and kCreate the entry point in
+// messages).
+template <typename T, typename V>
+int build_layout(Layout &L, const SpdArrays &a, const char *which, const char *kCreate = rlh::kCreate) {
   hipStream_t st = ctx().stream;
   const dim3 blk(kBlock);
   const int64_t n = a.rows, slices = (n + 63) / 64;
   const unsigned grid = blocks_for(slices, kWaves, 1 << 20);
   L.n = n;
+  L.ncol = a.cols;
   L.slices = slices;
   if (int rc = L.off.alloc(slices + 1)) return rc;
   if (int rc = L.width.alloc(slices)) return rc;
@@ -354,7 +379,7 @@ template <typename T, typename V> int build_layout(Layout &L, const SpdArrays &a
   RLH_HIP(hipGetLastError());
   RLH_HIP(hipMemcpyAsync(&hs, status, sizeof hs, hipMemcpyDeviceToHost, st));
   RLH_HIP(hipStreamSynchronize(st));           // the handle's arrays and the scratch are not referenced after the return
-  if (hs.err != kNoError || (int64_t)hs.entries != a.nnz) return report(hs, which, a.nnz);
+  if (hs.err != kNoError || (int64_t)hs.entries != a.nnz) return report(hs, which, a.nnz, kCreate);
   return 0;
 }
 
@@ -390,10 +415,10 @@ int run_typed(rlh_fsapply *p, int64_t m, const void *X, int64_t ldx, void *Y, in
       const dim3 grid(gx, (unsigned)nt);
       if (pass == 0)
         hipLaunchKernelGGL((fsap_product<T, V, Wt, true>), grid, blk, 0, st, p->g.view(), m - j0, (const T *)X + j0 * ldx, ldx,
-                           (const WRow<Wt> *)nullptr, W + t0 * p->n, (T *)nullptr, (int64_t)0);
+                           (const WRow<Wt> *)nullptr, W + t0 * p->n, (T *)nullptr, (int64_t)0, ShardView{});
       else
         hipLaunchKernelGGL((fsap_product<T, V, Wt, false>), grid, blk, 0, st, p->gh.view(), m - j0, (const T *)nullptr, (int64_t)0,
-                           (const WRow<Wt> *)(W + t0 * p->n), (WRow<Wt> *)nullptr, (T *)Y + j0 * ldy, ldy);
+                           (const WRow<Wt> *)(W + t0 * p->n), (WRow<Wt> *)nullptr, (T *)Y + j0 * ldy, ldy, ShardView{});
     }
   }
   RLH_HIP(hipGetLastError());
@@ -463,6 +488,252 @@ extern "C" int rlh_fsapply_info(rlh_fsapply_t p, int *work, int64_t *stored_slot
 }
 
 extern "C" int rlh_fsapply_destroy(rlh_fsapply_t p) {
+  if (!p) return 0;
+  if (ctx().ready) (void)hipStreamSynchronize(ctx().stream);
+  delete p;
+  return 0;
+}
+
+// ---------------------------------------------------------------- the application on a row shard (rlh_fsshard_*)
+// G_loc (the shard's rows of G; columns: own rows, then the rows of the x-halo block) and GH_loc (the shard's rows of
+// G^H; columns: own rows, then the halo rows of W) go through the same layout and the same two products; W is
+// [tile][n_own + n_whalo][kVT], its halo rows placed between the products from what the owners packed.
+struct rlh_fsshard {
+  int dtype = 0, work = 0;
+  int64_t n_own = 0, n_xhalo = 0, n_whalo = 0;
+  int64_t m_first = -1, placed = 0;  // the vectors of the last rlh_fsshard_first (-1: none yet), the halo rows placed since
+  rlh::Layout g, gh;
+  rlh::DevBuf<char> w;
+};
+
+namespace rlh {
+namespace {
+
+constexpr const char *kShardCreate = "rlh_fsshard_create";
+
+// dst row (drow0 + i) of tile t <- src row (idx ? idx[i] : i) of tile t, i < nrows, as 16-byte pieces (`pieces` per row;
+// the strides count rows).  An index outside [0, bound) is not followed: the row is written as zeros.
+__global__ __launch_bounds__(kBlock) void fsap_rows(int64_t nrows, int pieces, const int64_t *__restrict__ idx, int64_t bound,
+                                                    const uint4 *__restrict__ src, int64_t sstride, uint4 *__restrict__ dst,
+                                                    int64_t dstride, int64_t drow0) {
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x, tile = blockIdx.y;
+  if (e >= nrows * pieces) return;
+  const int64_t i = e / pieces, q = e - i * pieces;
+  const int64_t r = idx ? idx[i] : i;
+  uint4 v = make_uint4(0, 0, 0, 0);
+  if (r >= 0 && r < bound) v = src[(tile * sstride + r) * pieces + q];
+  dst[(tile * dstride + drow0 + i) * pieces + q] = v;
+}
+
+int move_rows(int64_t tiles, int64_t nrows, int pieces, const int64_t *idx, int64_t bound, const void *src, int64_t sstride,
+              void *dst, int64_t dstride, int64_t drow0) {
+  const unsigned gx = (unsigned)((nrows * pieces + kBlock - 1) / kBlock);
+  for (int64_t t0 = 0; t0 < tiles; t0 += kMaxTilesY) {
+    const int64_t nt = tiles - t0 < kMaxTilesY ? tiles - t0 : kMaxTilesY;
+    hipLaunchKernelGGL(fsap_rows, dim3(gx, (unsigned)nt), dim3(kBlock), 0, ctx().stream, nrows, pieces, idx, bound,
+                       (const uint4 *)src + t0 * sstride * pieces, sstride, (uint4 *)dst + t0 * dstride * pieces, dstride, drow0);
+  }
+  RLH_HIP(hipGetLastError());
+  return 0;
+}
+
+// bytes of one element of W
+int64_t w_elem_bytes(int dtype, int work) {
+  if (work == 2) return 2;
+  switch (dtype) {
+    case RLH_S: return 4;
+    case RLH_D: return work ? 4 : 8;
+    case RLH_C: return 8;
+    default: return work ? 8 : 16;
+  }
+}
+
+// f(T(), V(), Wt()) for the types of a plan
+template <typename F> int with_types(int dtype, int work, F f) {
+  switch (dtype) {
+    case RLH_S: return work == 2 ? f(float(), float(), bf16()) : f(float(), float(), float());
+    case RLH_D: return work == 2 ? f(double(), float(), bf16()) : work == 1 ? f(double(), float(), float()) : f(double(), double(), double());
+    case RLH_C: return f(c32(), c32(), c32());
+    default: return work ? f(c64(), c32(), c32()) : f(c64(), c64(), c64());
+  }
+}
+
+// one orientation: the host arrays into device memory, then the layout (the uploads go when this returns)
+template <typename T, typename V>
+int shard_layout(Layout &L, int64_t rows, int64_t cols, const int64_t *ip, const int32_t *ix, const void *va, const char *which) {
+  const int64_t nnz = ip[rows];
+  DevBuf<int64_t> dip;
+  DevBuf<int32_t> dix;
+  DevBuf<char> dva;
+  if (int rc = dip.upload(ip, (size_t)(rows + 1) * 8)) return rc;
+  if (int rc = dix.upload(ix, (size_t)nnz * 4, 16)) return rc;
+  if (int rc = dva.upload(va, (size_t)nnz * sizeof(T), 16)) return rc;
+  SpdArrays a;
+  a.rows = rows; a.cols = cols; a.nnz = nnz;
+  a.indptr = dip; a.idx = dix; a.val = dva.get();
+  return build_layout<T, V>(L, a, which, kShardCreate);
+}
+
+template <typename T, typename V, typename Wt>
+int shard_first(rlh_fsshard *p, int64_t m, const void *X, int64_t ldx, const void *XH, int64_t ldxh) {
+  const int64_t tiles = (m + kVT - 1) / kVT, wrows = p->n_own + p->n_whalo;
+  if (int rc = p->w.reserve((size_t)tiles * (size_t)wrows * sizeof(WRow<Wt>))) return rc;
+  WRow<Wt> *W = (WRow<Wt> *)p->w.get();
+  const unsigned gx = (unsigned)((p->g.slices + kWaves - 1) / kWaves);
+  for (int64_t t0 = 0; t0 < tiles && gx; t0 += kMaxTilesY) {
+    const int64_t nt = tiles - t0 < kMaxTilesY ? tiles - t0 : kMaxTilesY, j0 = t0 * kVT;
+    const ShardView sv{XH ? (const void *)((const T *)XH + j0 * ldxh) : nullptr, ldxh, wrows};
+    hipLaunchKernelGGL((fsap_product<T, V, Wt, true, true>), dim3(gx, (unsigned)nt), dim3(kBlock), 0, ctx().stream, p->g.view(),
+                       m - j0, (const T *)X + j0 * ldx, ldx, (const WRow<Wt> *)nullptr, W + t0 * wrows, (T *)nullptr, (int64_t)0, sv);
+  }
+  RLH_HIP(hipGetLastError());
+  return 0;
+}
+
+template <typename T, typename V, typename Wt> int shard_second(rlh_fsshard *p, int64_t m, void *Y, int64_t ldy) {
+  const int64_t tiles = (m + kVT - 1) / kVT, wrows = p->n_own + p->n_whalo;
+  const WRow<Wt> *W = (const WRow<Wt> *)p->w.get();
+  const unsigned gx = (unsigned)((p->gh.slices + kWaves - 1) / kWaves);
+  for (int64_t t0 = 0; t0 < tiles && gx; t0 += kMaxTilesY) {
+    const int64_t nt = tiles - t0 < kMaxTilesY ? tiles - t0 : kMaxTilesY, j0 = t0 * kVT;
+    const ShardView sv{nullptr, 0, wrows};
+    hipLaunchKernelGGL((fsap_product<T, V, Wt, false, true>), dim3(gx, (unsigned)nt), dim3(kBlock), 0, ctx().stream, p->gh.view(),
+                       m - j0, (const T *)nullptr, (int64_t)0, W + t0 * wrows, (WRow<Wt> *)nullptr, (T *)Y + j0 * ldy, ldy, sv);
+  }
+  RLH_HIP(hipGetLastError());
+  return 0;
+}
+
+// indptr[0] == 0 and non-decreasing
+int64_t first_decrease(const int64_t *ip, int64_t rows) {
+  if (ip[0] != 0) return 0;
+  for (int64_t r = 0; r < rows; ++r)
+    if (ip[r + 1] < ip[r]) return r + 1;
+  return -1;
+}
+
+}  // namespace
+}  // namespace rlh
+
+extern "C" int rlh_fsshard_create(rlh_fsshard_t *pp, int dtype, int work, int64_t n_own, int64_t n_xhalo, int64_t n_whalo,
+                                  const int64_t *g_indptr, const int32_t *g_indices, const void *g_values,
+                                  const int64_t *gh_indptr, const int32_t *gh_indices, const void *gh_values) {
+  if (int rc = require_ready()) return rc;
+  RLH_REQUIRE(pp != nullptr, "rlh_fsshard_create: null plan pointer");
+  *pp = nullptr;
+  RLH_REQUIRE(dtype == RLH_S || dtype == RLH_D || dtype == RLH_C || dtype == RLH_Z, "rlh_fsshard_create: unknown dtype %d", dtype);
+  RLH_REQUIRE(work >= 0 && work <= 2, "rlh_fsshard_create: work must be 0 (native), 1 (float32) or 2 (bf16), got %d", work);
+  RLH_REQUIRE(work != 2 || dtype == RLH_S || dtype == RLH_D, "rlh_fsshard_create: bfloat16 work blocks are for real types only");
+  RLH_REQUIRE(n_own >= 0 && n_xhalo >= 0 && n_whalo >= 0, "rlh_fsshard_create: negative size");
+  RLH_REQUIRE(n_own + n_xhalo <= INT32_MAX && n_own + n_whalo <= INT32_MAX, "rlh_fsshard_create: more than 2^31 - 1 columns");
+  RLH_REQUIRE(g_indptr && gh_indptr, "rlh_fsshard_create: null indptr");
+  int64_t bad = first_decrease(g_indptr, n_own);
+  RLH_REQUIRE(bad < 0, "rlh_fsshard_create: indptr of G must start at 0 and not decrease (row %lld)", (long long)(bad ? bad - 1 : 0));
+  bad = first_decrease(gh_indptr, n_own);
+  RLH_REQUIRE(bad < 0, "rlh_fsshard_create: indptr of G^H must start at 0 and not decrease (row %lld)", (long long)(bad ? bad - 1 : 0));
+  RLH_REQUIRE((g_indptr[n_own] == 0 || (g_indices && g_values)) && (gh_indptr[n_own] == 0 || (gh_indices && gh_values)),
+              "rlh_fsshard_create: null indices or values");
+  rlh_fsshard *p = new rlh_fsshard();
+  p->dtype = dtype;
+  p->work = work;
+  p->n_own = n_own;
+  p->n_xhalo = n_xhalo;
+  p->n_whalo = n_whalo;
+  int rc = 0;
+  if (n_own > 0)
+    rc = with_types(dtype, work, [&](auto t, auto v, auto) {
+      using T = decltype(t);
+      using V = decltype(v);
+      if (int r = shard_layout<T, V>(p->g, n_own, n_own + n_xhalo, g_indptr, g_indices, g_values, "G")) return r;
+      return shard_layout<T, V>(p->gh, n_own, n_own + n_whalo, gh_indptr, gh_indices, gh_values, "G^H");
+    });
+  if (rc) {
+    rlh_fsshard_destroy(p);
+    return rc;
+  }
+  *pp = p;
+  return 0;
+}
+
+extern "C" int rlh_fsshard_first(rlh_fsshard_t p, int64_t m, const void *X, int64_t ldx, const void *XH, int64_t ldxh) {
+  if (int rc = require_ready()) return rc;
+  RLH_REQUIRE(p, "rlh_fsshard_first: null plan");
+  RLH_REQUIRE(m >= 0, "rlh_fsshard_first: negative number of vectors");
+  if (m > 0 && p->n_own > 0) {
+    RLH_REQUIRE(X, "rlh_fsshard_first: null pointer");
+    RLH_REQUIRE(XH || p->n_xhalo == 0, "rlh_fsshard_first: null halo block with %lld halo rows", (long long)p->n_xhalo);
+    RLH_REQUIRE(ldx >= p->n_own && (!XH || ldxh >= p->n_xhalo), "rlh_fsshard_first: Matrix and vectors dimensions incompatible");
+  }
+  p->m_first = -1;
+  p->placed = 0;
+  if (m > 0)
+    if (int rc = with_types(p->dtype, p->work, [&](auto t, auto v, auto w) {
+          return shard_first<decltype(t), decltype(v), decltype(w)>(p, m, X, ldx, p->n_xhalo ? XH : nullptr, ldxh);
+        }))
+      return rc;
+  p->m_first = m;
+  return 0;
+}
+
+extern "C" int rlh_fsshard_pack(rlh_fsshard_t p, int64_t m, int64_t nidx, const int64_t *d_idx, void *out) {
+  if (int rc = require_ready()) return rc;
+  RLH_REQUIRE(p, "rlh_fsshard_pack: null plan");
+  RLH_REQUIRE(m >= 0 && nidx >= 0, "rlh_fsshard_pack: negative size");
+  RLH_REQUIRE(nidx <= p->n_own, "rlh_fsshard_pack: %lld rows asked of %lld own rows", (long long)nidx, (long long)p->n_own);
+  RLH_REQUIRE(p->m_first == m, "rlh_fsshard_pack: no rlh_fsshard_first with %lld vectors came before", (long long)m);
+  if (m == 0 || nidx == 0) return 0;
+  RLH_REQUIRE(d_idx && out, "rlh_fsshard_pack: null pointer");
+  const int64_t tiles = (m + kVT - 1) / kVT, wrows = p->n_own + p->n_whalo;
+  return move_rows(tiles, nidx, (int)(kVT * w_elem_bytes(p->dtype, p->work) / 16), d_idx, p->n_own, p->w.get(), wrows, out, nidx, 0);
+}
+
+extern "C" int rlh_fsshard_halo(rlh_fsshard_t p, int64_t m, int64_t first, int64_t count, const void *src) {
+  if (int rc = require_ready()) return rc;
+  RLH_REQUIRE(p, "rlh_fsshard_halo: null plan");
+  RLH_REQUIRE(m >= 0 && first >= 0 && count >= 0, "rlh_fsshard_halo: negative size");
+  RLH_REQUIRE(first + count <= p->n_whalo, "rlh_fsshard_halo: rows %lld .. %lld of %lld halo rows", (long long)first,
+              (long long)(first + count), (long long)p->n_whalo);
+  RLH_REQUIRE(p->m_first == m, "rlh_fsshard_halo: no rlh_fsshard_first with %lld vectors came before", (long long)m);
+  if (m > 0 && count > 0) {
+    RLH_REQUIRE(src, "rlh_fsshard_halo: null pointer");
+    const int64_t tiles = (m + kVT - 1) / kVT, wrows = p->n_own + p->n_whalo;
+    if (int rc = move_rows(tiles, count, (int)(kVT * w_elem_bytes(p->dtype, p->work) / 16), nullptr, count, src, count, p->w.get(),
+                           wrows, p->n_own + first))
+      return rc;
+  }
+  p->placed += count;
+  return 0;
+}
+
+extern "C" int rlh_fsshard_second(rlh_fsshard_t p, int64_t m, void *Y, int64_t ldy) {
+  if (int rc = require_ready()) return rc;
+  RLH_REQUIRE(p, "rlh_fsshard_second: null plan");
+  RLH_REQUIRE(m >= 0, "rlh_fsshard_second: negative number of vectors");
+  RLH_REQUIRE(p->m_first >= 0, "rlh_fsshard_second: no rlh_fsshard_first came before");
+  RLH_REQUIRE(p->m_first == m, "rlh_fsshard_second: the last rlh_fsshard_first had %lld vectors, not %lld", (long long)p->m_first,
+              (long long)m);
+  RLH_REQUIRE(p->placed >= p->n_whalo, "rlh_fsshard_second: halo rows missing (%lld of %lld placed)", (long long)p->placed,
+              (long long)p->n_whalo);
+  if (m == 0 || p->n_own == 0) return 0;
+  RLH_REQUIRE(Y, "rlh_fsshard_second: null pointer");
+  RLH_REQUIRE(ldy >= p->n_own, "rlh_fsshard_second: Matrix and vectors dimensions incompatible");
+  return with_types(p->dtype, p->work, [&](auto t, auto v, auto w) {
+    return shard_second<decltype(t), decltype(v), decltype(w)>(p, m, Y, ldy);
+  });
+}
+
+extern "C" int rlh_fsshard_info(rlh_fsshard_t p, int *work, int64_t *stored_slots, int64_t *tail_entries, int64_t *device_bytes,
+                                int64_t *w_row_bytes) {
+  RLH_REQUIRE(p, "rlh_fsshard_info: null plan");
+  if (work) *work = p->work;
+  if (stored_slots) *stored_slots = p->g.slots + p->gh.slots;
+  if (tail_entries) *tail_entries = p->g.tail + p->gh.tail;
+  if (device_bytes) *device_bytes = p->g.bytes() + p->gh.bytes() + (int64_t)p->w.bytes();
+  if (w_row_bytes) *w_row_bytes = kVT * w_elem_bytes(p->dtype, p->work);
+  return 0;
+}
+
+extern "C" int rlh_fsshard_destroy(rlh_fsshard_t p) {
   if (!p) return 0;
   if (ctx().ready) (void)hipStreamSynchronize(ctx().stream);
   delete p;

@@ -49,7 +49,11 @@ def partial_hevp(A, B=None, T=None, buckling=False, sigma=0, which=6, tol=1e-4, 
     of the computed G that are small in a scaling-invariant measure and solves every row again on what is left: a
     cheaper application for a few more iterations), as `ChebyshevPreconditioner`
     is from the operator; an IncompleteLU preconditioner is a host factorisation and is set up from a SciPy matrix
-    only.  A CPU tensor is taken as the SciPy matrix of its arrays (ndarrays come back).
+    only.  A CPU tensor is taken as the SciPy matrix of its arrays (ndarrays come back).  On row-sharded blocks
+    (`vectors` and ``operator=ShardedSparseMatrix(...)``) the approximate inverse is `ShardedApproximateInverse`
+    (algebra/hip/dist.py), built with the operator's partition: every rank holds its rows of G and its columns of G^H,
+    and an application exchanges the rows of x it reads from lower ranks and the rows of G x it reads from higher
+    ones; beyond ``levels=1, steps=0`` its pattern depends on the partition.
 
     Returns (lmd, x, status): eigenvalues ascending, eigenvectors as columns, status as
     in the reference (0 success, 1 iteration limit, 2 no search directions, 3/4 some
