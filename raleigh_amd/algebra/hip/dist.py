@@ -25,6 +25,7 @@ from ... import _lib
 from .vectors import Vectors, ReductionBatch
 from .memory import upload, download
 from .sparse import CsrOperator, full_from_upper
+from .precond import ApproximateInverse, WORK, check_work, work_element_bytes
 
 _REAL = {np.float32: np.float32, np.float64: np.float64,
          np.complex64: np.float32, np.complex128: np.float64}
@@ -174,6 +175,73 @@ def partition(n, size):
     off = [min(p * per, n) for p in range(size + 1)]
     off[size] = n
     return np.array(off, dtype=np.int64)
+
+
+def virtual_cut(r0, r1):
+    """The row at which ONE rank with forced collectives cuts its shard [r0, r1) into two virtual ranks (a multiple of 8
+    rows above r0): the rows on either side of it exchange their halo rows as sends to self."""
+    return r0 + (((r1 - r0) // 2) // 8) * 8
+
+
+class HaloExchange:
+    """The rows of other shards that a row-sharded operator reads in one application, and their exchange.
+
+    ids: the global ids of the rows wanted, ascending (so grouped by owner); n_own: this rank's rows.  Set-up is ONE
+    all_gather_object (every rank tells the owners which of their rows it wants) and leaves
+      recv   the receive runs (peer, first halo row, count), peers ascending;
+      send   what the peers want of this rank: (peer, device index list of own rows, count), peers ascending.
+    A rank exchanges with itself only under forced collectives."""
+
+    def __init__(self, comm, offsets, ids, n_own):
+        self._comm = comm
+        owner = np.searchsorted(offsets, ids, side='right') - 1
+        self.recv = []
+        for p in range(comm.size):
+            idx = np.nonzero(owner == p)[0]
+            if idx.size:
+                self.recv.append((p, int(idx[0]), int(idx.size)))
+        mine = {p: (ids[s:s + c] - offsets[p]).astype(np.int64) for p, s, c in self.recv}
+        wants = [None] * comm.size
+        comm.dist.all_gather_object(wants, mine, group=comm.group)
+        self.send = []
+        for p in range(comm.size):
+            if (p != comm.rank or comm.force) and wants[p] and comm.rank in wants[p]:
+                idx = np.ascontiguousarray(wants[p][comm.rank])
+                assert idx.size == 0 or (idx.min() >= 0 and idx.max() < n_own)
+                dbuf = comm.buffer(idx.nbytes)
+                dbuf.copy_(comm.torch.from_numpy(idx.view(np.uint8)))
+                self.send.append((p, dbuf, int(idx.size)))
+        self.send_rows = sum(cnt for _, _, cnt in self.send)
+        self._works = ()
+
+    def post(self, sendbuf, recvbuf, row_bytes, pack):
+        """pack(count, device index list, packed output) per peer, then all sends and all receives of count * row_bytes
+        bytes each, posted as one batch."""
+        dist, group = self._comm.dist, self._comm.group       # (this runs per application: no lookup twice)
+        ops, soff, roff = [], 0, 0
+        for p, didx, cnt in self.send:
+            pack(cnt, didx.data_ptr(), sendbuf.data_ptr() + soff)
+            ops.append(dist.P2POp(dist.isend, sendbuf[soff:soff + cnt * row_bytes], p, group=group))
+            soff += cnt * row_bytes
+        for p, _, cnt in self.recv:
+            ops.append(dist.P2POp(dist.irecv, recvbuf[roff:roff + cnt * row_bytes], p, group=group))
+            roff += cnt * row_bytes
+        self._works = dist.batch_isend_irecv(ops) if ops else ()
+
+    def wait(self):
+        """Returns when what `post` posted has arrived."""
+        for w in self._works:
+            w.wait()
+        self._works = ()
+
+    def assemble(self, recvbuf, halo, ld, m, es):
+        """The peers' packed blocks in recvbuf (column-major, ld = count, m vectors of es-byte elements) -> the one halo
+        block `halo` of leading dimension ld."""
+        L = _lib.lib()
+        roff = 0
+        for _, hs, cnt in self.recv:
+            _lib.check(L.rlh_copy2d(halo.data_ptr() + hs * es, ld * es, recvbuf.data_ptr() + roff, cnt * es, cnt * es, m, 2))
+            roff += cnt * m * es
 
 
 class ShardedVectors(Vectors):
@@ -435,11 +503,10 @@ class ShardedSparseMatrix:
             # go pack -> send to self -> receive -> halo block, so the whole exchange runs.  (Earlier rounds re-routed
             # EVERY reference to the last rows of the shard, diagonals included, which no real shard does: it hid two
             # layout rules that only real shards trip -- DESIGN 5.)
-            cut = r0 + (((r1 - r0) // 2) // 8) * 8
+            cut = virtual_cut(r0, r1)
             rows_of = np.repeat(np.arange(r0, r1, dtype=np.int64), np.diff(loc.indptr))
             own = (cols >= cut) == (rows_of >= cut)
         halo_cols = np.unique(cols[~own])                     # global ids, sorted => grouped by owner
-        owner = np.searchsorted(off, halo_cols, side='right') - 1
         # local column numbering: own rows first, then the halo rows from a multiple of 8 on (the
         # 1-7 columns in between are never referenced: they are the padding of the local block's
         # leading dimension), so that no 16-byte piece of the library's staging loads lies across
@@ -458,23 +525,7 @@ class ShardedSparseMatrix:
                              shape=(r1 - r0, n_own_pad + self._ld_halo))
         self._op = CsrOperator(ext, n_own=n_own_pad)
         self._nnz = nnz_global
-        # receive plan: contiguous runs of halo rows per owner
-        self._recv = []                                       # (peer, halo_start, count)
-        for p in range(comm.size):
-            idx = np.nonzero(owner == p)[0]
-            if idx.size:
-                self._recv.append((p, int(idx[0]), int(idx.size)))
-        # tell every owner which of its rows this rank needs
-        wants = [None] * comm.size
-        mine = {p: (halo_cols[s:s + c] - off[p]).astype(np.int64) for p, s, c in self._recv}
-        comm.dist.all_gather_object(wants, mine, group=comm.group)
-        self._send = []                                       # (peer, device index list, count)
-        for p in range(comm.size):
-            if (p != comm.rank or comm.force) and wants[p] and comm.rank in wants[p]:
-                idx = np.ascontiguousarray(wants[p][comm.rank])
-                dbuf = comm.buffer(idx.nbytes)
-                dbuf.copy_(comm.torch.from_numpy(idx.view(np.uint8)))
-                self._send.append((p, dbuf, int(idx.size)))
+        self._halo = HaloExchange(comm, off, halo_cols, self._n_own)
         self._bufs = {}
         self._bf16 = None
 
@@ -494,7 +545,7 @@ class ShardedSparseMatrix:
         key = (m, es)
         if key not in self._bufs:
             c = self._comm
-            ns = sum(cnt for _, _, cnt in self._send)
+            ns = self._halo.send_rows
             nr = self._ld_halo
             self._bufs[key] = (c.buffer(ns * m * es), c.buffer(nr * m * es), c.buffer(nr * m * es))
         return self._bufs[key]
@@ -510,35 +561,20 @@ class ShardedSparseMatrix:
     def _start_exchange_raw(self, m, es, gather):
         """`gather(count, device index list, packed output)` packs rows of the block being exchanged;
         es: bytes per element (2 for the bfloat16 work blocks of the preconditioner)."""
-        c = self._comm
-        if not (self._n_halo > 0 or self._send):
+        if not (self._n_halo > 0 or self._halo.send):
             return None
         sendbuf, recvbuf, halo = self._buffers(m, es)
-        ops, soff, roff = [], 0, 0
-        for p, didx, cnt in self._send:                   # pack the rows each peer needs
-            gather(cnt, didx.data_ptr(), sendbuf.data_ptr() + soff)
-            ops.append(c.dist.P2POp(c.dist.isend, sendbuf[soff:soff + cnt * m * es], p, group=c.group))
-            soff += cnt * m * es
-        for p, hs, cnt in self._recv:
-            ops.append(c.dist.P2POp(c.dist.irecv, recvbuf[roff:roff + cnt * m * es], p, group=c.group))
-            roff += cnt * m * es
-        works = c.dist.batch_isend_irecv(ops) if ops else []
-        return works, recvbuf, halo, m, es
+        self._halo.post(sendbuf, recvbuf, m * es, gather)
+        return recvbuf, halo, m, es
 
     def _finish_exchange(self, pending):
         """Waits for the transfers and assembles the halo block; returns (device pointer, leading
         dimension) or (None, 0)."""
         if pending is None:
             return None, 0
-        works, recvbuf, halo, m, es = pending
-        L = _lib.lib()
-        for w in works:
-            w.wait()
-        roff = 0
-        for p, hs, cnt in self._recv:                     # peer blocks (ld = cnt) -> one halo block (ld = n_halo)
-            _lib.check(L.rlh_copy2d(halo.data_ptr() + hs * es, self._ld_halo * es,
-                                    recvbuf.data_ptr() + roff, cnt * es, cnt * es, m, 2))
-            roff += cnt * m * es
+        recvbuf, halo, m, es = pending
+        self._halo.wait()
+        self._halo.assemble(recvbuf, halo, self._ld_halo, m, es)
         if self._n_halo > 0:
             return halo.data_ptr(), self._ld_halo
         return None, 0
@@ -644,11 +680,11 @@ class ShardedApproximateInverse:
     nnz, longest_row and fill are global (one all-reduce at set-up); dropped_entries covers this rank's rows;
     setup_seconds is the host wall time of the whole set-up on this rank."""
 
-    WORK = {'native': 0, 'float32': 1, 'bf16': 2}
+    WORK = WORK
 
     def __init__(self, matrix, comm, offsets=None, max_row=64, levels=1, steps=0, step_size=1, work='native', drop=0.0):
         self._plan = None
-        self._check_work(work, matrix.dtype)
+        check_work(work, matrix.dtype)
         full = full_from_upper(matrix)
         n = full.shape[0]
         off = partition(n, comm.size) if offsets is None else offsets
@@ -664,7 +700,7 @@ class ShardedApproximateInverse:
         self = cls.__new__(cls)
         self._plan = None
         rows = scs.csr_matrix(rows)
-        self._check_work(work, rows.dtype)
+        check_work(work, rows.dtype)
         assert rows.shape[1] == n and row0 == int(offsets[comm.rank])
 
         def rows_of(ids):
@@ -688,16 +724,8 @@ class ShardedApproximateInverse:
                     dict(max_row=max_row, levels=levels, steps=steps, step_size=step_size, drop=drop), work)
         return self
 
-    @classmethod
-    def _check_work(cls, work, dtype):
-        if work not in cls.WORK:
-            raise ValueError("work must be 'native', 'float32' or 'bf16', got %r" % (work,))
-        if work == 'bf16' and np.dtype(dtype).kind == 'c':
-            raise ValueError("work='bf16' is for real matrices only")
-
     def _setup(self, loc, r0, n, comm, off, rows_of, build, work):
         import time
-        from .precond import ApproximateInverse
         t_start = time.perf_counter()
         L = self._L = _lib.lib()
         self._comm, self._n, self._offsets, self.work = comm, n, off, work
@@ -739,7 +767,7 @@ class ShardedApproximateInverse:
         self._g = (gp, gi, gv)
         grow = np.repeat(np.arange(r0, r1, dtype=np.int64), np.diff(gp))
         forced = comm.size == 1 and comm.force
-        cut = r0 + (((r1 - r0) // 2) // 8) * 8                # (the two virtual ranks of ShardedSparseMatrix._setup)
+        cut = virtual_cut(r0, r1)                              # (the two virtual ranks of ShardedSparseMatrix._setup)
         own = ((gi >= cut) == (grow >= cut)) if forced else (gi >= r0)
         x_ids = np.unique(gi[~own])
         g_idx = np.where(own, gi - r0, n_own + np.searchsorted(x_ids, gi)).astype(np.int32)
@@ -772,8 +800,8 @@ class ShardedApproximateInverse:
         wrb = ctypes.c_int64()
         _lib.check(L.rlh_fsshard_info(plan, None, None, None, None, ctypes.byref(wrb)))
         self._w_row_bytes = int(wrb.value)
-        self._x_recv, self._x_send = self._exchange_plan(x_ids)
-        self._w_recv, self._w_send = self._exchange_plan(w_ids)
+        self._x_halo = HaloExchange(comm, off, x_ids, n_own)
+        self._w_halo = HaloExchange(comm, off, w_ids, n_own)
         self._bufs = {}
         # ---- what describes the whole of G: one all-reduce (a slot per rank carries its longest row)
         tt = comm.torch
@@ -786,29 +814,6 @@ class ShardedApproximateInverse:
         self.nnz, self.longest_row = int(t[0]), int(t[2:].max())
         self.fill = self.nnz / float(max(int(t[1]), 1))
         self.setup_seconds = time.perf_counter() - t_start
-
-    def _exchange_plan(self, ids):
-        """For the halo rows `ids` (global, ascending: grouped by owner): the receive runs (peer, first halo row, count)
-        and, from what the peers ask of this rank, the sends (peer, device index list of own rows, count)."""
-        comm, off = self._comm, self._offsets
-        owner = np.searchsorted(off, ids, side='right') - 1
-        recv = []
-        for p in range(comm.size):
-            idx = np.nonzero(owner == p)[0]
-            if idx.size:
-                recv.append((p, int(idx[0]), int(idx.size)))
-        mine = {p: (ids[s:s + c] - off[p]).astype(np.int64) for p, s, c in recv}
-        wants = [None] * comm.size
-        comm.dist.all_gather_object(wants, mine, group=comm.group)
-        send = []
-        for p in range(comm.size):
-            if (p != comm.rank or comm.force) and wants[p] and comm.rank in wants[p]:
-                idx = np.ascontiguousarray(wants[p][comm.rank])
-                assert idx.size == 0 or (idx.min() >= 0 and idx.max() < self._n_own)
-                dbuf = comm.buffer(idx.nbytes)
-                dbuf.copy_(comm.torch.from_numpy(idx.view(np.uint8)))
-                send.append((p, dbuf, int(idx.size)))
-        return recv, send
 
     def __del__(self):
         plan, self._plan = getattr(self, '_plan', None), None
@@ -843,9 +848,7 @@ class ShardedApproximateInverse:
         """This rank's share of one application: its entries of G and G^H at 4 + sizeof V, x read (own and halo rows)
         and y written in the matrix type, W written (own rows) and read (own and halo rows) in its own."""
         es = np.dtype(self._dtype).itemsize
-        cplx = np.dtype(self._dtype).kind == 'c'
-        ev = es if self.work == 'native' else min(es, 8 if cplx else 4)
-        ew = 2 if self.work == 'bf16' else ev
+        ev, ew = work_element_bytes(self.work, self._dtype)
         return (sum(self._nnz_loc) * (ev + 4) + m * es * (2 * self._n_own + self._n_xhalo)
                 + m * ew * (2 * self._n_own + self._n_whalo))
 
@@ -854,25 +857,10 @@ class ShardedApproximateInverse:
         if key not in self._bufs:
             c = self._comm
             per = -(-m // 8) * self._w_row_bytes
-            self._bufs[key] = (c.buffer(sum(cnt for _, _, cnt in self._x_send) * m * es), c.buffer(self._n_xhalo * m * es),
-                               c.buffer(self._n_xhalo * m * es), c.buffer(sum(cnt for _, _, cnt in self._w_send) * per),
+            self._bufs[key] = (c.buffer(self._x_halo.send_rows * m * es), c.buffer(self._n_xhalo * m * es),
+                               c.buffer(self._n_xhalo * m * es), c.buffer(self._w_halo.send_rows * per),
                                c.buffer(self._n_whalo * per))
         return self._bufs[key]
-
-    def _exchange(self, send, recv, sendbuf, recvbuf, row_bytes, pack):
-        """pack(count, device index list, packed output) per peer, then the sends and receives of count * row_bytes
-        bytes each; returns when they have arrived."""
-        c = self._comm
-        ops, soff, roff = [], 0, 0
-        for p, didx, cnt in send:
-            pack(cnt, didx.data_ptr(), sendbuf.data_ptr() + soff)
-            ops.append(c.dist.P2POp(c.dist.isend, sendbuf[soff:soff + cnt * row_bytes], p, group=c.group))
-            soff += cnt * row_bytes
-        for p, _, cnt in recv:
-            ops.append(c.dist.P2POp(c.dist.irecv, recvbuf[roff:roff + cnt * row_bytes], p, group=c.group))
-            roff += cnt * row_bytes
-        for w in (c.dist.batch_isend_irecv(ops) if ops else []):
-            w.wait()
 
     def apply(self, x, y):
         """y = G^H (G x) for ShardedVectors windows of equal size on this partition (y may be x)."""
@@ -892,23 +880,21 @@ class ShardedApproximateInverse:
         es, code, xp, ldx = x._es, x._code, x.data_ptr(), x.ld()
         xsend, xrecv, xhalo, wsend, wrecv = self._buffers(m, es)
         # the rows of x from lower ranks
-        self._exchange(self._x_send, self._x_recv, xsend, xrecv, m * es,
-                       lambda cnt, idx, out: _lib.check(L.rlh_gather_rows(code, cnt, idx, m, xp, ldx, out, cnt)))
+        self._x_halo.post(xsend, xrecv, m * es,
+                          lambda cnt, idx, out: _lib.check(L.rlh_gather_rows(code, cnt, idx, m, xp, ldx, out, cnt)))
+        self._x_halo.wait()
         nh = self._n_xhalo
-        if len(self._x_recv) == 1:                             # one owner: its packed block is the halo block
+        if len(self._x_halo.recv) == 1:                        # one owner: its packed block is the halo block
             xhalo = xrecv
         else:
-            roff = 0
-            for _, hs, cnt in self._x_recv:                    # peer blocks (ld = cnt) -> one halo block (ld = nh)
-                _lib.check(L.rlh_copy2d(xhalo.data_ptr() + hs * es, nh * es, xrecv.data_ptr() + roff, cnt * es, cnt * es, m, 2))
-                roff += cnt * m * es
+            self._x_halo.assemble(xrecv, xhalo, nh, m, es)
         _lib.check(L.rlh_fsshard_first(plan, m, xp, ldx, xhalo.data_ptr() if nh else None, nh))
         # the rows of W from higher ranks, in the type of W
         per = -(-m // 8) * self._w_row_bytes
-        self._exchange(self._w_send, self._w_recv, wsend, wrecv, per,
-                       lambda cnt, idx, out: _lib.check(L.rlh_fsshard_pack(plan, m, cnt, idx, out)))
+        self._w_halo.post(wsend, wrecv, per, lambda cnt, idx, out: _lib.check(L.rlh_fsshard_pack(plan, m, cnt, idx, out)))
+        self._w_halo.wait()
         roff = 0
-        for _, hs, cnt in self._w_recv:
+        for _, hs, cnt in self._w_halo.recv:
             _lib.check(L.rlh_fsshard_halo(plan, m, hs, cnt, wrecv.data_ptr() + roff))
             roff += cnt * per
         _lib.check(L.rlh_fsshard_second(plan, m, y.data_ptr(), y.ld()))

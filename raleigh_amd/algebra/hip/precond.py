@@ -193,6 +193,27 @@ class IncompleteLU:
         self._chain.solve(x, y)
 
 
+# The forms of the approximate inverse's own application (`work` of ApproximateInverse and of
+# dist.ShardedApproximateInverse) and the code the library's plans take for each.
+WORK = {'native': 0, 'float32': 1, 'bf16': 2}
+
+
+def check_work(work, dtype=None, none_ok=False):
+    """Refuses a `work` that is no key of WORK (None passes with none_ok) and, once the matrix type is known, 'bf16'
+    on a complex one."""
+    if not (work in WORK or (none_ok and work is None)):
+        raise ValueError("work must be %s'native', 'float32' or 'bf16', got %r" % ('None, ' if none_ok else '', work))
+    if dtype is not None and work == 'bf16' and np.dtype(dtype).kind == 'c':
+        raise ValueError("work='bf16' is for real matrices only")
+
+
+def work_element_bytes(work, dtype):
+    """(bytes of a stored value of G and G^H, bytes of an element of W) of a `work` plan on a matrix of type dtype."""
+    es = np.dtype(dtype).itemsize
+    ev = es if work == 'native' else min(es, 8 if np.dtype(dtype).kind == 'c' else 4)
+    return ev, (2 if work == 'bf16' else ev)
+
+
 class ApproximateInverse:
     """Factorised sparse approximate inverse T = G^H G ~ A^-1 (Kolotilina-Yeremin) of a Hermitian positive definite
     matrix, built AND applied on the device (rlh_fsai_*): the preconditioner for a matrix that already lies on the
@@ -243,14 +264,13 @@ class ApproximateInverse:
     `work` plan describe the filtered G, `truncated_rows` what `max_row` held back before it.  ``drop=0`` (the default)
     is the build without filtration through the entry points it always had."""
 
-    WORK = {'native': 0, 'float32': 1, 'bf16': 2}
+    WORK = WORK
 
     def __init__(self, matrix, max_row=64, levels=1, steps=0, step_size=1, work=None, drop=0.0):
         from . import device_data
         L = self._L = _lib.lib()                          # (the handle belongs to THIS library object)
         self._h = self._plan = None
-        if work is not None and work not in self.WORK:
-            raise ValueError("work must be None, 'native', 'float32' or 'bf16', got %r" % (work,))
+        check_work(work, none_ok=True)
         self.work = work
         max_row = int(max_row)
         if not 1 <= max_row <= 64:
@@ -310,8 +330,7 @@ class ApproximateInverse:
             args = (_lib.DTYPE_CODE[self._dtype], self._n, _lib.host_ptr(indptr), _lib.host_ptr(indices),
                     _lib.host_ptr(values))
         h = ctypes.c_void_p()
-        if work == 'bf16' and np.dtype(self._dtype).kind == 'c':
-            raise ValueError("work='bf16' is for real matrices only")
+        check_work(work, self._dtype, none_ok=True)
         self._create(getattr(L, name), name, h, *args, max_row, *more)
         self._finish(h)
         if work is not None:
@@ -391,9 +410,7 @@ class ApproximateInverse:
         if self.work is None:
             return 2 * self.nnz * (es + 4) + 4 * self._n * m * es
         # with a plan: entries at 4 + sizeof V, x read and y written in the matrix type, W written and read in its own
-        cplx = np.dtype(self._dtype).kind == 'c'
-        ev = es if self.work == 'native' else min(es, 8 if cplx else 4)
-        ew = 2 if self.work == 'bf16' else ev
+        ev, ew = work_element_bytes(self.work, self._dtype)
         return 2 * self.nnz * (ev + 4) + self._n * m * (2 * es + 2 * ew)
 
     def apply(self, x, y):

@@ -316,26 +316,23 @@ struct Layout {
   }
 };
 
-constexpr const char *kCreate = "rlh_fsapply_create";
-
-int report(const ApplyStatus &s, const char *which, int64_t nnz, const char *kCreate) {
+int report(const ApplyStatus &s, const char *which, int64_t nnz, const char *entry) {
   const int code = (int)(s.err >> 56);
   const long long pos = (long long)(s.err & (((unsigned long long)1 << 56) - 1));
   switch (code) {
-    case kErrSlice: set_error("%s: broken layout of %s: slice %lld does not lie inside its array", kCreate, which, pos); break;
-    case kErrLength: set_error("%s: broken layout of %s: row %lld is longer than its slice", kCreate, which, pos); break;
-    case kErrColumn: set_error("%s: broken layout of %s: column index out of range in row %lld", kCreate, which, pos); break;
-    case kErrTail: set_error("%s: broken layout of %s: the tail of row %lld does not lie inside its array", kCreate, which, pos); break;
+    case kErrSlice: set_error("%s: broken layout of %s: slice %lld does not lie inside its array", entry, which, pos); break;
+    case kErrLength: set_error("%s: broken layout of %s: row %lld is longer than its slice", entry, which, pos); break;
+    case kErrColumn: set_error("%s: broken layout of %s: column index out of range in row %lld", entry, which, pos); break;
+    case kErrTail: set_error("%s: broken layout of %s: the tail of row %lld does not lie inside its array", entry, which, pos); break;
     default:
-      set_error("%s: broken layout of %s: it holds %llu entries, the matrix %lld", kCreate, which, s.entries, (long long)nnz);
+      set_error("%s: broken layout of %s: it holds %llu entries, the matrix %lld", entry, which, s.entries, (long long)nnz);
   }
   return 1;
 }
 
-// The layout of one orientation (a: its CSR arrays in device memory, `which` names it and kCreate the entry point in
+// The layout of one orientation (a: its CSR arrays in device memory, `which` names it and `entry` the entry point in
 // messages).
-template <typename T, typename V>
-int build_layout(Layout &L, const SpdArrays &a, const char *which, const char *kCreate = rlh::kCreate) {
+template <typename T, typename V> int build_layout(Layout &L, const SpdArrays &a, const char *which, const char *entry) {
   hipStream_t st = ctx().stream;
   const dim3 blk(kBlock);
   const int64_t n = a.rows, slices = (n + 63) / 64;
@@ -361,7 +358,7 @@ int build_layout(Layout &L, const SpdArrays &a, const char *which, const char *k
   RLH_HIP(hipMemcpyAsync(&L.tail, L.tptr + n, 8, hipMemcpyDeviceToHost, st));
   RLH_HIP(hipStreamSynchronize(st));
   RLH_REQUIRE(L.slots >= 0 && L.tail >= 0 && L.tail <= a.nnz && L.slots <= 2 * (a.nnz - L.tail),
-              "%s: inconsistent slot counts of %s", kCreate, which);
+              "%s: inconsistent slot counts of %s", entry, which);
   if (L.slots) {
     if (int rc = L.col.alloc(L.slots)) return rc;
     if (int rc = L.val.alloc((size_t)L.slots * sizeof(V))) return rc;
@@ -379,49 +376,134 @@ int build_layout(Layout &L, const SpdArrays &a, const char *which, const char *k
   RLH_HIP(hipGetLastError());
   RLH_HIP(hipMemcpyAsync(&hs, status, sizeof hs, hipMemcpyDeviceToHost, st));
   RLH_HIP(hipStreamSynchronize(st));           // the handle's arrays and the scratch are not referenced after the return
-  if (hs.err != kNoError || (int64_t)hs.entries != a.nnz) return report(hs, which, a.nnz, kCreate);
+  if (hs.err != kNoError || (int64_t)hs.entries != a.nnz) return report(hs, which, a.nnz, entry);
   return 0;
 }
 
 }  // namespace
+
+// The plan behind both families of entry points.  A row shard (rlh_fsshard_*) holds G_loc (the shard's rows of G;
+// columns: own rows, then the rows of the x-halo block) and GH_loc (the shard's rows of G^H; columns: own rows, then the
+// halo rows of W); W is [tile][n_own + n_whalo][kVT], its halo rows placed between the products from what the owners
+// packed.  The whole matrix (rlh_fsapply_*) is the plan with n_own = n and no halo rows: it launches the products
+// without SHARD and does not look at m_first / placed.
+struct FsPlan {
+  int dtype = 0, work = 0;
+  int64_t n_own = 0, n_xhalo = 0, n_whalo = 0;
+  int64_t m_first = -1, placed = 0;  // the vectors of the last rlh_fsshard_first (-1: none yet), the halo rows placed since
+  Layout g, gh;                      // G for the first product, G^H for the second
+  DevBuf<char> w;                    // W = G X
+  int64_t wrows() const { return n_own + n_whalo; }
+};
+
 }  // namespace rlh
 
-struct rlh_fsapply {
-  int dtype = 0, work = 0;
-  int64_t n = 0;
-  rlh::Layout g, gh;                // G for the first product, G^H for the second
-  rlh::DevBuf<char> w;              // W = G X as [tile][row][kVT]
-};
+struct rlh_fsapply : rlh::FsPlan {};
+struct rlh_fsshard : rlh::FsPlan {};
 
 namespace rlh {
 namespace {
 
-template <typename T, typename V> int build_both(rlh_fsapply *p, const rlh_fsai *h) {
-  if (int rc = build_layout<T, V>(p->g, spd_arrays(h->spd, 0), "G")) return rc;
-  return build_layout<T, V>(p->gh, spd_arrays(h->spd, 1), "G^H");
+// f(T(), V(), Wt()) for the types of a plan: the one place that maps (dtype, work) to them
+template <typename F> int with_types(int dtype, int work, F f) {
+  switch (dtype) {
+    case RLH_S: return work == 2 ? f(float(), float(), bf16()) : f(float(), float(), float());
+    case RLH_D: return work == 2 ? f(double(), float(), bf16()) : work == 1 ? f(double(), float(), float()) : f(double(), double(), double());
+    case RLH_C: return f(c32(), c32(), c32());
+    default: return work ? f(c64(), c32(), c32()) : f(c64(), c64(), c64());
+  }
 }
 
-template <typename T, typename V, typename Wt>
-int run_typed(rlh_fsapply *p, int64_t m, const void *X, int64_t ldx, void *Y, int64_t ldy) {
-  const int64_t tiles = (m + kVT - 1) / kVT;
-  if (int rc = p->w.reserve((size_t)tiles * (size_t)p->n * sizeof(WRow<Wt>))) return rc;   // grows once per wider block
-  WRow<Wt> *W = (WRow<Wt> *)p->w.get();
-  const dim3 blk(kBlock);
-  const unsigned gx = (unsigned)((p->g.slices + kWaves - 1) / kWaves);
-  hipStream_t st = ctx().stream;
-  for (int pass = 0; pass < 2; ++pass) {
-    for (int64_t t0 = 0; t0 < tiles; t0 += kMaxTilesY) {
-      const int64_t nt = tiles - t0 < kMaxTilesY ? tiles - t0 : kMaxTilesY, j0 = t0 * kVT;
-      const dim3 grid(gx, (unsigned)nt);
-      if (pass == 0)
-        hipLaunchKernelGGL((fsap_product<T, V, Wt, true>), grid, blk, 0, st, p->g.view(), m - j0, (const T *)X + j0 * ldx, ldx,
-                           (const WRow<Wt> *)nullptr, W + t0 * p->n, (T *)nullptr, (int64_t)0, ShardView{});
-      else
-        hipLaunchKernelGGL((fsap_product<T, V, Wt, false>), grid, blk, 0, st, p->gh.view(), m - j0, (const T *)nullptr, (int64_t)0,
-                           (const WRow<Wt> *)(W + t0 * p->n), (WRow<Wt> *)nullptr, (T *)Y + j0 * ldy, ldy, ShardView{});
-    }
-  }
+// bytes of one element of W
+int64_t w_elem_bytes(const FsPlan *p) {
+  return with_types(p->dtype, p->work, [](auto, auto, auto w) { return (int)sizeof(w); });
+}
+
+int check_work(const char *entry, int dtype, int work) {
+  RLH_REQUIRE(work >= 0 && work <= 2, "%s: work must be 0 (native), 1 (float32) or 2 (bf16), got %d", entry, work);
+  RLH_REQUIRE(work != 2 || dtype == RLH_S || dtype == RLH_D, "%s: bfloat16 work blocks are for real types only", entry);
+  return 0;
+}
+
+// f(t0, nt) for the column tiles [t0, t0 + nt) of each launch: blockIdx.y takes at most kMaxTilesY of them
+template <typename F> void for_tile_chunks(int64_t tiles, F f) {
+  for (int64_t t0 = 0; t0 < tiles; t0 += kMaxTilesY) f(t0, tiles - t0 < kMaxTilesY ? tiles - t0 : kMaxTilesY);
+}
+
+// One product on all column tiles of m vectors.  FIRST: W = L [X ; XH], else Y = L W; W has wstride rows per tile.  The
+// operands of the other product are not looked at, XH and ldxh (null: no halo block) by a SHARD product alone.
+template <typename T, typename V, typename Wt, bool FIRST, bool SHARD>
+int launch_product(const Layout &L, int64_t m, const T *X, int64_t ldx, WRow<Wt> *W, int64_t wstride, T *Y, int64_t ldy,
+                   const T *XH, int64_t ldxh) {
+  const unsigned gx = (unsigned)((L.slices + kWaves - 1) / kWaves);
+  if (!gx) return 0;                                   // (a shard may own no rows)
+  for_tile_chunks((m + kVT - 1) / kVT, [&](int64_t t0, int64_t nt) {
+    const int64_t j0 = t0 * kVT;
+    WRow<Wt> *w = W + t0 * wstride;
+    const ShardView sv = SHARD ? ShardView{XH ? XH + j0 * ldxh : nullptr, ldxh, wstride} : ShardView{};
+    if constexpr (FIRST)
+      hipLaunchKernelGGL((fsap_product<T, V, Wt, true, SHARD>), dim3(gx, (unsigned)nt), dim3(kBlock), 0, ctx().stream, L.view(),
+                         m - j0, X + j0 * ldx, ldx, (const WRow<Wt> *)nullptr, w, (T *)nullptr, (int64_t)0, sv);
+    else
+      hipLaunchKernelGGL((fsap_product<T, V, Wt, false, SHARD>), dim3(gx, (unsigned)nt), dim3(kBlock), 0, ctx().stream, L.view(),
+                         m - j0, (const T *)nullptr, (int64_t)0, (const WRow<Wt> *)w, (WRow<Wt> *)nullptr, Y + j0 * ldy, ldy, sv);
+  });
   RLH_HIP(hipGetLastError());
+  return 0;
+}
+
+// W = G [X ; XH] of the plan, W grown to the block's tiles first
+template <bool SHARD> int first_product(FsPlan *p, int64_t m, const void *X, int64_t ldx, const void *XH, int64_t ldxh) {
+  return with_types(p->dtype, p->work, [&](auto t, auto v, auto w) {
+    using T = decltype(t);
+    using Wt = decltype(w);
+    const int64_t tiles = (m + kVT - 1) / kVT;
+    if (int rc = p->w.reserve((size_t)tiles * (size_t)p->wrows() * sizeof(WRow<Wt>))) return rc;   // grows once per wider block
+    return launch_product<T, decltype(v), Wt, true, SHARD>(p->g, m, (const T *)X, ldx, (WRow<Wt> *)p->w.get(), p->wrows(),
+                                                           (T *)nullptr, 0, (const T *)XH, ldxh);
+  });
+}
+
+// Y = G^H W of the plan
+template <bool SHARD> int second_product(FsPlan *p, int64_t m, void *Y, int64_t ldy) {
+  return with_types(p->dtype, p->work, [&](auto t, auto v, auto w) {
+    using T = decltype(t);
+    using Wt = decltype(w);
+    return launch_product<T, decltype(v), Wt, false, SHARD>(p->gh, m, (const T *)nullptr, 0, (WRow<Wt> *)p->w.get(), p->wrows(),
+                                                            (T *)Y, ldy, (const T *)nullptr, 0);
+  });
+}
+
+template <typename P> int plan_destroy(P *p) {
+  if (!p) return 0;
+  if (ctx().ready) (void)hipStreamSynchronize(ctx().stream);
+  delete p;
+  return 0;
+}
+
+// A new plan of the handle type P: build(p) makes its layouts; *pp is set when that succeeds
+template <typename P, typename Build>
+int make_plan(P **pp, int dtype, int work, int64_t n_own, int64_t n_xhalo, int64_t n_whalo, Build build) {
+  P *p = new P();
+  p->dtype = dtype;
+  p->work = work;
+  p->n_own = n_own;
+  p->n_xhalo = n_xhalo;
+  p->n_whalo = n_whalo;
+  if (int rc = build(p)) {
+    plan_destroy(p);
+    return rc;
+  }
+  *pp = p;
+  return 0;
+}
+
+int plan_info(const char *entry, const FsPlan *p, int *work, int64_t *stored_slots, int64_t *tail_entries, int64_t *device_bytes) {
+  RLH_REQUIRE(p, "%s: null plan", entry);
+  if (work) *work = p->work;
+  if (stored_slots) *stored_slots = p->g.slots + p->gh.slots;
+  if (tail_entries) *tail_entries = p->g.tail + p->gh.tail;
+  if (device_bytes) *device_bytes = p->g.bytes() + p->gh.bytes() + (int64_t)p->w.bytes();
   return 0;
 }
 
@@ -431,85 +513,43 @@ int run_typed(rlh_fsapply *p, int64_t m, const void *X, int64_t ldx, void *Y, in
 using namespace rlh;
 
 extern "C" int rlh_fsapply_create(rlh_fsapply_t *pp, rlh_fsai_t h, int work) {
+  constexpr const char *kEntry = "rlh_fsapply_create";
   if (int rc = require_ready()) return rc;
   RLH_REQUIRE(pp != nullptr, "rlh_fsapply_create: null plan pointer");
   *pp = nullptr;
   RLH_REQUIRE(h != nullptr, "rlh_fsapply_create: null handle");
-  RLH_REQUIRE(work >= 0 && work <= 2, "rlh_fsapply_create: work must be 0 (native), 1 (float32) or 2 (bf16), got %d", work);
-  RLH_REQUIRE(work != 2 || h->dtype == RLH_S || h->dtype == RLH_D, "rlh_fsapply_create: bfloat16 work blocks are for real types only");
-  rlh_fsapply *p = new rlh_fsapply();
-  p->dtype = h->dtype;
-  p->work = work;
-  p->n = h->n;
-  int rc = 0;
-  if (h->n > 0 && h->spd) {
-    switch (h->dtype) {
-      case RLH_S: rc = build_both<float, float>(p, h); break;
-      case RLH_D: rc = work ? build_both<double, float>(p, h) : build_both<double, double>(p, h); break;
-      case RLH_C: rc = build_both<c32, c32>(p, h); break;
-      default: rc = work ? build_both<c64, c32>(p, h) : build_both<c64, c64>(p, h);
-    }
-  }
-  if (rc) {
-    rlh_fsapply_destroy(p);
-    return rc;
-  }
-  *pp = p;
-  return 0;
+  if (int rc = check_work(kEntry, h->dtype, work)) return rc;
+  return make_plan(pp, h->dtype, work, h->n, 0, 0, [&](FsPlan *p) {
+    if (h->n == 0 || !h->spd) return 0;
+    return with_types(h->dtype, work, [&](auto t, auto v, auto) {
+      using T = decltype(t);
+      using V = decltype(v);
+      if (int rc = build_layout<T, V>(p->g, spd_arrays(h->spd, 0), "G", kEntry)) return rc;
+      return build_layout<T, V>(p->gh, spd_arrays(h->spd, 1), "G^H", kEntry);
+    });
+  });
 }
 
 extern "C" int rlh_fsapply_run(rlh_fsapply_t p, int64_t m, const void *X, int64_t ldx, void *Y, int64_t ldy) {
   if (int rc = require_ready()) return rc;
   RLH_REQUIRE(p, "rlh_fsapply_run: null plan");
   RLH_REQUIRE(m >= 0, "rlh_fsapply_run: negative number of vectors");
-  if (m == 0 || p->n == 0) return 0;
+  if (m == 0 || p->n_own == 0) return 0;
   RLH_REQUIRE(X && Y, "rlh_fsapply_run: null pointer");
-  RLH_REQUIRE(ldx >= p->n && ldy >= p->n, "rlh_fsapply_run: Matrix and vectors dimensions incompatible");
-  switch (p->dtype) {
-    case RLH_S:
-      return p->work == 2 ? run_typed<float, float, bf16>(p, m, X, ldx, Y, ldy) : run_typed<float, float, float>(p, m, X, ldx, Y, ldy);
-    case RLH_D:
-      return p->work == 2   ? run_typed<double, float, bf16>(p, m, X, ldx, Y, ldy)
-             : p->work == 1 ? run_typed<double, float, float>(p, m, X, ldx, Y, ldy)
-                            : run_typed<double, double, double>(p, m, X, ldx, Y, ldy);
-    case RLH_C: return run_typed<c32, c32, c32>(p, m, X, ldx, Y, ldy);
-    default:
-      return p->work ? run_typed<c64, c32, c32>(p, m, X, ldx, Y, ldy) : run_typed<c64, c64, c64>(p, m, X, ldx, Y, ldy);
-  }
+  RLH_REQUIRE(ldx >= p->n_own && ldy >= p->n_own, "rlh_fsapply_run: Matrix and vectors dimensions incompatible");
+  if (int rc = first_product<false>(p, m, X, ldx, nullptr, 0)) return rc;
+  return second_product<false>(p, m, Y, ldy);
 }
 
 extern "C" int rlh_fsapply_info(rlh_fsapply_t p, int *work, int64_t *stored_slots, int64_t *tail_entries, int64_t *device_bytes) {
-  RLH_REQUIRE(p, "rlh_fsapply_info: null plan");
-  if (work) *work = p->work;
-  if (stored_slots) *stored_slots = p->g.slots + p->gh.slots;
-  if (tail_entries) *tail_entries = p->g.tail + p->gh.tail;
-  if (device_bytes) *device_bytes = p->g.bytes() + p->gh.bytes() + (int64_t)p->w.bytes();
-  return 0;
+  return plan_info("rlh_fsapply_info", p, work, stored_slots, tail_entries, device_bytes);
 }
 
-extern "C" int rlh_fsapply_destroy(rlh_fsapply_t p) {
-  if (!p) return 0;
-  if (ctx().ready) (void)hipStreamSynchronize(ctx().stream);
-  delete p;
-  return 0;
-}
+extern "C" int rlh_fsapply_destroy(rlh_fsapply_t p) { return plan_destroy(p); }
 
 // ---------------------------------------------------------------- the application on a row shard (rlh_fsshard_*)
-// G_loc (the shard's rows of G; columns: own rows, then the rows of the x-halo block) and GH_loc (the shard's rows of
-// G^H; columns: own rows, then the halo rows of W) go through the same layout and the same two products; W is
-// [tile][n_own + n_whalo][kVT], its halo rows placed between the products from what the owners packed.
-struct rlh_fsshard {
-  int dtype = 0, work = 0;
-  int64_t n_own = 0, n_xhalo = 0, n_whalo = 0;
-  int64_t m_first = -1, placed = 0;  // the vectors of the last rlh_fsshard_first (-1: none yet), the halo rows placed since
-  rlh::Layout g, gh;
-  rlh::DevBuf<char> w;
-};
-
 namespace rlh {
 namespace {
-
-constexpr const char *kShardCreate = "rlh_fsshard_create";
 
 // dst row (drow0 + i) of tile t <- src row (idx ? idx[i] : i) of tile t, i < nrows, as 16-byte pieces (`pieces` per row;
 // the strides count rows).  An index outside [0, bound) is not followed: the row is written as zeros.
@@ -525,37 +565,17 @@ __global__ __launch_bounds__(kBlock) void fsap_rows(int64_t nrows, int pieces, c
   dst[(tile * dstride + drow0 + i) * pieces + q] = v;
 }
 
-int move_rows(int64_t tiles, int64_t nrows, int pieces, const int64_t *idx, int64_t bound, const void *src, int64_t sstride,
+// fsap_rows on the tiles of m vectors of the plan's W
+int move_rows(const FsPlan *p, int64_t m, int64_t nrows, const int64_t *idx, int64_t bound, const void *src, int64_t sstride,
               void *dst, int64_t dstride, int64_t drow0) {
+  const int pieces = (int)(kVT * w_elem_bytes(p) / 16);
   const unsigned gx = (unsigned)((nrows * pieces + kBlock - 1) / kBlock);
-  for (int64_t t0 = 0; t0 < tiles; t0 += kMaxTilesY) {
-    const int64_t nt = tiles - t0 < kMaxTilesY ? tiles - t0 : kMaxTilesY;
+  for_tile_chunks((m + kVT - 1) / kVT, [&](int64_t t0, int64_t nt) {
     hipLaunchKernelGGL(fsap_rows, dim3(gx, (unsigned)nt), dim3(kBlock), 0, ctx().stream, nrows, pieces, idx, bound,
                        (const uint4 *)src + t0 * sstride * pieces, sstride, (uint4 *)dst + t0 * dstride * pieces, dstride, drow0);
-  }
+  });
   RLH_HIP(hipGetLastError());
   return 0;
-}
-
-// bytes of one element of W
-int64_t w_elem_bytes(int dtype, int work) {
-  if (work == 2) return 2;
-  switch (dtype) {
-    case RLH_S: return 4;
-    case RLH_D: return work ? 4 : 8;
-    case RLH_C: return 8;
-    default: return work ? 8 : 16;
-  }
-}
-
-// f(T(), V(), Wt()) for the types of a plan
-template <typename F> int with_types(int dtype, int work, F f) {
-  switch (dtype) {
-    case RLH_S: return work == 2 ? f(float(), float(), bf16()) : f(float(), float(), float());
-    case RLH_D: return work == 2 ? f(double(), float(), bf16()) : work == 1 ? f(double(), float(), float()) : f(double(), double(), double());
-    case RLH_C: return f(c32(), c32(), c32());
-    default: return work ? f(c64(), c32(), c32()) : f(c64(), c64(), c64());
-  }
 }
 
 // one orientation: the host arrays into device memory, then the layout (the uploads go when this returns)
@@ -571,37 +591,7 @@ int shard_layout(Layout &L, int64_t rows, int64_t cols, const int64_t *ip, const
   SpdArrays a;
   a.rows = rows; a.cols = cols; a.nnz = nnz;
   a.indptr = dip; a.idx = dix; a.val = dva.get();
-  return build_layout<T, V>(L, a, which, kShardCreate);
-}
-
-template <typename T, typename V, typename Wt>
-int shard_first(rlh_fsshard *p, int64_t m, const void *X, int64_t ldx, const void *XH, int64_t ldxh) {
-  const int64_t tiles = (m + kVT - 1) / kVT, wrows = p->n_own + p->n_whalo;
-  if (int rc = p->w.reserve((size_t)tiles * (size_t)wrows * sizeof(WRow<Wt>))) return rc;
-  WRow<Wt> *W = (WRow<Wt> *)p->w.get();
-  const unsigned gx = (unsigned)((p->g.slices + kWaves - 1) / kWaves);
-  for (int64_t t0 = 0; t0 < tiles && gx; t0 += kMaxTilesY) {
-    const int64_t nt = tiles - t0 < kMaxTilesY ? tiles - t0 : kMaxTilesY, j0 = t0 * kVT;
-    const ShardView sv{XH ? (const void *)((const T *)XH + j0 * ldxh) : nullptr, ldxh, wrows};
-    hipLaunchKernelGGL((fsap_product<T, V, Wt, true, true>), dim3(gx, (unsigned)nt), dim3(kBlock), 0, ctx().stream, p->g.view(),
-                       m - j0, (const T *)X + j0 * ldx, ldx, (const WRow<Wt> *)nullptr, W + t0 * wrows, (T *)nullptr, (int64_t)0, sv);
-  }
-  RLH_HIP(hipGetLastError());
-  return 0;
-}
-
-template <typename T, typename V, typename Wt> int shard_second(rlh_fsshard *p, int64_t m, void *Y, int64_t ldy) {
-  const int64_t tiles = (m + kVT - 1) / kVT, wrows = p->n_own + p->n_whalo;
-  const WRow<Wt> *W = (const WRow<Wt> *)p->w.get();
-  const unsigned gx = (unsigned)((p->gh.slices + kWaves - 1) / kWaves);
-  for (int64_t t0 = 0; t0 < tiles && gx; t0 += kMaxTilesY) {
-    const int64_t nt = tiles - t0 < kMaxTilesY ? tiles - t0 : kMaxTilesY, j0 = t0 * kVT;
-    const ShardView sv{nullptr, 0, wrows};
-    hipLaunchKernelGGL((fsap_product<T, V, Wt, false, true>), dim3(gx, (unsigned)nt), dim3(kBlock), 0, ctx().stream, p->gh.view(),
-                       m - j0, (const T *)nullptr, (int64_t)0, W + t0 * wrows, (WRow<Wt> *)nullptr, (T *)Y + j0 * ldy, ldy, sv);
-  }
-  RLH_HIP(hipGetLastError());
-  return 0;
+  return build_layout<T, V>(L, a, which, "rlh_fsshard_create");
 }
 
 // indptr[0] == 0 and non-decreasing
@@ -622,8 +612,7 @@ extern "C" int rlh_fsshard_create(rlh_fsshard_t *pp, int dtype, int work, int64_
   RLH_REQUIRE(pp != nullptr, "rlh_fsshard_create: null plan pointer");
   *pp = nullptr;
   RLH_REQUIRE(dtype == RLH_S || dtype == RLH_D || dtype == RLH_C || dtype == RLH_Z, "rlh_fsshard_create: unknown dtype %d", dtype);
-  RLH_REQUIRE(work >= 0 && work <= 2, "rlh_fsshard_create: work must be 0 (native), 1 (float32) or 2 (bf16), got %d", work);
-  RLH_REQUIRE(work != 2 || dtype == RLH_S || dtype == RLH_D, "rlh_fsshard_create: bfloat16 work blocks are for real types only");
+  if (int rc = check_work("rlh_fsshard_create", dtype, work)) return rc;
   RLH_REQUIRE(n_own >= 0 && n_xhalo >= 0 && n_whalo >= 0, "rlh_fsshard_create: negative size");
   RLH_REQUIRE(n_own + n_xhalo <= INT32_MAX && n_own + n_whalo <= INT32_MAX, "rlh_fsshard_create: more than 2^31 - 1 columns");
   RLH_REQUIRE(g_indptr && gh_indptr, "rlh_fsshard_create: null indptr");
@@ -633,26 +622,15 @@ extern "C" int rlh_fsshard_create(rlh_fsshard_t *pp, int dtype, int work, int64_
   RLH_REQUIRE(bad < 0, "rlh_fsshard_create: indptr of G^H must start at 0 and not decrease (row %lld)", (long long)(bad ? bad - 1 : 0));
   RLH_REQUIRE((g_indptr[n_own] == 0 || (g_indices && g_values)) && (gh_indptr[n_own] == 0 || (gh_indices && gh_values)),
               "rlh_fsshard_create: null indices or values");
-  rlh_fsshard *p = new rlh_fsshard();
-  p->dtype = dtype;
-  p->work = work;
-  p->n_own = n_own;
-  p->n_xhalo = n_xhalo;
-  p->n_whalo = n_whalo;
-  int rc = 0;
-  if (n_own > 0)
-    rc = with_types(dtype, work, [&](auto t, auto v, auto) {
+  return make_plan(pp, dtype, work, n_own, n_xhalo, n_whalo, [&](FsPlan *p) {
+    if (n_own == 0) return 0;
+    return with_types(dtype, work, [&](auto t, auto v, auto) {
       using T = decltype(t);
       using V = decltype(v);
-      if (int r = shard_layout<T, V>(p->g, n_own, n_own + n_xhalo, g_indptr, g_indices, g_values, "G")) return r;
+      if (int rc = shard_layout<T, V>(p->g, n_own, n_own + n_xhalo, g_indptr, g_indices, g_values, "G")) return rc;
       return shard_layout<T, V>(p->gh, n_own, n_own + n_whalo, gh_indptr, gh_indices, gh_values, "G^H");
     });
-  if (rc) {
-    rlh_fsshard_destroy(p);
-    return rc;
-  }
-  *pp = p;
-  return 0;
+  });
 }
 
 extern "C" int rlh_fsshard_first(rlh_fsshard_t p, int64_t m, const void *X, int64_t ldx, const void *XH, int64_t ldxh) {
@@ -667,10 +645,7 @@ extern "C" int rlh_fsshard_first(rlh_fsshard_t p, int64_t m, const void *X, int6
   p->m_first = -1;
   p->placed = 0;
   if (m > 0)
-    if (int rc = with_types(p->dtype, p->work, [&](auto t, auto v, auto w) {
-          return shard_first<decltype(t), decltype(v), decltype(w)>(p, m, X, ldx, p->n_xhalo ? XH : nullptr, ldxh);
-        }))
-      return rc;
+    if (int rc = first_product<true>(p, m, X, ldx, p->n_xhalo ? XH : nullptr, ldxh)) return rc;
   p->m_first = m;
   return 0;
 }
@@ -683,8 +658,7 @@ extern "C" int rlh_fsshard_pack(rlh_fsshard_t p, int64_t m, int64_t nidx, const 
   RLH_REQUIRE(p->m_first == m, "rlh_fsshard_pack: no rlh_fsshard_first with %lld vectors came before", (long long)m);
   if (m == 0 || nidx == 0) return 0;
   RLH_REQUIRE(d_idx && out, "rlh_fsshard_pack: null pointer");
-  const int64_t tiles = (m + kVT - 1) / kVT, wrows = p->n_own + p->n_whalo;
-  return move_rows(tiles, nidx, (int)(kVT * w_elem_bytes(p->dtype, p->work) / 16), d_idx, p->n_own, p->w.get(), wrows, out, nidx, 0);
+  return move_rows(p, m, nidx, d_idx, p->n_own, p->w.get(), p->wrows(), out, nidx, 0);
 }
 
 extern "C" int rlh_fsshard_halo(rlh_fsshard_t p, int64_t m, int64_t first, int64_t count, const void *src) {
@@ -696,10 +670,7 @@ extern "C" int rlh_fsshard_halo(rlh_fsshard_t p, int64_t m, int64_t first, int64
   RLH_REQUIRE(p->m_first == m, "rlh_fsshard_halo: no rlh_fsshard_first with %lld vectors came before", (long long)m);
   if (m > 0 && count > 0) {
     RLH_REQUIRE(src, "rlh_fsshard_halo: null pointer");
-    const int64_t tiles = (m + kVT - 1) / kVT, wrows = p->n_own + p->n_whalo;
-    if (int rc = move_rows(tiles, count, (int)(kVT * w_elem_bytes(p->dtype, p->work) / 16), nullptr, count, src, count, p->w.get(),
-                           wrows, p->n_own + first))
-      return rc;
+    if (int rc = move_rows(p, m, count, nullptr, count, src, count, p->w.get(), p->wrows(), p->n_own + first)) return rc;
   }
   p->placed += count;
   return 0;
@@ -717,25 +688,14 @@ extern "C" int rlh_fsshard_second(rlh_fsshard_t p, int64_t m, void *Y, int64_t l
   if (m == 0 || p->n_own == 0) return 0;
   RLH_REQUIRE(Y, "rlh_fsshard_second: null pointer");
   RLH_REQUIRE(ldy >= p->n_own, "rlh_fsshard_second: Matrix and vectors dimensions incompatible");
-  return with_types(p->dtype, p->work, [&](auto t, auto v, auto w) {
-    return shard_second<decltype(t), decltype(v), decltype(w)>(p, m, Y, ldy);
-  });
+  return second_product<true>(p, m, Y, ldy);
 }
 
 extern "C" int rlh_fsshard_info(rlh_fsshard_t p, int *work, int64_t *stored_slots, int64_t *tail_entries, int64_t *device_bytes,
                                 int64_t *w_row_bytes) {
-  RLH_REQUIRE(p, "rlh_fsshard_info: null plan");
-  if (work) *work = p->work;
-  if (stored_slots) *stored_slots = p->g.slots + p->gh.slots;
-  if (tail_entries) *tail_entries = p->g.tail + p->gh.tail;
-  if (device_bytes) *device_bytes = p->g.bytes() + p->gh.bytes() + (int64_t)p->w.bytes();
-  if (w_row_bytes) *w_row_bytes = kVT * w_elem_bytes(p->dtype, p->work);
+  if (int rc = plan_info("rlh_fsshard_info", p, work, stored_slots, tail_entries, device_bytes)) return rc;
+  if (w_row_bytes) *w_row_bytes = kVT * w_elem_bytes(p);
   return 0;
 }
 
-extern "C" int rlh_fsshard_destroy(rlh_fsshard_t p) {
-  if (!p) return 0;
-  if (ctx().ready) (void)hipStreamSynchronize(ctx().stream);
-  delete p;
-  return 0;
-}
+extern "C" int rlh_fsshard_destroy(rlh_fsshard_t p) { return plan_destroy(p); }
