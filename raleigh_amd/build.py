@@ -16,7 +16,7 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, 'csrc')
 LIBDIR = os.path.join(PKG, 'lib')
 LIBPATH = os.path.join(LIBDIR, 'librlhip.so')
-SOURCES = ['context', 'gram', 'update', 'spmm', 'spmm_wide_build', 'spmm_build_device', 'spmm_wide_s', 'spmm_wide_d', 'spmm_wide_c',
+SOURCES = ['context', 'gram', 'update', 'spmm', 'spmm_build', 'spmm_wide_build', 'spmm_build_device', 'spmm_wide_s', 'spmm_wide_d', 'spmm_wide_c',
            'spmm_wide_z', 'spmm_wide_bf16', 'sptrsv', 'dense', 'spmm_data', 'dense_bytes', 'fsai', 'fsai_apply']
 HOST_SOURCES = ['ldlt_host', 'shm_reduce']        # plain C++ (host only): compiled by the same driver, no offload
 FLAGS = ['-O3', '--offload-arch=gfx950', '-fPIC', '-std=c++17', '-Wno-unused-result']

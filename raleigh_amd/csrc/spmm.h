@@ -1,4 +1,5 @@
-// Shared declarations of the sparse operator (K13): the handle, the host-side window analysis and
+// Shared declarations of the sparse operator (K13): the handle, the constants and entry storage of the
+// 1024-row layouts (kernels: spmm.hip, host builder: spmm_build.hip), the host-side window analysis and
 // the XCD-aware launch order used by both windowed layouts (spmm.hip, spmm_wide.inc).
 #pragma once
 
@@ -137,10 +138,11 @@ struct rlh_csr {
   rlh::DevBuf<int32_t> well_gsrc;    // device: first column of every 64-entry staging group
   rlh::DevBuf<uint16_t> well_idx;    // device: position of the entry's column in the staged image
   rlh::DevBuf<void> well_vals;       // device
-  double well_ratio = 0.0;           // staged elements per stored entry slot (diagnostic)
   rlh::LaunchOrder well_launch;      // of the blocks
-  int well_inbounds = 0;             // every staging group lies inside [0, n_cols)
-  int well_aligned = 0;              // every staging group starts on a multiple of 8 columns
+  // the staging of whichever windowed layout the handle has (set by well_build, wide_build and wide_build_device; the stacks: stk_aligned, stk_overhang)
+  double stage_ratio = 0.0;          // staged elements per stored entry slot (diagnostic; set even where no layout qualifies)
+  int stage_inbounds = 0;            // every staging group lies inside [0, n_cols)
+  int stage_aligned = 0;             // every staging group starts on a multiple of 8 columns
   // the same layout over STACKS of row blocks (spmm.hip, "Stacked blocks"): a workgroup takes kStkR 1024-row blocks whose
   // windows overlap (for a 3-D stencil two blocks one grid plane apart) and stages the union of their windows once
   int64_t stk_blocks = 0;            // stacks; 0: not built
@@ -183,6 +185,32 @@ struct ChebArgs {
   const T *B; int64_t ldb;
   double cy, cp, cb;
 };
+
+// ---- the 1024-row windowed layout and its stacks (kernels: spmm.hip; host builder: spmm_build.hip)
+constexpr int kWellRows = 1024;
+template <typename T> struct WellCfg { static constexpr int SMAX = sizeof(T) >= 16 ? 4 : 8; };   // <= 64 KiB per buffer
+constexpr int kStkR = 2;                           // row blocks per stack
+constexpr int kStkBufBytes = 80 * 1024;            // per staging buffer
+constexpr int kStkLdsBytes = 160 * 1024;
+// slots of the ring: four of 40 KB, or -- 16-byte elements, whose image of one vector is as large as two of the others'
+// -- two of 80 KB (the bytes in flight are what counts, not the vectors)
+template <typename T> struct StkRing { static constexpr int NB = sizeof(T) >= 16 ? 2 : 4, SLOT = kStkLdsBytes / NB; };
+constexpr int kStkMaxPatterns = 4096;
+constexpr int kStkMaxDeltas = 64;                  // position patterns per member of a stack
+
+// Entry storage of a block: slot t of thread l (row l of the block) lives in 16-byte pieces per
+// thread -- values [t / VPG][l][t % VPG] with VPG = 16 / sizeof(T) values per piece, positions
+// [t / 8][l][t % 8] -- so that a thread fetches its row's entries with a few 16-byte loads (one
+// 4- or 8-byte and one 2-byte load per entry cost as many vector-memory instructions as all the
+// staging of the block).  A block's slots are padded to a multiple of 8; eoff counts slots.
+template <typename T>
+__host__ __device__ inline int64_t well_val_index(int64_t eoff, int t, int l) {
+  constexpr int VPG = 16 / (int)sizeof(T) > 0 ? 16 / (int)sizeof(T) : 1;
+  return (eoff + (t / VPG) * VPG) * 1024 + (int64_t)l * VPG + (t % VPG);
+}
+__host__ __device__ inline int64_t well_idx_index(int64_t eoff, int t, int l) {
+  return (eoff + (t / 8) * 8) * 1024 + (int64_t)l * 8 + (t % 8);
+}
 
 // ---- element helpers shared by the SpMM kernels
 __device__ __forceinline__ float nt_load(const float *p) { return __builtin_nontemporal_load(p); }
@@ -283,12 +311,6 @@ static inline int32_t find_windows_of(std::vector<int32_t> &cols, int64_t nc, in
   return (off + unit - 1) / unit * unit;
 }
 
-static inline int32_t find_windows(const int64_t *indptr, const int32_t *indices, int64_t r0, int64_t r1, int64_t nc,
-                                   int gap, int gs, int round_groups, std::vector<Win> &ws) {
-  std::vector<int32_t> cols(indices + indptr[r0], indices + indptr[r1]);
-  return find_windows_of(cols, nc, gap, gs, round_groups, ws);
-}
-
 // position of column c in the staged image (last window starting at or before c)
 static inline int32_t staged_position(const std::vector<Win> &ws, int32_t c) {
   size_t lo = 0, hi = ws.size();
@@ -318,18 +340,19 @@ static inline void fill_group_sources(const std::vector<Win> &ws, int32_t ngroup
   for (; filled < ngroups; ++filled) gsrc[filled] = last;
 }
 
-// host buffer whose elements are NOT zeroed at allocation (std::vector would fill 0.6 GB serially before the host threads
-// overwrite every element of it; left alone, the pages are first touched by the threads that fill them)
-template <typename E> struct RawBuf {
-  std::unique_ptr<E[]> p;
-  size_t n;
-  explicit RawBuf(size_t count) : p(new E[count > 0 ? count : 1]), n(count) {}
-  E &operator[](size_t i) { return p[i]; }
-  const E &operator[](size_t i) const { return p[i]; }
-  E *data() { return p.get(); }
-  const E *data() const { return p.get(); }
-  size_t size() const { return n; }
-};
+// what the 16-byte staging path may assume of a layout's staging groups (`gs` columns each, first columns in `gsrc`):
+// *inbounds (if asked): every group inside [0, n_cols); *aligned: every group starts on a multiple of 8 columns;
+// returns the columns the furthest group reaches past n_cols (0: none)
+static inline int64_t stage_flags(const int32_t *gsrc, int64_t ngroups, int gs, int64_t n_cols, int *inbounds, int *aligned) {
+  int64_t overhang = 0;
+  *aligned = 1;
+  for (int64_t g = 0; g < ngroups; ++g) {
+    overhang = std::max(overhang, (int64_t)gsrc[g] + gs - n_cols);
+    if (gsrc[g] & 7) *aligned = 0;
+  }
+  if (inbounds) *inbounds = overhang == 0;
+  return overhang;
+}
 
 // RLH_SPMM_VERBOSE=1: wall time of the phases of a layout build on stderr
 struct PhaseClock {
@@ -361,6 +384,50 @@ static void parallel_blocks(int64_t nblocks, F fn) {
   for (unsigned t = 1; t < nt; ++t) pool.emplace_back(worker);
   worker();
   for (auto &t : pool) t.join();
+}
+
+// The rows cut into uniform blocks of `rows`: per block its longest row and its column windows in staging groups of `gs` columns (find_windows_of; the group
+// count a multiple of `round_groups`); over all blocks the largest of either, the staged columns and the entry slots (longest row x rows): their ratio decides whether staging pays.
+struct BlockAnalysis {
+  std::vector<std::vector<Win>> wins;
+  std::vector<int32_t> width, ngroups;
+  int32_t wmax = 0, gmax = 0;
+  int64_t staged = 0, slots = 0;
+  explicit BlockAnalysis(size_t nblocks) : wins(nblocks), width(nblocks, 0), ngroups(nblocks, 0) {}
+  double ratio() const { return slots > 0 ? (double)staged / (double)slots : 0.0; }
+};
+static inline BlockAnalysis analyse_blocks(const int64_t *indptr, const int32_t *indices, int64_t n, int64_t nc, int rows, int gs, int round_groups) {
+  const int64_t nblocks = (n + rows - 1) / rows;
+  BlockAnalysis a((size_t)nblocks);
+  parallel_blocks(nblocks, [&](int64_t b) {
+    const int64_t r0 = b * rows, r1 = (r0 + rows < n) ? r0 + rows : n;
+    int64_t w = 0;
+    for (int64_t r = r0; r < r1; ++r) w = std::max<int64_t>(w, indptr[r + 1] - indptr[r]);
+    a.width[b] = (int32_t)std::min<int64_t>(w, 1 << 20);
+    std::vector<int32_t> cols(indices + indptr[r0], indices + indptr[r1]);
+    a.ngroups[b] = find_windows_of(cols, nc, 32, gs, round_groups, a.wins[b]) / gs;
+  });
+  for (int64_t b = 0; b < nblocks; ++b) {
+    a.wmax = std::max(a.wmax, a.width[b]);
+    a.gmax = std::max(a.gmax, a.ngroups[b]);
+    a.staged += (int64_t)a.ngroups[b] * gs;
+    a.slots += (int64_t)a.width[b] * rows;
+  }
+  return a;
+}
+
+// fn(b, c, ov) for every window of unit b and every granule c (rows [c * rows, (c + 1) * rows)) of which it covers ov > 0 rows, in the order of the
+// units, their windows and the granules (the tie-breaks of the stack matching and of well_group_fill see it); halo columns are not rows of this shard
+template <typename F>
+static inline void for_each_overlap(const std::vector<std::vector<Win>> &wins, int64_t nunits, int64_t n_rows, int rows, F fn) {
+  for (int64_t b = 0; b < nunits; ++b)
+    for (const Win &w : wins[(size_t)b]) {
+      const int64_t lo = w.start, hi = std::min<int64_t>((int64_t)w.start + w.len, n_rows);
+      for (int64_t c = lo / rows; c * rows < hi; ++c) {
+        const int64_t ov = std::min<int64_t>(hi, (c + 1) * rows) - std::max<int64_t>(lo, c * rows);
+        if (ov > 0) fn(b, c, ov);
+      }
+    }
 }
 
 // Launch groups on the block-overlap graph.  A group is the `per_xcd` units one XCD works on at the same time: what it
@@ -443,19 +510,12 @@ static inline void well_schedule(const std::vector<std::vector<Win>> &wins, int6
   }
   // overlap graph: weight = rows of unit c that unit b stages (both directions)
   WellGraph adj((size_t)nblocks);
-  for (int64_t b = 0; b < nblocks; ++b)
-    for (const auto &w : wins[b]) {
-      int64_t lo = w.start, hi = (int64_t)w.start + w.len;
-      if (hi > n_rows) hi = n_rows;                 // halo columns are not rows of this shard
-      for (int64_t c = lo / rows_per_block; c * rows_per_block < hi; ++c) {
-        const int64_t u = owner ? (*owner)[(size_t)c] : c;
-        if (u == b || u < 0) continue;
-        const int64_t ov = std::min<int64_t>(hi, (c + 1) * rows_per_block) - std::max<int64_t>(lo, c * rows_per_block);
-        if (ov <= 0) continue;
-        adj[b].push_back({(int32_t)u, (int32_t)ov});
-        adj[u].push_back({(int32_t)b, (int32_t)ov});
-      }
-    }
+  for_each_overlap(wins, nblocks, n_rows, rows_per_block, [&](int64_t b, int64_t c, int64_t ov) {
+    const int64_t u = owner ? (*owner)[(size_t)c] : c;
+    if (u == b || u < 0) return;
+    adj[b].push_back({(int32_t)u, (int32_t)ov});
+    adj[u].push_back({(int32_t)b, (int32_t)ov});
+  });
   std::vector<char> done((size_t)nblocks, 0);
   std::vector<int64_t> weight((size_t)nblocks, 0);
   int64_t seed = 0;

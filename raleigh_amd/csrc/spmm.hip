@@ -4,7 +4,7 @@
 // 'SUNF'/'HUNF' descriptor on the column-major n x m block
 // (raleigh/algebra/sparse_mkl.py:16-48, raleigh/algebra/mkl_wrap.py:204-276).
 // Here the caller hands over the FULL 0-based CSR (both triangles); at creation it is re-laid-out
-// on the host in one of three device layouts (rlh_csr_layout reports which):
+// on the host (spmm_build.hip, spmm_wide_build.hip) in one of three device layouts (rlh_csr_layout reports which):
 //  * 1024-row windowed ELL (this file, well_spmm_kernel): rows of at most 8 entries of a real
 //    type with column locality -- stencils.  A block's column windows are staged through the LDS,
 //    the row's entries stay in registers for all vectors.  Measured 54.6 % of the 8 TB/s peak on
@@ -15,8 +15,6 @@
 //  * sliced ELLPACK, slice height 64 (sell_spmm_kernel): no column locality.  One 8-byte gather of
 //    X per stored entry and vector; limited by the rate at which a CU retires per-lane gathers
 //    (profiles/r01_spmm_sweep2.txt), not by HBM: 34 % on the 7-point Laplacian.
-#include <unordered_map>
-
 #include "spmm.h"
 
 namespace rlh {
@@ -190,21 +188,7 @@ static int launch_spmm(const rlh_csr *h, int64_t m, const T *X, int64_t ldx, int
 // Each element of X is then loaded once per window it lies in (3.4x for the 7-point stencil on
 // 215^3: centre + y neighbours in one window, the two z planes in one each) instead of once per
 // entry (7x), and the seven reads per row come out of the LDS.
-template <typename T> struct WellCfg { static constexpr int SMAX = sizeof(T) >= 16 ? 4 : 8; };   // <= 64 KiB per buffer
-
-// Entry storage of a block: slot t of thread l (row l of the block) lives in 16-byte pieces per
-// thread -- values [t / VPG][l][t % VPG] with VPG = 16 / sizeof(T) values per piece, positions
-// [t / 8][l][t % 8] -- so that a thread fetches its row's entries with a few 16-byte loads (one
-// 4- or 8-byte and one 2-byte load per entry cost as many vector-memory instructions as all the
-// staging of the block).  A block's slots are padded to a multiple of 8; eoff counts slots.
-template <typename T>
-__host__ __device__ inline int64_t well_val_index(int64_t eoff, int t, int l) {
-  constexpr int VPG = 16 / (int)sizeof(T) > 0 ? 16 / (int)sizeof(T) : 1;
-  return (eoff + (t / VPG) * VPG) * 1024 + (int64_t)l * VPG + (t % VPG);
-}
-__host__ __device__ inline int64_t well_idx_index(int64_t eoff, int t, int l) {
-  return (eoff + (t / 8) * 8) * 1024 + (int64_t)l * 8 + (t % 8);
-}
+// (WellCfg and the entry storage of a block, well_val_index / well_idx_index: spmm.h, shared with the host builder)
 // the row's WMAX values and positions (the host pads every row to WMAX slots: value 0 at the position of
 // the row's own first entry, so a padding slot never touches a column the row does not reference)
 template <typename T, int WMAX>
@@ -227,9 +211,6 @@ __device__ __forceinline__ void well_load_entries(const T *__restrict__ vals, co
     for (int k = 0; k < 8; ++k) pos[g * 8 + k] = (unsigned)piece.h[k];
   }
 }
-constexpr int kWellRows = 1024;
-constexpr int kStkMaxPatterns = 4096;
-constexpr int kStkMaxDeltas = 64;                  // position patterns per member of a stack
 
 // The same with the values out of the stacks' dictionary: the row's pattern index (4 bytes) and the 8 values of that
 // pattern (a few dozen 16-byte lines that stay in the L1 / L2 for the whole launch) instead of 8 values per row.
@@ -511,10 +492,7 @@ __global__ __launch_bounds__(1024) void well_spmm_kernel(const WellMeta *__restr
 // (2 + R * 1.42) / R elements per row instead of 3.42.  The host picks the stacks on the window-overlap graph (greedy
 // matching: the unstacked block that overlaps a block's windows most), so nothing here knows about grids; blocks without a
 // partner run as stacks of one.  Same entry storage, staging plan and step pipeline as above (16-byte staging only: the
-// caller checks that every group is in range); the two staging buffers are the CU's whole LDS.
-constexpr int kStkR = 2;                           // row blocks per stack
-constexpr int kStkBufBytes = 80 * 1024;            // per staging buffer
-
+// caller checks that every group is in range); the two staging buffers are the CU's whole LDS (kStkR, kStkBufBytes: spmm.h).
 template <typename T, int R>
 __global__ __launch_bounds__(1024) void well_stack_kernel(const WellMeta *__restrict__ meta,
                                                           const int32_t *__restrict__ member,
@@ -700,11 +678,6 @@ __device__ __forceinline__ void wait_vm_outstanding(int n) {
 #undef RLH_WC8
 #undef RLH_WC
 }
-
-constexpr int kStkLdsBytes = 160 * 1024;
-// slots of the ring: four of 40 KB, or -- 16-byte elements, whose image of one vector is as large as two of the others'
-// -- two of 80 KB (the bytes in flight are what counts, not the vectors)
-template <typename T> struct StkRing { static constexpr int NB = sizeof(T) >= 16 ? 2 : 4, SLOT = kStkLdsBytes / NB; };
 
 // "this value is needed now" for the compiler's wait placement
 __device__ __forceinline__ void stk_touch(float &v) { asm volatile("" : "+v"(v)); }
@@ -1110,7 +1083,7 @@ static int launch_well_w(const rlh_csr *h, int part, int64_t m, const T *X, int6
   constexpr int EPL = 16 / (int)sizeof(T);
   if constexpr (EPL > 1) {
     const int vec = env_int("RLH_SPMM_VEC", 1);         // 0: 8-byte staging (tunable)
-    const bool whole = h->well_inbounds && (H == nullptr || n_own == h->n_cols || (h->well_aligned && n_own % EPL == 0));
+    const bool whole = h->stage_inbounds && (H == nullptr || n_own == h->n_cols || (h->stage_aligned && n_own % EPL == 0));
     if (vec && whole) return launch_well_we<T, WMAX, EPL>(h, part, m, X, ldx, n_own, H, ldh, Y, ldy, cheb);
   }
   return launch_well_we<T, WMAX, 1>(h, part, m, X, ldx, n_own, H, ldh, Y, ldy, cheb);
@@ -1522,730 +1495,11 @@ static int gather_rows_impl(int64_t nidx, const int64_t *d_idx, int64_t m, const
   });
 }
 
-template <int DT>
-static int csr_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices, const void *values_) {
-  using T = typename DType<DT>::T;
-  const T *values = (const T *)values_;
-  const int64_t n = h->n_rows;
-  const int64_t ns = (n + 63) / 64;
-  std::vector<int64_t> sp(ns + 1, 0);
-  for (int64_t s = 0; s < ns; ++s) {
-    int64_t w = 0;
-    for (int64_t r = s * 64; r < n && r < (s + 1) * 64; ++r) {
-      const int64_t len = indptr[r + 1] - indptr[r];
-      if (len > w) w = len;
-    }
-    sp[s + 1] = sp[s] + w * 64;
-  }
-  const int64_t padded = sp[ns];
-  std::vector<int32_t> cols((size_t)padded);
-  std::vector<T> vals((size_t)padded);
-  for (int64_t s = 0; s < ns; ++s) {
-    const int64_t w = (sp[s + 1] - sp[s]) / 64;
-    for (int l = 0; l < 64; ++l) {
-      const int64_t r = s * 64 + l;
-      const int64_t b = r < n ? indptr[r] : 0, len = r < n ? indptr[r + 1] - b : 0;
-      // padding entries carry value 0 and a harmless in-range column (the row's first, else 0)
-      const int32_t padcol = len > 0 ? indices[b] : 0;
-      for (int64_t t = 0; t < w; ++t) {
-        const int64_t e = sp[s] + t * 64 + l;
-        if (t < len) { cols[e] = indices[b + t]; vals[e] = values[b + t]; }
-        else { cols[e] = padcol; memset(&vals[e], 0, sizeof(T)); }
-      }
-    }
-  }
-  h->n_slices = ns;
-  h->padded = padded;
-  if (int rc = h->slice_ptr.upload(sp.data(), (size_t)(ns + 1) * sizeof(int64_t))) return rc;
-  if (padded > 0) {
-    if (int rc = h->cols.upload(cols.data(), (size_t)padded * sizeof(int32_t))) return rc;
-    if (int rc = h->vals.upload(vals.data(), (size_t)padded * sizeof(T))) return rc;
-  }
-  h->device_bytes = (ns + 1) * 8 + padded * (4 + (int64_t)sizeof(T));
-  return 0;
-}
-
-
-template <int DT>
-static int stack_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices, const void *values_,
-                       const std::vector<std::vector<Win>> &wins, int64_t staged_unstacked);
-
-// Host side of the 1024-row windowed layout.  Returns 0 with h->well_blocks == 0 when the matrix
-// does not qualify (a row longer than 8 entries, a block whose windows do not fit the LDS buffer,
-// or too little column locality for the staging to pay).
-template <int DT>
-static int well_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices, const void *values_, bool force,
-                      bool stack_only = false) {
-  using T = typename DType<DT>::T;
-  constexpr int SMAX = WellCfg<T>::SMAX;
-  const T *values = (const T *)values_;
-  const int64_t n = h->n_rows;
-  const int64_t nblocks = (n + kWellRows - 1) / kWellRows;
-  h->well_blocks = 0;
-  if (nblocks == 0 || h->nnz == 0) return 0;
-  PhaseClock clk;
-  std::vector<std::vector<Win>> wins((size_t)nblocks);
-  std::vector<int32_t> width((size_t)nblocks, 0), ngroups((size_t)nblocks, 0);
-  parallel_blocks(nblocks, [&](int64_t b) {
-    const int64_t r0 = b * kWellRows, r1 = (r0 + kWellRows < n) ? r0 + kWellRows : n;
-    int64_t w = 0;
-    for (int64_t r = r0; r < r1; ++r) w = std::max<int64_t>(w, indptr[r + 1] - indptr[r]);
-    width[b] = (int32_t)std::min<int64_t>(w, 1 << 20);
-    // groups per block: a multiple of 8 (one 16-byte load covers 2, 4 or -- bfloat16 -- 8 groups)
-    ngroups[b] = find_windows(indptr, indices, r0, r1, h->n_cols, 32, 64, 8, wins[b]) / 64;
-  });
-  clk.lap("well: windows");
-  int32_t wmax = 0, gmax = 0;
-  int64_t staged = 0, slots = 0;
-  for (int64_t b = 0; b < nblocks; ++b) {
-    wmax = std::max(wmax, width[b]);
-    gmax = std::max(gmax, ngroups[b]);
-    staged += (int64_t)ngroups[b] * 64;
-    slots += (int64_t)width[b] * kWellRows;
-  }
-  h->well_ratio = slots > 0 ? (double)staged / (double)slots : 0.0;
-  // (the limit on a block's image is the unstacked kernel's staging buffer: a complex operator never runs that kernel -- its
-  // stacks have a ring slot of their own size, checked by stack_build)
-  if (wmax > 8 || (!stack_only && gmax > 16 * SMAX)) {
-    if (clk.on) fprintf(stderr, "csr layout: well: not built (longest row %d, largest block image %d groups of 64 columns, limit %d)\n", wmax, gmax, 16 * SMAX);
-    return 0;
-  }
-  // measured (profiles/r01_spmm_windowed.txt): at 0.65 staged elements per entry slot (5-point
-  // stencil) the windowed kernel is 1.27x faster than the sliced one, at 1.06 (a diagonal
-  // matrix) 4 % slower
-  if (!force && staged * 10 > slots * 9) {
-    if (clk.on) fprintf(stderr, "csr layout: well: not built (%lld staged elements for %lld entry slots)\n", (long long)staged, (long long)slots);
-    return 0;
-  }
-  if (stack_only) {          // the complex types: the stacks for rlh_spmm on the whole operator, the interleaved layout for the rest
-    h->well_staged = (double)staged / (double)n;
-    return stack_build<DT>(h, indptr, indices, values_, wins, staged);
-  }
-  h->well_wmax = 8;
-  std::vector<WellMeta> meta((size_t)nblocks);
-  int64_t eoff = 0;
-  int64_t goff = 0;
-  for (int64_t b = 0; b < nblocks; ++b) {
-    meta[b] = WellMeta{eoff, (int32_t)goff, width[b] | (ngroups[b] << 8)};
-    eoff += 8;                                      // every row is stored as 8 slots (16-byte pieces per thread)
-    goff += ngroups[b];
-  }
-  RLH_REQUIRE(goff < ((int64_t)1 << 31), "rlh_csr_create: too many staging groups");
-  std::vector<int32_t> gsrc((size_t)goff);
-  const int64_t epad = 0;
-  RawBuf<uint16_t> idx((size_t)(eoff + epad) * kWellRows);      // (every slot of every block is written below)
-  RawBuf<T> vals((size_t)(eoff + epad) * kWellRows);
-  parallel_blocks(nblocks, [&](int64_t b) {
-    const std::vector<Win> &ws = wins[b];
-    fill_group_sources(ws, ngroups[b], 64, gsrc.data() + meta[b].goff);
-    const int64_t r0 = b * kWellRows;
-    for (int l = 0; l < kWellRows; ++l) {
-      const int64_t r = r0 + l;
-      const int64_t p = r < n ? indptr[r] : 0, len = r < n ? indptr[r + 1] - p : 0;
-      // padding slots carry value 0 and the position of the row's own first entry, so that they
-      // only ever touch a column the row references (0 * Inf of a foreign column would be NaN)
-      const uint16_t padpos = len > 0 ? (uint16_t)staged_position(ws, indices[p]) : 0;
-      size_t hint = 0;
-      for (int32_t t = 0; t < 8; ++t) {
-        const int64_t ev = well_val_index<T>(meta[b].eoff, t, l), ei = well_idx_index(meta[b].eoff, t, l);
-        if (t < len) {
-          idx[ei] = (uint16_t)staged_position_walk(ws, indices[p + t], hint);
-          vals[ev] = values[p + t];
-        } else {
-          idx[ei] = padpos;
-          memset(&vals[ev], 0, sizeof(T));
-        }
-      }
-    }
-  });
-  clk.lap("well: entries");
-  // what the 16-byte staging path may assume
-  h->well_inbounds = 1;
-  h->well_aligned = 1;
-  for (int64_t g = 0; g < goff; ++g) {
-    if ((int64_t)gsrc[g] + 64 > h->n_cols) h->well_inbounds = 0;
-    if (gsrc[g] & 7) h->well_aligned = 0;
-  }
-  std::vector<int32_t> order, maxcol((size_t)nblocks);
-  well_schedule(wins, nblocks, n, kWellRows, ctx().num_cu, order);
-  for (int64_t b = 0; b < nblocks; ++b) maxcol[(size_t)b] = wins[b].back().start + wins[b].back().len - 1;
-  clk.lap("well: schedule");
-  if (int rc = h->well_launch.set(std::move(order), std::move(maxcol))) return rc;
-  if (int rc = h->well_meta.upload(meta.data(), (size_t)nblocks * sizeof(WellMeta))) return rc;
-  if (int rc = h->well_gsrc.upload(gsrc.data(), (size_t)goff * sizeof(int32_t), sizeof(int32_t))) return rc;
-  const size_t ne = (size_t)(eoff + epad) * kWellRows;
-  if (int rc = h->well_idx.upload(idx.data(), ne * sizeof(uint16_t), sizeof(uint16_t))) return rc;
-  if (int rc = h->well_vals.upload(vals.data(), ne * sizeof(T), sizeof(T))) return rc;
-  h->padded = eoff * kWellRows;
-  h->device_bytes = nblocks * (int64_t)sizeof(WellMeta) + h->well_launch.len * 4 + goff * 4 + (int64_t)ne * (2 + (int64_t)sizeof(T));
-  h->well_blocks = nblocks;
-  h->well_staged = (double)staged / (double)n;
-  clk.lap("well: upload");
-  if (h->well_inbounds) return stack_build<DT>(h, indptr, indices, values_, wins, staged);
-  return 0;
-}
-
-// The far stride of a grid operator: the offset (largest column - row) most rows share, e.g. one grid plane for a 3-D
-// stencil (0: fewer than 60 % of the sampled rows agree).  Row blocks of a stack are partners one such stride apart.
-static int64_t far_stride(const int64_t *indptr, const int32_t *indices, int64_t n) {
-  std::unordered_map<int64_t, int64_t> count;
-  int64_t samples = 0;
-  const int64_t step = std::max<int64_t>(1, n / 50000);
-  for (int64_t i = 0; i < n; i += step) {
-    if (indptr[i + 1] == indptr[i]) continue;
-    const int64_t d = (int64_t)indices[indptr[i + 1] - 1] - i;
-    ++samples;
-    if (d > 0) ++count[d];
-  }
-  int64_t best = 0, best_count = 0;
-  for (const auto &kv : count)
-    if (kv.second > best_count || (kv.second == best_count && kv.first < best)) { best = kv.first; best_count = kv.second; }
-  return best_count * 10 >= samples * 6 ? best : 0;
-}
-
-// Host side of the stacked layout ("Stacked blocks" above): the stacks by greedy matching on the window-overlap graph of
-// the 1024-row blocks, then windows / staging groups / entries per stack exactly as well_build lays them out per block.
-// Built only where it stages at least 10 % less than the unstacked layout (RLH_SPMM_STACK=2 builds it regardless, 0 never).
-template <int DT>
-static int stack_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices, const void *values_,
-                       const std::vector<std::vector<Win>> &wins, int64_t staged_unstacked) {
-  using T = typename DType<DT>::T;
-  constexpr int R = kStkR;
-  // groups one vector's image may have: a buffer of the register-staged kernel for the real types (the LDS-DMA kernel
-  // takes over from it where the image fits a ring slot), a ring slot for the complex ones (LDS-DMA only)
-  constexpr int BUFG = (DType<DT>::cplx ? StkRing<T>::SLOT : kStkBufBytes) / (64 * (int)sizeof(T));
-  const T *values = (const T *)values_;
-  const int64_t n = h->n_rows;
-  const int64_t nblocks = (int64_t)wins.size();
-  const int mode = env_int("RLH_SPMM_STACK", 1);
-  h->stk_blocks = 0;
-  // (fewer than 4 row blocks per CU: halving the number of work units costs more than the staging saves -- lap3d 61^3,
-  // 222 blocks: 12.4 us as blocks, 14.1 us as stacks)
-  // A complex operator that small (the row shards of BASELINE config 5: 977 / 489 / 245 blocks on 2 / 4 / 8 GPUs) still takes
-  // the LDS-DMA kernel -- its alternative is the interleaved layout at 0.6-0.7 of the rate: as pairs while every CU gets a
-  // stack (measured on one shard of 2 / 4: product 0.44 / 0.24 ms as pairs, 0.54 / 0.29 as stacks of one, 0.77 / 0.40
-  // interleaved), as stacks of ONE block below that (one of 8: 0.15 ms, 0.18 as pairs on half the CUs, 0.19 interleaved;
-  // tools/c5_shard_bench.py).  RLH_SPMM_STACK_SINGLE=0: no stacks then, as for the real types.
-  bool single = false;
-  if (mode == 0 || nblocks < 2) return 0;
-  if (mode < 2 && nblocks < 4 * (int64_t)ctx().num_cu) {
-    // (below three quarters of a block per CU the interleaved layout's 256-row units fill the chip better: 123 blocks, 50^3:
-    // product 0.077 ms interleaved, 0.087 as stacks of one; 256 blocks, 64^3: 0.170 against 0.131)
-    if (!DType<DT>::cplx || 4 * nblocks < 3 * (int64_t)ctx().num_cu || env_int("RLH_SPMM_STACK_SINGLE", 1) == 0) return 0;
-    single = 4 * nblocks < 7 * (int64_t)ctx().num_cu;
-  }
-  PhaseClock clk;
-  // ---- the row ranges of the blocks: uniform 1024-row blocks, paired by greedy matching on the window-overlap graph
-  std::vector<int64_t> brow;
-  std::vector<int32_t> owner, members;
-  for (int64_t b = 0; b <= nblocks; ++b) brow.push_back(std::min(b * kWellRows, n));
-  // overlap of block b's windows with the rows of block c, both directions summed
-  std::vector<std::vector<std::pair<int32_t, int64_t>>> adj((size_t)nblocks);
-  auto bump = [&](int64_t b, int64_t c, int64_t ov) {
-    for (auto &e : adj[(size_t)b])
-      if (e.first == (int32_t)c) { e.second += ov; return; }
-    adj[(size_t)b].push_back({(int32_t)c, ov});
-  };
-  for (int64_t b = 0; b < nblocks; ++b)
-    for (const Win &w : wins[(size_t)b]) {
-      const int64_t lo = w.start, hi = std::min<int64_t>((int64_t)w.start + w.len, n);
-      for (int64_t c = lo / kWellRows; c * kWellRows < hi; ++c) {
-        if (c == b) continue;
-        const int64_t ov = std::min<int64_t>(hi, (c + 1) * kWellRows) - std::max<int64_t>(lo, c * kWellRows);
-        if (ov <= 0) continue;
-        bump(b, c, ov);
-        bump(c, b, ov);
-      }
-    }
-  owner.assign((size_t)nblocks, -1);
-  int64_t next_free = 0;
-  for (int64_t b = 0; b < nblocks; ++b) {
-    if (owner[(size_t)b] >= 0) continue;
-    const int32_t sb = (int32_t)(members.size() / R);
-    owner[(size_t)b] = sb;
-    members.push_back((int32_t)b);
-    for (int r = 1; r < R; ++r) {
-      int32_t best = -1;
-      int64_t wbest = 0;
-      if (single) { members.push_back(-1); continue; }
-      for (size_t k = (size_t)(sb * R); k < members.size(); ++k)          // heaviest free neighbour of the stack so far
-        for (const auto &e : adj[(size_t)members[k]])
-          if (owner[(size_t)e.first] < 0 && (e.second > wbest || (e.second == wbest && best >= 0 && e.first < best))) {
-            best = e.first;
-            wbest = e.second;
-          }
-      if (best < 0) {                                                   // none: the next free block in order
-        while (next_free < nblocks && owner[(size_t)next_free] >= 0) ++next_free;
-        if (next_free < nblocks) best = (int32_t)next_free;
-      }
-      if (best >= 0) owner[(size_t)best] = sb;
-      members.push_back(best);
-    }
-  }
-
-  int64_t nst = (int64_t)members.size() / R;
-  const int64_t nc8 = (h->n_cols + 7) & ~(int64_t)7;                    // windows may end here: aligned starts at the far end too
-  std::vector<std::vector<Win>> swins((size_t)nst);
-  std::vector<int32_t> ngroups((size_t)nst, 0);
-  auto analyse = [&](int64_t count) {
-    swins.assign((size_t)count, std::vector<Win>());
-    ngroups.assign((size_t)count, 0);
-    parallel_blocks(count, [&](int64_t sb) {
-      std::vector<int32_t> cols;
-      for (int r = 0; r < R; ++r) {
-        const int64_t mb = members[(size_t)(sb * R + r)];
-        if (mb < 0) continue;
-        const int64_t r0 = brow[(size_t)mb], r1 = brow[(size_t)mb + 1];
-        cols.insert(cols.end(), indices + indptr[r0], indices + indptr[r1]);
-      }
-      ngroups[(size_t)sb] = find_windows_of(cols, nc8, 32, 64, 8, swins[(size_t)sb]) / 64;
-    });
-  };
-  clk.lap("stack: matching");
-  analyse(nst);
-  // Uniform blocks pair up exactly when the far stride of the operator (a grid plane) is a whole number of them, and well
-  // enough when it nearly is (215^2 = 45.14 blocks: 2.49 staged elements per row).  When a block and its partner one plane
-  // on are half a block out of step (126^2 = 15.5 blocks), the union of their windows outgrows a slot of the ring and the
-  // stacks fall apart into stacks of one (config 5 at 126^3: 1.03 ms against 0.82 ms at 128^3).  Then -- and only then: at
-  // 215^3 the uniform blocks are 4 % faster -- the blocks are cut plane by plane instead, ceil(plane / 1024) blocks of
-  // (nearly) equal size per plane, so that block j of a plane and block j of the next are exact translates of each other:
-  // 126^3 complex128 in 0.865 ms.  Float32 operators keep the uniform blocks (their bfloat16 step moves rows in 16-byte
-  // pieces of eight).  RLH_SPMM_STACK_ALIGN=0: never, =2: whenever a far stride exists.
-  {
-    constexpr int DMAG0 = StkRing<T>::SLOT / (64 * (int)sizeof(T));
-    const int align_mode = env_int("RLH_SPMM_STACK_ALIGN", 1);
-    int64_t apart = 0, pairs = 0;
-    for (int64_t sb = 0; sb < nst; ++sb)
-      if (members[(size_t)(sb * R + 1)] >= 0) { ++pairs; apart += ngroups[(size_t)sb] > std::min(BUFG, DMAG0); }
-    const int64_t plane = (R == 2 && DT != RLH_S && align_mode != 0 && (apart * 4 > pairs || align_mode == 2))
-                              ? far_stride(indptr, indices, n) : 0;
-    if (plane > kWellRows && plane < n && plane % kWellRows != 0) {
-      brow.clear();
-      members.clear();
-      std::vector<int64_t> first_of_plane;              // block id of the first block of every plane
-      brow.push_back(0);
-      for (int64_t p0 = 0; p0 < n; p0 += plane) {
-        const int64_t len = std::min(plane, n - p0), k = (len + kWellRows - 1) / kWellRows;
-        first_of_plane.push_back((int64_t)brow.size() - 1);
-        for (int64_t j = 1; j <= k; ++j) brow.push_back(p0 + len * j / k);
-      }
-      first_of_plane.push_back((int64_t)brow.size() - 1);
-      const int64_t planes = (int64_t)first_of_plane.size() - 1;
-      for (int64_t p = 0; p < planes; p += 2) {
-        const int64_t b0 = first_of_plane[(size_t)p], k0 = first_of_plane[(size_t)p + 1] - b0;
-        const int64_t b1 = p + 1 < planes ? first_of_plane[(size_t)p + 1] : -1, k1 = p + 1 < planes ? first_of_plane[(size_t)p + 2] - b1 : 0;
-        for (int64_t j = 0; j < std::max(k0, k1); ++j) {
-          if (j < k0) { members.push_back((int32_t)(b0 + j)); members.push_back(j < k1 ? (int32_t)(b1 + j) : -1); }
-          else { members.push_back((int32_t)(b1 + j)); members.push_back(-1); }
-        }
-      }
-      nst = (int64_t)members.size() / R;
-      owner.assign(brow.size() - 1, -1);
-      for (size_t k = 0; k < members.size(); ++k)
-        if (members[k] >= 0) owner[(size_t)members[k]] = (int32_t)(k / R);
-      analyse(nst);
-    }
-  }
-  const int64_t nblk = (int64_t)brow.size() - 1;
-  clk.lap("stack: windows");
-  // a stack whose image does not fit (grid planes half a row block out of step with the blocks: 126^2 rows = 15.5
-  // blocks) is taken apart into stacks of one
-  // ... and so is a stack of a real type whose image fits the register-staged kernel's buffer but not a slot of the LDS-DMA
-  // ring, as long as such stacks are few (the blocks of a row shard next to its halo columns: their windows lie in two far
-  // apart column ranges): one oversized stack would otherwise take the LDS-DMA kernel -- the only one that serves row
-  // shards -- away from the whole operator (the forced one-rank run of lap3d 215^3 fell back to the unstacked kernel that
-  // way: 1.33 instead of 1.12 ms per product)
-  constexpr int DMAG = StkRing<T>::SLOT / (64 * (int)sizeof(T));
-  int64_t over_dma = 0;
-  for (int64_t sb = 0; sb < nst; ++sb) over_dma += ngroups[(size_t)sb] > DMAG && members[(size_t)(sb * R + 1)] >= 0;
-  const int CAPG = (over_dma > 0 && over_dma * 20 <= nst) ? std::min(BUFG, DMAG) : BUFG;
-  bool split = false;
-  for (int64_t sb = 0; sb < nst && !split; ++sb) split = ngroups[(size_t)sb] > CAPG && members[(size_t)(sb * R + 1)] >= 0;
-  if (split) {
-    std::vector<int32_t> again;
-    for (int64_t sb = 0; sb < nst; ++sb) {
-      if (ngroups[(size_t)sb] <= CAPG || members[(size_t)(sb * R + 1)] < 0) {
-        for (int r = 0; r < R; ++r) again.push_back(members[(size_t)(sb * R + r)]);
-        continue;
-      }
-      for (int r = 0; r < R; ++r) {
-        again.push_back(members[(size_t)(sb * R + r)]);
-        for (int q = 1; q < R; ++q) again.push_back(-1);
-      }
-    }
-    members.swap(again);
-    nst = (int64_t)members.size() / R;
-    for (int64_t sb = 0; sb < nst; ++sb)
-      for (int r = 0; r < R; ++r)
-        if (members[(size_t)(sb * R + r)] >= 0) owner[(size_t)members[(size_t)(sb * R + r)]] = (int32_t)sb;
-    analyse(nst);
-  }
-  int64_t staged = 0;
-  int32_t gmax = 0;
-  for (int64_t sb = 0; sb < nst; ++sb) {
-    staged += (int64_t)ngroups[(size_t)sb] * 64;
-    gmax = std::max(gmax, ngroups[(size_t)sb]);
-  }
-  h->stk_staged = (double)staged / (double)(n > 0 ? n : 1);
-  h->stk_gmax = gmax;
-  if (gmax > BUFG) {                                                     // a stack's image must fit one buffer
-    if (clk.on) fprintf(stderr, "csr layout: stack: not built (largest image %d groups of 64 columns, a buffer holds %d)\n", gmax, BUFG);
-    return 0;
-  }
-  // (the complex types: the alternative is the interleaved layout, which re-stages the windows in passes of a few vectors
-  // -- config 5's operator at 160^3 in complex64: 1.87 ms there, 0.86 ms here)
-  if (mode < 2 && !DType<DT>::cplx && staged * 10 > staged_unstacked * 9) return 0;
-  std::vector<WellMeta> meta((size_t)nst);
-  int64_t goff = 0;
-  for (int64_t sb = 0; sb < nst; ++sb) {
-    meta[(size_t)sb] = WellMeta{sb * 8 * R, (int32_t)goff, 8 | (ngroups[(size_t)sb] << 8)};
-    goff += ngroups[(size_t)sb];
-  }
-  RLH_REQUIRE(goff < ((int64_t)1 << 31), "rlh_csr_create: too many staging groups");
-  std::vector<int32_t> gsrc((size_t)goff);
-  const size_t ne = (size_t)nst * 8 * R * kWellRows;
-  RawBuf<uint16_t> idx(ne);                                     // (every slot of every stack is written below)
-  RawBuf<T> vals(ne);
-  std::atomic<int> self_ok{1};
-  parallel_blocks(nst, [&](int64_t sb) {
-    const std::vector<Win> &ws = swins[(size_t)sb];
-    fill_group_sources(ws, ngroups[(size_t)sb], 64, gsrc.data() + meta[(size_t)sb].goff);
-    for (int r = 0; r < R; ++r) {
-      const int64_t mb = members[(size_t)(sb * R + r)];
-      const int64_t eoff = meta[(size_t)sb].eoff + 8 * r;
-      for (int l = 0; l < kWellRows; ++l) {
-        const int64_t row = mb >= 0 && brow[(size_t)mb] + l < brow[(size_t)mb + 1] ? brow[(size_t)mb] + l : n;
-        const int64_t p = row < n ? indptr[row] : 0, len = row < n ? indptr[row + 1] - p : 0;
-        const uint16_t padpos = len > 0 ? (uint16_t)staged_position(ws, indices[p]) : 0;
-        size_t hint = 0;
-        for (int32_t t = 0; t < 8; ++t) {
-          const int64_t ev = well_val_index<T>(eoff, t, l), ei = well_idx_index(eoff, t, l);
-          if (t < len) {
-            idx[(size_t)ei] = (uint16_t)staged_position_walk(ws, indices[p + t], hint);
-            vals[(size_t)ev] = values[p + t];
-          } else {
-            idx[(size_t)ei] = padpos;
-            memset(&vals[(size_t)ev], 0, sizeof(T));
-          }
-        }
-        // the LAST slot of a row with a free one carries (value 0 and) the position of the row's OWN column, where the row
-        // stores its diagonal entry: the fused Chebyshev step then finds y[row] in the staged image instead of reading the
-        // block a second time (well_stack_dma_kernel<..., CHEB>); one row without makes the handle say so
-        if (row < n) {
-          bool has_diag = false;
-          for (int64_t e = p; e < p + len && !has_diag; ++e) has_diag = indices[e] == row;
-          if (len <= 7 && has_diag) idx[(size_t)well_idx_index(eoff, 7, l)] = (uint16_t)staged_position(ws, (int32_t)row);
-          else self_ok.store(0, std::memory_order_relaxed);
-        }
-      }
-    }
-  });
-  h->stk_self = self_ok.load();
-  clk.lap("stack: entries");
-  h->stk_overhang = 0;
-  for (int64_t g = 0; g < goff; ++g) {
-    if ((int64_t)gsrc[(size_t)g] + 64 > nc8) return 0;                  // 16-byte staging needs whole groups
-    if ((int64_t)gsrc[(size_t)g] + 64 > h->n_cols) h->stk_overhang = (int)(nc8 - h->n_cols);
-  }
-  h->stk_aligned = 1;
-  for (int64_t g = 0; g < goff; ++g)
-    if (gsrc[(size_t)g] & 7) h->stk_aligned = 0;
-  std::vector<int32_t> order, maxcol((size_t)nst);
-  for (int64_t sb = 0; sb < nst; ++sb) maxcol[(size_t)sb] = swins[(size_t)sb].back().start + swins[(size_t)sb].back().len - 1;
-  std::vector<int32_t> granule_owner((size_t)((n + kWellRows - 1) / kWellRows), -1);      // the stack that owns row 1024 c
-  {
-    int64_t blk = 0;
-    for (size_t c = 0; c < granule_owner.size(); ++c) {
-      while (blk + 1 < nblk && brow[(size_t)blk + 1] <= (int64_t)c * kWellRows) ++blk;
-      granule_owner[c] = owner[(size_t)blk];
-    }
-  }
-  well_schedule(swins, nst, n, kWellRows, ctx().num_cu, order, &granule_owner);
-  clk.lap("stack: schedule");
-  if (int rc = h->stk_launch.set(std::move(order), std::move(maxcol))) return rc;
-  if (int rc = h->stk_meta.upload(meta.data(), (size_t)nst * sizeof(WellMeta))) return rc;
-  {
-    std::vector<int32_t> ranges(members.size() * 2, 0);                   // (first row, rows) of every member; (0, 0): none
-    for (size_t k = 0; k < members.size(); ++k)
-      if (members[k] >= 0) {
-        ranges[2 * k] = (int32_t)brow[(size_t)members[k]];
-        ranges[2 * k + 1] = (int32_t)(brow[(size_t)members[k] + 1] - brow[(size_t)members[k]]);
-      }
-    if (int rc = h->stk_member.upload(ranges.data(), ranges.size() * sizeof(int32_t))) return rc;
-  }
-  if (int rc = h->stk_gsrc.upload(gsrc.data(), (size_t)goff * sizeof(int32_t), sizeof(int32_t))) return rc;
-  // value dictionary: the distinct 8-slot value tuples of the rows (byte-wise), given up beyond kStkMaxPatterns
-  {
-    std::vector<int32_t> pat((size_t)nst * R * kWellRows, 0);
-    std::vector<T> table;
-    std::unordered_map<uint64_t, std::vector<int32_t>> seen;
-    bool ok = env_int("RLH_SPMM_STACK_PAT", 1) != 0;
-    int32_t last_id = -1;
-    T last_tup[8];
-    for (int64_t sb = 0; sb < nst && ok; ++sb)
-      for (int r = 0; r < R && ok; ++r) {
-        const int64_t eoff = meta[(size_t)sb].eoff + 8 * r;
-        for (int l = 0; l < kWellRows; ++l) {
-          T tup[8];
-          for (int t = 0; t < 8; ++t) tup[t] = vals[(size_t)well_val_index<T>(eoff, t, l)];
-          if (last_id >= 0 && !memcmp(last_tup, tup, sizeof(tup))) {      // (a stencil: the same as the row before)
-            pat[(size_t)((sb * R + r) * kWellRows + l)] = last_id;
-            continue;
-          }
-          uint64_t hsh = 1469598103934665603ull;
-          const unsigned char *bytes = reinterpret_cast<const unsigned char *>(tup);
-          for (size_t k = 0; k < sizeof(tup); ++k) hsh = (hsh ^ bytes[k]) * 1099511628211ull;
-          std::vector<int32_t> &cand = seen[hsh];
-          int32_t id = -1;
-          for (int32_t c : cand)
-            if (!memcmp(&table[(size_t)c * 8], tup, sizeof(tup))) { id = c; break; }
-          if (id < 0) {
-            id = (int32_t)(table.size() / 8);
-            if (id >= kStkMaxPatterns) { ok = false; break; }
-            table.insert(table.end(), tup, tup + 8);
-            cand.push_back(id);
-          }
-          pat[(size_t)((sb * R + r) * kWellRows + l)] = id;
-          last_id = id;
-          memcpy(last_tup, tup, sizeof(tup));
-        }
-      }
-    clk.lap("stack: value dictionary");
-    // position patterns per member: the positions less the row's index in its block (mod 2^16)
-    std::vector<uint16_t> dtab;
-    bool dok = ok && env_int("RLH_SPMM_STACK_PAT", 1) >= 1 && env_int("RLH_SPMM_STACK_DPAT", 1) != 0;
-    if (dok) {
-      dtab.assign((size_t)nst * R * kStkMaxDeltas * 8, 0);
-      for (int64_t sb = 0; sb < nst && dok; ++sb)
-        for (int r = 0; r < R && dok; ++r) {
-          const int64_t eoff = meta[(size_t)sb].eoff + 8 * r, pb = sb * R + r;
-          uint16_t *tab = dtab.data() + (size_t)pb * kStkMaxDeltas * 8;
-          int used = 0;
-          const int64_t mb = members[(size_t)pb];
-          for (int l = 0; l < kWellRows && dok; ++l) {
-            if (mb < 0 || brow[(size_t)mb] + l >= brow[(size_t)mb + 1]) continue;   // no such row: nothing is stored for it, any pattern will do
-            uint16_t tup[8];
-            for (int t = 0; t < 8; ++t) tup[t] = (uint16_t)(idx[(size_t)well_idx_index(eoff, t, l)] - (uint16_t)l);
-            int id = -1;
-            for (int c = used - 1; c >= 0; --c)           // (the last one used is the likeliest)
-              if (!memcmp(tab + c * 8, tup, sizeof(tup))) { id = c; break; }
-            if (id < 0) {
-              if (used >= kStkMaxDeltas) { dok = false; break; }
-              id = used++;
-              memcpy(tab + id * 8, tup, sizeof(tup));
-            }
-            pat[(size_t)(pb * kWellRows + l)] |= id << 16;
-          }
-        }
-      if (!dok)
-        for (int32_t &w : pat) w &= 0xffff;
-    }
-    clk.lap("stack: position dictionary");
-    h->stk_npat = 0;
-    if (ok && !table.empty()) {
-      if (dok) {
-        if (int rc = h->stk_dtab.upload(dtab.data(), dtab.size() * sizeof(uint16_t))) return rc;
-        h->device_bytes += (int64_t)dtab.size() * 2;
-      }
-      h->stk_npat = (int64_t)table.size() / 8;
-      if (int rc = h->stk_pat.upload(pat.data(), pat.size() * sizeof(int32_t))) return rc;
-      if (int rc = h->stk_table.upload(table.data(), table.size() * sizeof(T))) return rc;
-      h->device_bytes += (int64_t)pat.size() * 4 + (int64_t)table.size() * (int64_t)sizeof(T);
-    }
-  }
-  if (int rc = h->stk_idx.upload(idx.data(), ne * sizeof(uint16_t))) return rc;
-  if (int rc = h->stk_vals.upload(vals.data(), ne * sizeof(T))) return rc;
-  h->device_bytes += nst * (int64_t)sizeof(WellMeta) + h->stk_launch.len * 4 + goff * 4 + (int64_t)members.size() * 8 +
-                     (int64_t)ne * (2 + (int64_t)sizeof(T));
-  h->stk_blocks = nst;
-  clk.lap("stack: upload");
-  return 0;
-}
-
-// The Hermitian operator defined by the UPPER triangle of a square CSR matrix (entries below the diagonal, if the caller
-// stores them, are ignored): A = U + U^H - diag(U), what mkl_?csrmm computes with the 'SUNF' / 'HUNF' descriptor the
-// reference passes (raleigh/algebra/mkl_wrap.py:211-276).  One counting pass and one fill pass over the entries on the
-// host (row i of the result = the mirrored entries (j, i), j < i, in ascending j, then the row's own upper entries:
-// sorted if the input rows are), then the ordinary rlh_csr_create.
-template <typename T> static inline T conj_of(T v) { return v; }
-template <> inline c32 conj_of(c32 v) { return c32{v.re, -v.im}; }
-template <> inline c64 conj_of(c64 v) { return c64{v.re, -v.im}; }
-
-template <typename T>
-static int csr_from_upper(rlh_csr_t *out, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices, const T *values) {
-  PhaseClock clk;
-  // counting pass, rows dealt to the host threads: own entries per row, mirrored entries per target row (atomic: two
-  // threads may mirror into the same row)
-  std::unique_ptr<std::atomic<int64_t>[]> cnt(new std::atomic<int64_t>[(size_t)n + 1]);
-  std::vector<int64_t> below((size_t)n, 0);
-  std::atomic<int64_t> bad_row{-1};
-  std::atomic<int> bad_kind{0};
-  host_parallel(64, [&](int t, int nt) {
-    for (int64_t i = n * t / nt; i < n * (t + 1) / nt; ++i) cnt[(size_t)i + 1].store(0, std::memory_order_relaxed);
-    if (t == 0) cnt[0].store(0, std::memory_order_relaxed);
-  });
-  host_parallel(64, [&](int t, int nt) {
-    for (int64_t i = n * t / nt; i < n * (t + 1) / nt; ++i) {
-      int32_t prev = -1;
-      int64_t own = 0;
-      for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e) {
-        const int32_t j = indices[e];
-        if (j < 0 || j >= n) { bad_row.store(i); bad_kind.store(1); return; }
-        if (j <= prev) { bad_row.store(i); bad_kind.store(2); return; }
-        prev = j;
-        if (j < i) continue;
-        ++own;
-        if (j > i) cnt[(size_t)j + 1].fetch_add(1, std::memory_order_relaxed);
-      }
-      below[(size_t)i] = own;                                   // (own entries for now)
-    }
-  });
-  RLH_REQUIRE(bad_kind.load() != 1, "rlh_csr_create_upper: column index out of range in row %lld", (long long)bad_row.load());
-  RLH_REQUIRE(bad_kind.load() != 2, "rlh_csr_create_upper: the column indices of row %lld are not sorted (or repeat)",
-              (long long)bad_row.load());
-  // A caller that stores BOTH triangles of a Hermitian matrix (what SciPy users hold) has handed over the operator itself:
-  // if every entry below the diagonal is the conjugate of its mirror image above it -- checked entry by entry, one binary
-  // search each, on the host threads -- and the two triangles have equally many entries, nothing needs mirroring and no
-  // second copy of the matrix is allocated (lap3d 215^3: 0.2 s and 0.8 GB less).  Any mismatch: the upper triangle rules.
-  {
-    int64_t own_total = 0, mirrored_total = 0;
-    for (int64_t i = 0; i < n; ++i) { own_total += below[(size_t)i]; mirrored_total += cnt[(size_t)i + 1].load(std::memory_order_relaxed); }
-    const int64_t lower_total = indptr[n] - own_total;
-    if (lower_total > 0 && lower_total == mirrored_total) {
-      std::atomic<int> mismatch{0};
-      host_parallel(64, [&](int t, int nt) {
-        for (int64_t i = n * t / nt; i < n * (t + 1) / nt && !mismatch.load(std::memory_order_relaxed); ++i)
-          for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e) {
-            const int32_t j = indices[e];
-            if (j >= i) break;                                   // (sorted: the rest of the row is the upper part)
-            const int32_t *b0 = indices + indptr[j], *b1 = indices + indptr[j + 1];
-            const int32_t *f = std::lower_bound(b0, b1, (int32_t)i);
-            if (f == b1 || *f != (int32_t)i) { mismatch.store(1); break; }
-            const T up = conj_of(values[f - indices]);
-            if (memcmp(&up, &values[e], sizeof(T)) != 0) { mismatch.store(1); break; }
-          }
-      });
-      if (!mismatch.load()) {
-        clk.lap("both triangles given and consistent");
-        return rlh_csr_create(out, dtype, n, n, indptr, indices, values);
-      }
-    }
-  }
-  std::vector<int64_t> rp((size_t)n + 1, 0);
-  for (int64_t i = 0; i < n; ++i) {
-    const int64_t mirrored = cnt[(size_t)i + 1].load(std::memory_order_relaxed);
-    rp[(size_t)i + 1] = rp[(size_t)i] + mirrored + below[(size_t)i];
-    below[(size_t)i] = mirrored;
-    cnt[(size_t)i].store(rp[(size_t)i], std::memory_order_relaxed);     // where the next mirrored entry of row i goes
-  }
-  std::vector<int32_t> idx((size_t)rp[(size_t)n]);
-  std::vector<T> val((size_t)rp[(size_t)n]);
-  host_parallel(64, [&](int t, int nt) {
-    for (int64_t i = n * t / nt; i < n * (t + 1) / nt; ++i) {
-      int64_t w = rp[(size_t)i] + below[(size_t)i];               // the row's own entries follow its mirrored ones
-      for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e) {
-        const int32_t j = indices[e];
-        if (j < i) continue;
-        idx[(size_t)w] = j; val[(size_t)w] = values[e]; ++w;
-        if (j > i) {
-          const int64_t d = cnt[(size_t)j].fetch_add(1, std::memory_order_relaxed);
-          idx[(size_t)d] = (int32_t)i; val[(size_t)d] = conj_of(values[e]);
-        }
-      }
-    }
-  });
-  // the mirrored entries of a row arrive in whatever order the threads reached them: ascending column order restored
-  host_parallel(64, [&](int t, int nt) {
-    std::vector<std::pair<int32_t, T>> tmp;
-    for (int64_t i = n * t / nt; i < n * (t + 1) / nt; ++i) {
-      const int64_t b0 = rp[(size_t)i], m = below[(size_t)i];
-      bool sorted = true;
-      for (int64_t k = 1; k < m && sorted; ++k) sorted = idx[(size_t)(b0 + k - 1)] < idx[(size_t)(b0 + k)];
-      if (sorted) continue;
-      tmp.resize((size_t)m);
-      for (int64_t k = 0; k < m; ++k) tmp[(size_t)k] = {idx[(size_t)(b0 + k)], val[(size_t)(b0 + k)]};
-      std::sort(tmp.begin(), tmp.end(), [](const std::pair<int32_t, T> &x, const std::pair<int32_t, T> &y) { return x.first < y.first; });
-      for (int64_t k = 0; k < m; ++k) { idx[(size_t)(b0 + k)] = tmp[(size_t)k].first; val[(size_t)(b0 + k)] = tmp[(size_t)k].second; }
-    }
-  });
-  clk.lap("mirror the upper triangle");
-  return rlh_csr_create(out, dtype, n, n, rp.data(), idx.data(), val.data());
-}
-
 }  // namespace rlh
 
 using namespace rlh;
 
 extern "C" {
-
-int rlh_csr_create(rlh_csr_t *out, int dtype, int64_t n_rows, int64_t n_cols, const int64_t *indptr,
-                   const int32_t *indices, const void *values) {
-  if (int rc = require_ready()) return rc;
-  RLH_REQUIRE(out != nullptr, "rlh_csr_create: null handle pointer");
-  *out = nullptr;
-  RLH_REQUIRE(dtype_valid(dtype), "rlh_csr_create: unknown dtype %d", dtype);
-  RLH_REQUIRE(n_rows >= 0 && n_cols >= 0 && n_cols < ((int64_t)1 << 31), "rlh_csr_create: bad shape");
-  RLH_REQUIRE(indptr != nullptr, "rlh_csr_create: null indptr");
-  PhaseClock clk;
-  const int64_t nnz = indptr[n_rows] - indptr[0];
-  RLH_REQUIRE(indptr[0] == 0 && nnz >= 0, "rlh_csr_create: indptr must be 0-based and non-decreasing");
-  RLH_REQUIRE(nnz == 0 || (indices && values), "rlh_csr_create: null indices/values");
-  for (int64_t r = 0; r < n_rows; ++r)
-    RLH_REQUIRE(indptr[r + 1] >= indptr[r], "rlh_csr_create: indptr decreases at row %lld", (long long)r);
-  for (int64_t e = 0; e < nnz; ++e)
-    RLH_REQUIRE(indices[e] >= 0 && indices[e] < n_cols, "rlh_csr_create: column index %d out of range at entry %lld",
-                indices[e], (long long)e);
-  clk.lap("argument checks");
-  rlh_csr *h = new rlh_csr();
-  h->dtype = dtype; h->n_rows = n_rows; h->n_cols = n_cols; h->nnz = nnz;
-  // Layout (RLH_SPMM_FORMAT=sell|well|wide overrides the choice and the locality test; read per
-  // handle so tests can cover all three): rows of at most 8 entries of a real type -> the 1024-row
-  // windowed layout; otherwise, or when that one does not qualify -> the 256-row interleaved
-  // layout; no column locality at all -> sliced ELL.
-  const char *fmt = getenv("RLH_SPMM_FORMAT");
-  const bool want_sell = fmt && !strcmp(fmt, "sell"), force_well = fmt && !strcmp(fmt, "well");
-  const bool force_wide = fmt && !strcmp(fmt, "wide");
-  int rc = 0;
-  if (!want_sell && !force_wide) {
-    switch (dtype) {
-      case RLH_S: rc = well_build<RLH_S>(h, indptr, indices, values, force_well); break;
-      case RLH_D: rc = well_build<RLH_D>(h, indptr, indices, values, force_well); break;
-      case RLH_C: rc = well_build<RLH_C>(h, indptr, indices, values, false, true); break;
-      case RLH_Z: rc = well_build<RLH_Z>(h, indptr, indices, values, false, true); break;
-    }
-  }
-  if (rc == 0 && h->well_blocks == 0 && !want_sell) rc = wide_build(h, indptr, indices, values, force_well || force_wide);
-  if (rc == 0 && h->well_blocks == 0 && h->wide_blocks == 0) {
-    switch (dtype) {
-      case RLH_S: rc = csr_build<RLH_S>(h, indptr, indices, values); break;
-      case RLH_D: rc = csr_build<RLH_D>(h, indptr, indices, values); break;
-      case RLH_C: rc = csr_build<RLH_C>(h, indptr, indices, values); break;
-      case RLH_Z: rc = csr_build<RLH_Z>(h, indptr, indices, values); break;
-    }
-  }
-  if (rc) { rlh_csr_destroy(h); return rc; }
-  *out = h;
-  return 0;
-}
-
-int rlh_csr_create_upper(rlh_csr_t *out, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
-                         const void *values) {
-  if (int rc = require_ready()) return rc;
-  RLH_REQUIRE(out != nullptr, "rlh_csr_create_upper: null handle pointer");
-  *out = nullptr;
-  RLH_REQUIRE(dtype_valid(dtype), "rlh_csr_create_upper: unknown dtype %d", dtype);
-  RLH_REQUIRE(n >= 0 && n < ((int64_t)1 << 31) && indptr != nullptr && indptr[0] == 0, "rlh_csr_create_upper: bad matrix");
-  for (int64_t r = 0; r < n; ++r)
-    RLH_REQUIRE(indptr[r + 1] >= indptr[r], "rlh_csr_create_upper: indptr decreases at row %lld", (long long)r);
-  RLH_REQUIRE(indptr[n] == 0 || (indices && values), "rlh_csr_create_upper: null indices/values");
-  switch (dtype) {
-    case RLH_S: return csr_from_upper<float>(out, dtype, n, indptr, indices, (const float *)values);
-    case RLH_D: return csr_from_upper<double>(out, dtype, n, indptr, indices, (const double *)values);
-    case RLH_C: return csr_from_upper<c32>(out, dtype, n, indptr, indices, (const c32 *)values);
-    case RLH_Z: return csr_from_upper<c64>(out, dtype, n, indptr, indices, (const c64 *)values);
-  }
-  return 1;
-}
 
 int rlh_csr_destroy(rlh_csr_t h) {
   if (!h) return 0;
@@ -2268,10 +1522,10 @@ int rlh_csr_info(rlh_csr_t h, int64_t *n_rows, int64_t *n_cols, int64_t *nnz, in
 // (the 1024-row windowed layout stages by 16-byte pieces only: every group inside the column range; the interleaved layout
 // has an element-wise staging for the others, so any float32 handle in it is taken)
 static inline bool bf16_layout_ok(const rlh_csr *h) {
-  return h->dtype == RLH_S && ((h->well_blocks > 0 && h->well_inbounds) || h->wide_blocks > 0);
+  return h->dtype == RLH_S && ((h->well_blocks > 0 && h->stage_inbounds) || h->wide_blocks > 0);
 }
 static inline bool bf16_halo_ok(const rlh_csr *h, int64_t n_own, int64_t ldh) {
-  return h->well_aligned && n_own % 8 == 0 && ldh % 8 == 0;
+  return h->stage_aligned && n_own % 8 == 0 && ldh % 8 == 0;
 }
 // the bfloat16 Chebyshev step on the stacks, VPS vectors per step (the caller has checked that the stacks take the call)
 template <int VPS>
@@ -2306,7 +1560,7 @@ int rlh_csr_layout(rlh_csr_t h, int *layout, int64_t *stored, double *staged_per
   RLH_REQUIRE(h != nullptr, "rlh_csr_layout: null handle");
   if (layout) *layout = h->wide_blocks > 0 ? 2 : (h->well_blocks > 0 ? 1 : 0);
   if (stored) *stored = h->padded;
-  if (staged_per_slot) *staged_per_slot = h->well_ratio;
+  if (staged_per_slot) *staged_per_slot = h->stage_ratio;
   return 0;
 }
 

@@ -17,7 +17,7 @@
 //   (host)         the qualification rules of wide_build, the offsets of the blocks, K
 //   wide_place     the groups' first columns into their final place (a group that would reach past the last column
 //                  is moved left to end on it, as find_windows_of does)
-//   (host)         runs of consecutive groups are the windows: well_schedule, well_inbounds, well_aligned
+//   (host)         runs of consecutive groups are the windows: well_schedule, stage_inbounds, stage_aligned
 //   wide_fill      positions and values in the storage order of wide_build (spmm_wide_build.hip)
 // A window here is a run of referenced 16-aligned groups, not find_windows_of's hole-bridging merge: windows decide
 // staging positions, not sums.  Slot order (a row's stored order), padding slots (value 0, position of the row's
@@ -139,7 +139,7 @@ __device__ __forceinline__ T entry_value(bool mirror, int64_t i, int64_t j, int6
   return va[k];
 }
 
-// ---------------------------------------------------------------- sliced ELL (storage order of csr_build, spmm.hip)
+// ---------------------------------------------------------------- sliced ELL (storage order of csr_build, spmm_build.hip)
 __global__ __launch_bounds__(kBlock) void sell_widths(int64_t n, int64_t ns, const int64_t *__restrict__ ip, int64_t *__restrict__ out) {
   const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (s >= ns) return;
@@ -362,7 +362,7 @@ int wide_build_device(rlh_csr *h, CsrScratch &w, Lap &lap, bool mirror, bool for
     staged += (int64_t)rec[b].ng * kWideGroup;
     slots += (int64_t)rec[b].width * kWideRows;
   }
-  h->well_ratio = slots > 0 ? (double)staged / (double)slots : 0.0;
+  h->stage_ratio = slots > 0 ? (double)staged / (double)slots : 0.0;
   if ((int64_t)gmax * kWideGroup * wide_stride(wide_min_nv(h->dtype), es) + 2 * kWideHeader > kWideLdsBytes) return 0;
   if (gmax * 4 > kWideHeader || wmax > 8 * 32767) return 0;
   if (!force && staged * 10 > slots * 9) return 0;
@@ -403,14 +403,11 @@ int wide_build_device(rlh_csr *h, CsrScratch &w, Lap &lap, bool mirror, bool for
   if (int rc = lap("positions and values")) return rc;
   // the windows of a block: its runs of consecutive groups
   std::vector<std::vector<Win>> wins((size_t)nblocks);
-  h->well_inbounds = 1;
-  h->well_aligned = 1;
+  stage_flags(gsrc.data(), goff, kWideGroup, h->n_cols, &h->stage_inbounds, &h->stage_aligned);
   for (int64_t b = 0; b < nblocks; ++b) {
     std::vector<Win> &ws = wins[(size_t)b];
     for (int32_t g = 0; g < rec[b].ng; ++g) {
       const int32_t src = gsrc[(size_t)meta[b].goff + g];
-      if ((int64_t)src + kWideGroup > h->n_cols) h->well_inbounds = 0;
-      if (src & 7) h->well_aligned = 0;
       if (!ws.empty() && ws.back().start + ws.back().len == src) ws.back().len += kWideGroup;
       else ws.push_back(Win{src, kWideGroup, g * kWideGroup});
     }

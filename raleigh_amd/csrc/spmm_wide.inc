@@ -307,8 +307,8 @@ static int wide_launch_nv(rlh_csr *h, int part, int64_t m, const T *X, int64_t l
   a.idx = (const rlh_u32x4e *)h->wide_idx; a.vals = (const rlh_u32x4e *)h->wide_vals;
   a.n_rows = h->n_rows; a.n_cols = h->n_cols; a.sched = sched; a.sched_len = sched_len;
   a.X = X; a.ldx = ldx; a.n_own = n_own; a.H = H; a.ldh = ldh; a.Y = Y; a.ldy = ldy; a.m = (int)m;
-  a.vec = (env_int("RLH_SPMM_VEC", 1) != 0 && h->well_inbounds &&
-           (H == nullptr || n_own == h->n_cols || (h->well_aligned && n_own % EPL == 0))) ? 1 : 0;
+  a.vec = (env_int("RLH_SPMM_VEC", 1) != 0 && h->stage_inbounds &&
+           (H == nullptr || n_own == h->n_cols || (h->stage_aligned && n_own % EPL == 0))) ? 1 : 0;
   a.cheb = cheb ? *cheb : ChebArgs<T>{};
   if (cheb)
     hipLaunchKernelGGL((wide_spmm_kernel<T, NV, VS, true, K>), dim3((unsigned)grid), dim3(256 / K * VS), lds, c.stream, a);

@@ -334,8 +334,8 @@ int wide_cheb_bf16(rlh_csr *h, int part, int64_t m, const void *Y16, int64_t ldy
   a.P = (unsigned short *)P16; a.ldp = ldp; a.B = (const unsigned short *)B16; a.ldb = ldb; a.m = (int)m;
   // 16-byte staging loads: every group inside the column range and, with a halo block, no piece across n_own (the
   // pieces of a vector may start on any column: the loads are declared 2-byte aligned)
-  a.vec = (env_int("RLH_SPMM_VEC", 1) != 0 && h->well_inbounds &&
-           (a.H == nullptr || (h->well_aligned && n_own % 8 == 0))) ? 1 : 0;
+  a.vec = (env_int("RLH_SPMM_VEC", 1) != 0 && h->stage_inbounds &&
+           (a.H == nullptr || (h->stage_aligned && n_own % 8 == 0))) ? 1 : 0;
   a.cy = (float)cy; a.cp = (float)cp; a.cb = (float)cb;
   if (h->wide_k == 2) {                           // row pairs: eight vectors per thread and row, NV / 8 sets of 128 threads
     if (nv == 8) return wide_bf16_launch<8, 1, 2>(h, part, a);

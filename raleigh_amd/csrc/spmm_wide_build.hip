@@ -2,7 +2,7 @@
 //
 // Rows are cut into blocks of 256 (one row per thread of a 256-thread workgroup).  Per block the
 // referenced columns are merged into windows of whole 16-column staging groups (spmm.h
-// find_windows); an entry stores its value and the 16-bit position of its column in the block's
+// analyse_blocks); an entry stores its value and the 16-bit position of its column in the block's
 // staged image.  Entries are stored in CHUNKS of 8 slots per row, as 16-byte pieces per thread:
 //   values    [chunk][piece k][row]   piece k = slots k * VPG .. + VPG - 1,  VPG = 16 / sizeof(T)
 //   positions [chunk][row]            8 x uint16
@@ -33,29 +33,13 @@ int wide_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices, const 
   const int64_t nblocks = (n + kWideRows - 1) / kWideRows;
   h->wide_blocks = 0;
   if (nblocks == 0 || h->nnz == 0) return 0;
-  std::vector<std::vector<Win>> wins((size_t)nblocks);
-  std::vector<int32_t> width((size_t)nblocks, 0), ngroups((size_t)nblocks, 0);
-  parallel_blocks(nblocks, [&](int64_t b) {
-    const int64_t r0 = b * kWideRows, r1 = (r0 + kWideRows < n) ? r0 + kWideRows : n;
-    int64_t w = 0;
-    for (int64_t r = r0; r < r1; ++r) w = std::max<int64_t>(w, indptr[r + 1] - indptr[r]);
-    width[b] = (int32_t)std::min<int64_t>(w, 1 << 20);
-    ngroups[b] = find_windows(indptr, indices, r0, r1, h->n_cols, 32, kWideGroup, 1, wins[b]) / kWideGroup;
-  });
-  int32_t wmax = 0, gmax = 0;
-  int64_t staged = 0, slots = 0;
-  for (int64_t b = 0; b < nblocks; ++b) {
-    wmax = std::max(wmax, width[b]);
-    gmax = std::max(gmax, ngroups[b]);
-    staged += (int64_t)ngroups[b] * kWideGroup;
-    slots += (int64_t)width[b] * kWideRows;
-  }
-  h->well_ratio = slots > 0 ? (double)staged / (double)slots : 0.0;
+  const BlockAnalysis an = analyse_blocks(indptr, indices, n, h->n_cols, kWideRows, kWideGroup, 1);
+  h->stage_ratio = an.ratio();
   // every block's image must fit the LDS with the smallest number of vectors per pass, positions
   // are 16 bits, a row has at most 8 * 32767 slots, and the group list must fit the header
-  if ((int64_t)gmax * kWideGroup * wide_stride(wide_min_nv(h->dtype), es) + 2 * kWideHeader > kWideLdsBytes) return 0;
-  if (gmax * 4 > kWideHeader || wmax > 8 * 32767) return 0;
-  if (!force && staged * 10 > slots * 9) return 0;      // too little column locality for the staging to pay
+  if ((int64_t)an.gmax * kWideGroup * wide_stride(wide_min_nv(h->dtype), es) + 2 * kWideHeader > kWideLdsBytes) return 0;
+  if (an.gmax * 4 > kWideHeader || an.wmax > 8 * 32767) return 0;
+  if (!force && an.staged * 10 > an.slots * 9) return 0;      // too little column locality for the staging to pay
   // Rows that share their column pattern with the row after them -- the unknowns of a node of a finite-element model: every
   // degree of freedom of a node couples to every degree of freedom of its neighbours -- are given to ONE thread in pairs: the
   // pair's entries are one position and two values, and the staged x values of an entry, which are what bounds the kernel
@@ -78,10 +62,10 @@ int wide_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices, const 
   std::vector<WideMeta> meta((size_t)nblocks);
   int64_t eoff = 0, goff = 0;
   for (int64_t b = 0; b < nblocks; ++b) {
-    const int nch = std::max(1, (width[b] + 7) / 8);
-    meta[b] = WideMeta{eoff, (int32_t)goff, (int16_t)nch, (int16_t)ngroups[b]};
+    const int nch = std::max(1, (an.width[b] + 7) / 8);
+    meta[b] = WideMeta{eoff, (int32_t)goff, (int16_t)nch, (int16_t)an.ngroups[b]};
     eoff += nch;
-    goff += ngroups[b];
+    goff += an.ngroups[b];
   }
   RLH_REQUIRE(goff < ((int64_t)1 << 31), "rlh_csr_create: too many staging groups");
   std::vector<int32_t> gsrc((size_t)goff);
@@ -90,8 +74,8 @@ int wide_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices, const 
   std::vector<char> idx((size_t)nchunks * TPS * 16, 0);
   std::vector<char> vals((size_t)nchunks * VP * kWideRows * 16, 0);
   parallel_blocks(nblocks, [&](int64_t b) {
-    const std::vector<Win> &ws = wins[b];
-    fill_group_sources(ws, ngroups[b], kWideGroup, gsrc.data() + meta[b].goff);
+    const std::vector<Win> &ws = an.wins[b];
+    fill_group_sources(ws, an.ngroups[b], kWideGroup, gsrc.data() + meta[b].goff);
     const int64_t r0 = b * kWideRows;
     for (int l = 0; l < kWideRows; ++l) {
       const int64_t r = r0 + l;
@@ -117,16 +101,11 @@ int wide_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices, const 
       }
     }
   });
-  h->well_inbounds = 1;
-  h->well_aligned = 1;
-  for (int64_t g = 0; g < goff; ++g) {
-    if ((int64_t)gsrc[g] + kWideGroup > h->n_cols) h->well_inbounds = 0;
-    if (gsrc[g] & 7) h->well_aligned = 0;
-  }
-  well_schedule(wins, nblocks, n, kWideRows, ctx().num_cu * 2, h->wide_order);
+  stage_flags(gsrc.data(), goff, kWideGroup, h->n_cols, &h->stage_inbounds, &h->stage_aligned);
+  well_schedule(an.wins, nblocks, n, kWideRows, ctx().num_cu * 2, h->wide_order);
   h->wide_maxcol.resize((size_t)nblocks);
-  for (int64_t b = 0; b < nblocks; ++b) h->wide_maxcol[(size_t)b] = wins[b].back().start + wins[b].back().len - 1;
-  h->wide_gmax = gmax;
+  for (int64_t b = 0; b < nblocks; ++b) h->wide_maxcol[(size_t)b] = an.wins[b].back().start + an.wins[b].back().len - 1;
+  h->wide_gmax = an.gmax;
   if (int rc = h->wide_meta.upload(meta.data(), (size_t)nblocks * sizeof(WideMeta))) return rc;
   if (int rc = h->wide_gsrc.upload(gsrc.data(), (size_t)goff * sizeof(int32_t), sizeof(int32_t))) return rc;
   if (int rc = h->wide_idx.upload(idx.data(), idx.size())) return rc;
