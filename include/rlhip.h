@@ -599,6 +599,41 @@ int rlh_fsapply_run(rlh_fsapply_t p, int64_t m, const void *X, int64_t ldx, void
 int rlh_fsapply_info(rlh_fsapply_t p, int *work, int64_t *stored_slots, int64_t *tail_entries, int64_t *device_bytes);
 int rlh_fsapply_destroy(rlh_fsapply_t p);
 
+/* ---- new matrix values on the kept pattern: every row of G is solved again, for a new matrix A', on the columns the
+ *      handle already has, and the new values go everywhere the handle and a plan keep them.  Only the numeric phase
+ *      of a build runs: no pattern walk, no enrichment, no filter, no transpose, no partition; nothing but status
+ *      records travels to the host.  What a handle of any create call above paid for its pattern is paid once for a
+ *      whole sequence of matrices (continuation, parameter sweeps, nonlinear or time-dependent operators).
+ * rlh_fsvalues_update_device: a canonical CSR matrix of the handle's n and dtype in DEVICE memory (index_bits 32 or
+ * 64).  The upper triangle defines A'; nothing below the diagonal is read.  The checks are those of the create calls on
+ * indptr[0], a decreasing indptr, the last entry against the allocations, the column range, strict ascent and a stored
+ * diagonal, with their messages under this entry point's name, each naming the smallest offending row.  The structure
+ * of A' may differ from that of the matrix the handle was built from: a position of a local block that A' does not
+ * store is zero, explicit zeros change nothing, and there is no partner check.
+ * rlh_fsvalues_update: the same from HOST arrays (int64 row pointers, int32 columns), which are uploaded and take the
+ * same path.
+ * Row i keeps its columns P; its values become those of the local solve of the create calls on S = A'[P, P] (the
+ * same kernel in the bin of the row's length, RLH_FSAI_BINS read as a create call reads it; a row's bits do not depend
+ * on its bin).  They are written into G and, conjugated, into the matching places of G^H: the bits a build on the
+ * same pattern would store.  Where the pattern came from levels alone and the structure of A' is that of A, the
+ * handle is bit for bit the fresh build of A'; where it was chosen by value (steps, drop) it is the Kaporin minimiser
+ * for A' on the pattern chosen for A.  A block that is not positive definite fails the call with the build's message.
+ * All or nothing: the rows are solved into scratch and committed when every one succeeded; after a failed call the
+ * handle holds the bits it held before.  Afterwards rlh_fsai_get and rlh_fsai_apply act on the new G; rlh_fsai_info
+ * (nnz, longest_row, truncated_rows, setup_seconds), rlh_fsfilter_info, rlh_fsai_levels and rlh_fsai_adaptive keep
+ * describing how the pattern was made.  The scratch lives for the call only: device_bytes does not change and
+ * rlh_device_live returns to its level.  n = 0 is a valid update that does nothing.  Synchronises.
+ * rlh_fsvalues_plan: refills the values of both layouts of a plan made from that handle from the handle's current
+ * arrays, rounded to the plan's V as at creation; W and the layout's structure stay.  A plan that is not refilled
+ * keeps applying the old values.  Refused, with a message naming the entry point, when n, the dtype, the entries or
+ * the row lengths of plan and handle do not match.  (Row-shard plans have no such call.)
+ * rlh_fsvalues_info: the successful updates of the handle and the device seconds of the last one (events). */
+int rlh_fsvalues_update_device(rlh_fsai_t h, int index_bits, const void *d_indptr, const void *d_indices,
+                               const void *d_values);
+int rlh_fsvalues_update(rlh_fsai_t h, const int64_t *indptr, const int32_t *indices, const void *values);
+int rlh_fsvalues_plan(rlh_fsapply_t p, rlh_fsai_t h);
+int rlh_fsvalues_info(rlh_fsai_t h, int64_t *updates, double *seconds);
+
 /* ---- the same application on a ROW SHARD of G: rank r owns the rows [r0, r1) of the vectors, G_loc = the rows
  *      [r0, r1) of G and GH_loc = the rows [r0, r1) of G^H (the own COLUMNS of G, values conjugated by the caller).
  * rlh_fsshard_create: HOST CSR arrays of the two matrices, n_own rows each.  A column c of G_loc is own row c for

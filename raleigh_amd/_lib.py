@@ -138,6 +138,10 @@ SIGNATURES = {
     'rlh_fsapply_run': [_p, _i64, _p, _i64, _p, _i64],
     'rlh_fsapply_info': [_p, ctypes.POINTER(_int), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
     'rlh_fsapply_destroy': [_p],
+    'rlh_fsvalues_update_device': [_p, _int, _p, _p, _p],
+    'rlh_fsvalues_update': [_p, _p, _p, _p],
+    'rlh_fsvalues_plan': [_p, _p],
+    'rlh_fsvalues_info': [_p, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)],
     'rlh_fsshard_create': [ctypes.POINTER(_p), _int, _int, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p],
     'rlh_fsshard_first': [_p, _i64, _p, _i64, _p, _i64],
     'rlh_fsshard_pack': [_p, _i64, _i64, _p, _p],

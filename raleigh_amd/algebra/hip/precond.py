@@ -262,12 +262,18 @@ class ApproximateInverse:
     matrices measured) a few more iterations.  The build stays on the device (rlh_fsfilter_create*), one filter and
     one more solve per row.  `dropped_entries` counts what was removed; `nnz`, `fill`, `longest_row`, `csr()` and a
     `work` plan describe the filtered G, `truncated_rows` what `max_row` held back before it.  ``drop=0`` (the default)
-    is the build without filtration through the entry points it always had."""
+    is the build without filtration through the entry points it always had.
+
+    `update_values(matrix)` keeps the pattern and solves every row again for a new matrix of the same size and type:
+    the set-up of a sequence of matrices (continuation, a parameter sweep, a nonlinear or time-dependent operator)
+    pays for the pattern once.  The result is the Kaporin minimiser for the new matrix on the kept pattern.  It is bit
+    for bit the fresh build where the pattern came from `levels` alone and the structure of the matrix is unchanged;
+    where the pattern was chosen by value (`steps`, `drop`) for the old values it is a different, still Hermitian
+    positive definite, preconditioner than a fresh build would give."""
 
     WORK = WORK
 
     def __init__(self, matrix, max_row=64, levels=1, steps=0, step_size=1, work=None, drop=0.0):
-        from . import device_data
         L = self._L = _lib.lib()                          # (the handle belongs to THIS library object)
         self._h = self._plan = None
         check_work(work, none_ok=True)
@@ -293,42 +299,15 @@ class ApproximateInverse:
             more, kind = (levels, steps, step_size), '_adaptive'
         else:                                               # (level 1 goes through the entry points it always had)
             more, kind = (() if levels == 1 else (levels,)), ('' if levels == 1 else '_levels')
-        t = None
-        if device_data.is_tensor(matrix):
-            from .sparse import operator_tensor
-            t = operator_tensor(matrix)
-            if not device_data._on_device(t):
-                matrix, t = device_data.to_host(t), None
+        self._dtype, self._n, self._nnz_a, bits, pointers, _alive = self._matrix_arrays(matrix)
+        code = _lib.DTYPE_CODE[self._dtype]
         # the entry point and its arguments between the handle and max_row (the arrays they point at live to the call)
-        if t is not None:
-            import torch
-            self._dtype = device_data.numpy_type(t)
-            crow, col, val = t.crow_indices(), t.col_indices(), t.values()
-            if col.dtype != crow.dtype:                     # (torch takes mixed index types: both as the wider one)
-                crow, col = crow.to(torch.int64), col.to(torch.int64)
-            crow, col = crow.contiguous(), col.contiguous()
-            val = val.detach().resolve_conj().resolve_neg().contiguous()
-            if val.is_cuda:                                 # the conversions may have launched work on torch's stream
-                torch.cuda.current_stream(val.device).synchronize()
-            self._n = int(t.shape[0])
-            self._nnz_a = int(val.numel())
+        if bits is not None:
             name = 'rlh_fsfilter_create_device' if drop else 'rlh_fsai_create%s_device' % kind
-            args = (_lib.DTYPE_CODE[self._dtype], self._n, 32 if crow.element_size() == 4 else 64,
-                    ctypes.c_void_p(crow.data_ptr()), ctypes.c_void_p(col.data_ptr()), ctypes.c_void_p(val.data_ptr()))
+            args = (code, self._n, bits) + pointers
         else:
-            from .sparse_data import canonical_csr
-            a = canonical_csr(matrix)
-            if a.shape[0] != a.shape[1]:
-                raise ValueError('a square matrix is needed, got %d x %d' % a.shape)
-            self._dtype = a.dtype.type
-            self._n = int(a.shape[0])
-            self._nnz_a = int(a.nnz)
-            indptr = np.ascontiguousarray(a.indptr, dtype=np.int64)
-            indices = np.ascontiguousarray(a.indices, dtype=np.int32)
-            values = np.ascontiguousarray(a.data)
             name = 'rlh_fsfilter_create' if drop else 'rlh_fsai_create' + kind
-            args = (_lib.DTYPE_CODE[self._dtype], self._n, _lib.host_ptr(indptr), _lib.host_ptr(indices),
-                    _lib.host_ptr(values))
+            args = (code, self._n) + pointers
         h = ctypes.c_void_p()
         check_work(work, self._dtype, none_ok=True)
         self._create(getattr(L, name), name, h, *args, max_row, *more)
@@ -339,9 +318,48 @@ class ApproximateInverse:
             self._plan = plan
 
     @staticmethod
+    def _matrix_arrays(matrix):
+        """What the constructor and `update_values` take as a matrix: (type, n, stored entries, index bits, the pointers
+        to row pointers, columns and values, the arrays those point at).  index bits 32 / 64: a tensor on the GPU, used
+        where it is (DEVICE pointers); None: a SciPy matrix or a CPU tensor as its SciPy matrix, canonical CSR with int64
+        row pointers and int32 columns (host pointers)."""
+        from . import device_data
+        t = None
+        if device_data.is_tensor(matrix):
+            from .sparse import operator_tensor
+            t = operator_tensor(matrix)
+            if not device_data._on_device(t):
+                matrix, t = device_data.to_host(t), None
+        if t is not None:
+            import torch
+            crow, col, val = t.crow_indices(), t.col_indices(), t.values()
+            if col.dtype != crow.dtype:                     # (torch takes mixed index types: both as the wider one)
+                crow, col = crow.to(torch.int64), col.to(torch.int64)
+            crow, col = crow.contiguous(), col.contiguous()
+            val = val.detach().resolve_conj().resolve_neg().contiguous()
+            if val.is_cuda:                                 # the conversions may have launched work on torch's stream
+                torch.cuda.current_stream(val.device).synchronize()
+            pointers = (ctypes.c_void_p(crow.data_ptr()), ctypes.c_void_p(col.data_ptr()), ctypes.c_void_p(val.data_ptr()))
+            return (device_data.numpy_type(t), int(t.shape[0]), int(val.numel()), 32 if crow.element_size() == 4 else 64,
+                    pointers, (crow, col, val))
+        from .sparse_data import canonical_csr
+        a = canonical_csr(matrix)
+        if a.shape[0] != a.shape[1]:
+            raise ValueError('a square matrix is needed, got %d x %d' % a.shape)
+        indptr = np.ascontiguousarray(a.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(a.indices, dtype=np.int32)
+        values = np.ascontiguousarray(a.data)
+        pointers = (_lib.host_ptr(indptr), _lib.host_ptr(indices), _lib.host_ptr(values))
+        return a.dtype.type, int(a.shape[0]), int(a.nnz), None, pointers, (indptr, indices, values)
+
+    @staticmethod
     def _create(fn, name, h, *args):
+        ApproximateInverse._checked(fn, name, ctypes.byref(h), *args)
+
+    @staticmethod
+    def _checked(fn, name, *args):
         try:
-            _lib.check(fn(ctypes.byref(h), *args))
+            _lib.check(fn(*args))
         except _lib.RlhError as e:
             text = str(e)
             if ': %s:' % name not in text:                  # a HIP failure, not the library's own check
@@ -362,6 +380,7 @@ class ApproximateInverse:
         self.setup_seconds = float(sec.value)
         self.fill = self.nnz / float(max(self._nnz_a, 1))
         self.dropped_entries = 0
+        self.updates, self.update_seconds = 0, 0.0
         if self.drop:
             drop, removed = ctypes.c_double(), ctypes.c_int64()
             _lib.check(self._L.rlh_fsfilter_info(h, ctypes.byref(drop), ctypes.byref(removed)))
@@ -380,6 +399,30 @@ class ApproximateInverse:
                 self._L.rlh_fsai_destroy(h)
             except Exception:
                 pass
+
+    def update_values(self, matrix):
+        """New matrix values on the kept pattern: every row of G is solved again for `matrix` on the columns it has
+        (rlh_fsvalues_update*: the numeric phase of the build alone, on the device), then the plan of a `work` form is
+        refilled.  matrix: what the constructor takes, of the same size and type; its structure may differ (a position
+        it does not store counts as zero).  `updates` counts the successful calls, `update_seconds` holds the device
+        seconds of the last; `nnz`, `fill`, `longest_row`, `truncated_rows`, `dropped_entries` and `setup_seconds` keep
+        describing the build.  A refused matrix leaves the preconditioner as it was."""
+        dtype, n, _, bits, pointers, _alive = self._matrix_arrays(matrix)
+        if n != self._n:
+            raise ValueError('the preconditioner was built for a matrix of size %d, got one of size %d' % (self._n, n))
+        if np.dtype(dtype) != np.dtype(self._dtype):
+            raise ValueError('the preconditioner was built for a matrix of type %s, got one of type %s'
+                             % (np.dtype(self._dtype).name, np.dtype(dtype).name))
+        L = self._L
+        if bits is not None:
+            self._checked(L.rlh_fsvalues_update_device, 'rlh_fsvalues_update_device', self._h, bits, *pointers)
+        else:
+            self._checked(L.rlh_fsvalues_update, 'rlh_fsvalues_update', self._h, *pointers)
+        if self._plan:
+            _lib.check(L.rlh_fsvalues_plan(self._plan, self._h))
+        updates, sec = ctypes.c_int64(), ctypes.c_double()
+        _lib.check(L.rlh_fsvalues_info(self._h, ctypes.byref(updates), ctypes.byref(sec)))
+        self.updates, self.update_seconds = int(updates.value), float(sec.value)
 
     def size(self):
         return self._n

@@ -47,6 +47,12 @@
 // create_device check it and run fsai_build inside make_handle.  fsai_build is the one build path: its device arrays are
 // DevBufs (FsaiScratch holds those that pattern_totals works on), pattern_totals is the scan-fetch-wait-check sequence after the level pattern and again after
 // enrichment, and for_each_bin with launch_bin launches the enrichment and the set-up kernels bin by bin.
+//
+// New values on the kept pattern (rlh_fsvalues_update*, fsai_update): the numeric phase alone.  checked_input (shared with
+// the build: the checks on the arrays as they came), fsai_kept_rows (a stored diagonal, the rows' lengths from the
+// handle's G, the keys of the bins), pattern_totals, fsai_bin_rows, then solve_rows (shared with the build: fsai_setup
+// bin by bin) into a scratch value array, the pattern read from the operator's own arrays of G.  Only when every row
+// succeeded do the values go to G and, conjugated, to G^H (spd_set_values, spmm_data.h); structure and partitions stay.
 #include "fsai.h"
 
 #include <algorithm>
@@ -184,6 +190,30 @@ __global__ __launch_bounds__(kBlock) void fsai_fill(int64_t n, const int32_t *__
     for (int64_t t = 0; t < k; ++t) gi[g0 + t] = ix[a0 + t];
     put_row(bins, i);
   }
+}
+
+// An update of the values (rlh_fsvalues_update*) keeps the pattern: per row the new matrix must store its diagonal
+// (nothing else is asked of its structure: the solve reads entries on or above the diagonal and takes a missing one
+// as zero); the kept entries of the row are those of the handle's G (gp: its row pointers), the keys those of its bin
+__global__ __launch_bounds__(kBlock) void fsai_kept_rows(int64_t n, int four, const int64_t *__restrict__ ip,
+                                                         const int32_t *__restrict__ ix, const int64_t *__restrict__ gp,
+                                                         int64_t *__restrict__ cnt, int64_t *__restrict__ keya,
+                                                         int64_t *__restrict__ keyb, FsaiStatus *st) {
+  if (failed(st)) return;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+    const int64_t ke = ip[i + 1], d = lower_bound_col(ix, ip[i], ke, i);
+    if (d == ke || (int64_t)ix[d] != i) build_error(st, kErrDiag, i);
+    const int64_t k = gp[i + 1] - gp[i];
+    cnt[i] = k;
+    bin_keys(k, four, &keya[i], &keyb[i]);
+  }
+}
+
+// the rows of the bins alone (an update: the columns of G stay where they are)
+__global__ __launch_bounds__(kBlock) void fsai_bin_rows(int64_t n, Bins bins) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) put_row(bins, i);
 }
 
 // lanes of one wave that exchange data through the LDS: the LDS serves a wave's accesses in order; this keeps the
@@ -643,6 +673,13 @@ struct FsaiScratch {
   DevBuf<int64_t> cnt, ka, kb;            // per row: kept entries and the keys of the bin,
   DevBuf<int64_t> gp, sa, sb, bsum;       // their exclusive scans and the scans' tile sums
   hipEvent_t e0 = nullptr, e1 = nullptr;
+  int alloc_rows(int64_t n) {             // everything above but the status record, for n rows
+    for (DevBuf<int64_t> *p : {&cnt, &ka, &kb})
+      if (int rc = p->alloc(n)) return rc;
+    for (DevBuf<int64_t> *p : {&gp, &sa, &sb})
+      if (int rc = p->alloc(n + 1)) return rc;
+    return bsum.alloc((n + kScanTile - 1) / kScanTile + 1);
+  }
   ~FsaiScratch() {
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
@@ -713,10 +750,78 @@ int pattern_totals(const char *name, int64_t n, const FsaiScratch &w, int64_t ca
   return 0;
 }
 
+// The caller's arrays once they have passed the checks on them as they came: indptr as int64 and columns as int32 (the
+// caller's own arrays where they already are, else converted copies that live as long as this record).  cap: the
+// entries the index and value arrays can hold; nnz: indptr's last entry.
+struct FsaiInput {
+  const int64_t *ip64 = nullptr;
+  const int32_t *ix32 = nullptr;
+  DevBuf<int64_t> indptr;
+  DevBuf<int32_t> cols;
+  int64_t cap = INT64_MAX, nnz = 0;
+};
+
+// The checks of a build and of an update on ip, ix, va (device arrays, n >= 1): indptr, then the columns of every row.
+// Allocates and initialises w.status; *hs is the record as the host saw it last.
+template <typename T, typename P, typename I>
+int checked_input(const char *name, int64_t n, const P *ip, const I *ix, const T *va, FsaiScratch &w, FsaiStatus *hs, FsaiInput *in) {
+  hipStream_t st = ctx().stream;
+  const dim3 blk(kBlock);
+  int64_t cap = INT64_MAX;
+  const int64_t room_p = bytes_from(ip), room_i = bytes_from(ix), room_v = bytes_from(va);
+  RLH_REQUIRE(room_p < 0 || room_p >= (int64_t)sizeof(P) * (n + 1), "%s: the indptr array holds fewer than n + 1 entries", name);
+  if (!ix || !va) cap = 0;
+  if (room_i >= 0) cap = std::min<int64_t>(cap, room_i / (int64_t)sizeof(I));
+  if (room_v >= 0) cap = std::min<int64_t>(cap, room_v / (int64_t)sizeof(T));
+  in->cap = cap;
+  if (int rc = w.status.alloc(1)) return rc;
+  *hs = FsaiStatus{};
+  hs->err = kNoError;
+  RLH_HIP(hipMemcpyAsync(w.status, hs, sizeof *hs, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(spd_check_indptr<P>, dim3(blocks_for(n + 1, kBlock, 4096)), blk, 0, st, n, ip, cap, w.status);
+  hipLaunchKernelGGL((fsai_check_columns<P, I>), dim3(blocks_for(n, kBlock / 64, 8192)), blk, 0, st, n, ip, ix, w.status);
+  RLH_HIP(hipGetLastError());
+  RLH_HIP(hipMemcpyAsync(hs, w.status, sizeof *hs, hipMemcpyDeviceToHost, st));
+  RLH_HIP(hipStreamSynchronize(st));
+  if (hs->err != kNoError) return report(name, *hs, cap);
+  const int64_t nnz = in->nnz = hs->nnz;
+  if constexpr (std::is_same<P, int64_t>::value) {
+    in->ip64 = ip;
+  } else {
+    if (int rc = in->indptr.alloc(n + 1)) return rc;
+    hipLaunchKernelGGL((spd_convert_index<P, int64_t>), dim3(blocks_for(n + 1, kBlock, 4096)), blk, 0, st, n + 1, ip, in->indptr.get());
+    in->ip64 = in->indptr;
+  }
+  if constexpr (std::is_same<I, int32_t>::value) {
+    in->ix32 = ix;
+  } else {
+    if (int rc = in->cols.alloc(std::max<int64_t>(nnz, 1))) return rc;
+    if (nnz) hipLaunchKernelGGL((spd_convert_index<I, int32_t>), dim3(blocks_for(nnz, kBlock, 8192)), blk, 0, st, nnz, ix, in->cols.get());
+    in->ix32 = in->cols;
+  }
+  return 0;
+}
+
+// Every row solved on its pattern, bin by bin (the pattern of gp and `columns`, the bins as they stand, the values to
+// `values`); the host waits and reports what the kernels found.
+template <typename T>
+int solve_rows(const char *name, int64_t n, const Bins &bins, const FsaiInput &in, const T *va, const int64_t *gp, const int32_t *columns,
+               T *values, const FsaiScratch &w, FsaiStatus *hs) {
+  hipStream_t st = ctx().stream;
+  for_each_bin(bins, n, [&](auto lanes, int64_t count, const int32_t *list) {
+    constexpr int kLanes = decltype(lanes)::value;
+    launch_bin<T, kLanes>(fsai_setup<T, kLanes>, count, list, in.ip64, in.ix32, va, gp, columns, values, w.status.get());
+  });
+  RLH_HIP(hipGetLastError());
+  RLH_HIP(hipMemcpyAsync(hs, w.status, sizeof *hs, hipMemcpyDeviceToHost, st));
+  RLH_HIP(hipStreamSynchronize(st));
+  return hs->err != kNoError ? report(name, *hs, in.cap) : 0;
+}
+
 // `name`: the entry point the messages speak for.  ip, ix, va: device arrays, n >= 1.
 template <typename T, typename P, typename I>
 int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T *va, const FsaiPlan &plan) {
-  const int64_t es = sizeof(T), n = h->n;
+  const int64_t n = h->n;
   const int max_row = plan.max_row, levels = plan.levels, steps = plan.steps, step_size = plan.step_size, four = plan.four;
   const int grow = plan.grow();
   hipStream_t st = ctx().stream;
@@ -725,52 +830,17 @@ int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T 
   RLH_HIP(hipEventCreate(&w.e0));
   RLH_HIP(hipEventCreate(&w.e1));
   RLH_HIP(hipEventRecord(w.e0, st));
-  // ---- the checks on the arrays as they came
-  int64_t cap = INT64_MAX;
-  const int64_t room_p = bytes_from(ip), room_i = bytes_from(ix), room_v = bytes_from(va);
-  RLH_REQUIRE(room_p < 0 || room_p >= (int64_t)sizeof(P) * (n + 1), "%s: the indptr array holds fewer than n + 1 entries", name);
-  if (!ix || !va) cap = 0;
-  if (room_i >= 0) cap = std::min<int64_t>(cap, room_i / (int64_t)sizeof(I));
-  if (room_v >= 0) cap = std::min<int64_t>(cap, room_v / es);
-  if (int rc = w.status.alloc(1)) return rc;
   FsaiStatus hs{};
-  hs.err = kNoError;
-  RLH_HIP(hipMemcpyAsync(w.status, &hs, sizeof hs, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(spd_check_indptr<P>, dim3(blocks_for(n + 1, kBlock, 4096)), blk, 0, st, n, ip, cap, w.status);
-  hipLaunchKernelGGL((fsai_check_columns<P, I>), dim3(blocks_for(n, kBlock / 64, 8192)), blk, 0, st, n, ip, ix, w.status);
-  RLH_HIP(hipGetLastError());
-  RLH_HIP(hipMemcpyAsync(&hs, w.status, sizeof hs, hipMemcpyDeviceToHost, st));
-  RLH_HIP(hipStreamSynchronize(st));
-  if (hs.err != kNoError) return report(name, hs, cap);
-  const int64_t nnz = hs.nnz;
-  // ---- indptr as int64 and columns as int32 (the caller's own arrays where they already are)
-  const int64_t *ip64;
-  const int32_t *ix32;
-  DevBuf<int64_t> indptr;
-  DevBuf<int32_t> cols;
-  if constexpr (std::is_same<P, int64_t>::value) {
-    ip64 = ip;
-  } else {
-    if (int rc = indptr.alloc(n + 1)) return rc;
-    hipLaunchKernelGGL((spd_convert_index<P, int64_t>), dim3(blocks_for(n + 1, kBlock, 4096)), blk, 0, st, n + 1, ip, indptr);
-    ip64 = indptr;
-  }
-  if constexpr (std::is_same<I, int32_t>::value) {
-    ix32 = ix;
-  } else {
-    if (int rc = cols.alloc(std::max<int64_t>(nnz, 1))) return rc;
-    if (nnz) hipLaunchKernelGGL((spd_convert_index<I, int32_t>), dim3(blocks_for(nnz, kBlock, 8192)), blk, 0, st, nnz, ix, cols);
-    ix32 = cols;
-  }
+  FsaiInput in;
+  if (int rc = checked_input(name, n, ip, ix, va, w, &hs, &in)) return rc;
+  const int64_t cap = in.cap;
+  const int64_t *ip64 = in.ip64;
+  const int32_t *ix32 = in.ix32;
   // ---- the pattern
-  const int64_t nb = (n + kScanTile - 1) / kScanTile;
   const int64_t most = (int64_t)ctx().num_cu * kSetupBlocksPerCu;
   DevBuf<int64_t> start;
-  for (DevBuf<int64_t> *p : {&w.cnt, &w.ka, &w.kb, &start})
-    if (int rc = p->alloc(n)) return rc;
-  for (DevBuf<int64_t> *p : {&w.gp, &w.sa, &w.sb})
-    if (int rc = p->alloc(n + 1)) return rc;
-  if (int rc = w.bsum.alloc(nb + 1)) return rc;
+  if (int rc = w.alloc_rows(n)) return rc;
+  if (int rc = start.alloc(n)) return rc;
   hipLaunchKernelGGL(fsai_count, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, max_row, levels == 1 ? 1 : 0, four, grow, ip64,
                      ix32, w.cnt, w.ka, w.kb, start, w.status);
   hipLaunchKernelGGL(fsai_resolve_error, dim3(1), dim3(1), 0, st, n, ip64, ix32, w.status);
@@ -821,18 +891,8 @@ int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T 
   h->longest = hs.longest;
   DevBuf<T> gv;
   if (int rc = gv.alloc(gnnz)) return rc;
-  // ---- the rows, bin by bin (the pattern of w.gp and `columns`, the bins as they stand); the host waits and reports
-  auto solve_rows = [&](const int32_t *columns, T *values) -> int {
-    for_each_bin(bins, n, [&](auto lanes, int64_t count, const int32_t *list) {
-      constexpr int kLanes = decltype(lanes)::value;
-      launch_bin<T, kLanes>(fsai_setup<T, kLanes>, count, list, ip64, ix32, va, w.gp.get(), columns, values, w.status.get());
-    });
-    RLH_HIP(hipGetLastError());
-    RLH_HIP(hipMemcpyAsync(&hs, w.status, sizeof hs, hipMemcpyDeviceToHost, st));
-    RLH_HIP(hipStreamSynchronize(st));
-    return hs.err != kNoError ? report(name, hs, cap) : 0;
-  };
-  if (int rc = solve_rows(gi, gv)) return rc;
+  // ---- the rows, bin by bin (the pattern of w.gp and gi, the bins as they stand)
+  if (int rc = solve_rows<T>(name, n, bins, in, va, w.gp, gi, gv, w, &hs)) return rc;
   if (plan.drop > 0) {
     // ---- post-filtration: the kept columns of every row go to a slab at the row's old offset; counts, keys and scans
     // are made again, the slab is compacted (fsai_fill again) and every row is solved once more on what is left, in
@@ -855,7 +915,7 @@ int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T 
     if (int rc = gi_kept.alloc(gnnz)) return rc;
     if (int rc = gv_kept.alloc(gnnz)) return rc;
     hipLaunchKernelGGL(fsai_fill, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, kept_cols, old_gp, w.gp, gi_kept, bins);
-    if (int rc = solve_rows(gi_kept, gv_kept)) return rc;
+    if (int rc = solve_rows<T>(name, n, bins, in, va, w.gp, gi_kept, gv_kept, w, &hs)) return rc;
     gi = std::move(gi_kept);                       // (the stream is idle: nothing reads the unfiltered G any more)
     gv = std::move(gv_kept);
     h->nnz = gnnz;
@@ -872,7 +932,7 @@ int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T 
     RLH_HIP(hipGetLastError());
     rc = rlh_spd_create_device(&h->spd, h->dtype, n, n, 32, gp32, gi, gv);
   } else {
-    cols.reset();                     // (the set-up was the last to read the converted columns)
+    in.cols.reset();                  // (the set-up was the last to read the converted columns)
     if (int rc2 = gi64.alloc(gnnz)) return rc2;
     hipLaunchKernelGGL((spd_convert_index<int32_t, int64_t>), dim3(blocks_for(gnnz, kBlock, 8192)), blk, 0, st, gnnz, gi, gi64);
     rc = rlh_spd_create_device(&h->spd, h->dtype, n, n, 64, w.gp, gi64, gv);
@@ -893,6 +953,65 @@ int fsai_build_any(rlh_fsai *h, const char *name, const void *ip, const void *ix
     case RLH_D: return fsai_build<double, P, I>(h, name, (const P *)ip, (const I *)ix, (const double *)va, plan);
     case RLH_C: return fsai_build<c32, P, I>(h, name, (const P *)ip, (const I *)ix, (const c32 *)va, plan);
     case RLH_Z: return fsai_build<c64, P, I>(h, name, (const P *)ip, (const I *)ix, (const c64 *)va, plan);
+  }
+  return 1;
+}
+
+// New values on the pattern the handle has (rlh_fsvalues_update*): the checks of a build on the new arrays (no partner
+// check: nothing below the diagonal is read), the bins of the rows' lengths, every row solved into scratch by the
+// build's own fsai_setup and, when all succeeded, the values committed to G and G^H of the handle's operator.  What
+// the update allocates is released when it returns; the handle's index arrays and partitions are not touched.
+template <typename T, typename P, typename I>
+int fsai_update(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T *va) {
+  const int64_t n = h->n;
+  const int four = four_bins();
+  hipStream_t st = ctx().stream;
+  const dim3 blk(kBlock);
+  FsaiScratch w;
+  RLH_HIP(hipEventCreate(&w.e0));
+  RLH_HIP(hipEventCreate(&w.e1));
+  RLH_HIP(hipEventRecord(w.e0, st));
+  FsaiStatus hs{};
+  FsaiInput in;
+  if (int rc = checked_input(name, n, ip, ix, va, w, &hs, &in)) return rc;
+  const SpdArrays g = spd_arrays(h->spd, 0);
+  const unsigned grid = blocks_for(n, kBlock, (int64_t)ctx().num_cu * kSetupBlocksPerCu);
+  if (int rc = w.alloc_rows(n)) return rc;
+  hipLaunchKernelGGL(fsai_kept_rows, dim3(grid), blk, 0, st, n, four, in.ip64, in.ix32, g.indptr, w.cnt.get(), w.ka.get(), w.kb.get(),
+                     w.status.get());
+  int64_t gnnz = 0;
+  Bins bins{};
+  if (int rc = pattern_totals(name, n, w, in.cap, g.nnz, g.nnz, &hs, &gnnz, &bins)) return rc;
+  DevBuf<int32_t> bin_rows;
+  DevBuf<T> gv;
+  if (int rc = bin_rows.alloc(n)) return rc;
+  if (int rc = gv.alloc(gnnz)) return rc;
+  bins.rows = bin_rows;
+  hipLaunchKernelGGL(fsai_bin_rows, dim3(grid), blk, 0, st, n, bins);
+  if (int rc = solve_rows<T>(name, n, bins, in, va, g.indptr, g.idx, gv, w, &hs)) return rc;
+  // ---- every row succeeded: the new values go to the operator
+  if (int rc = spd_set_values(h->spd, gv)) return rc;
+  RLH_HIP(hipEventRecord(w.e1, st));
+  RLH_HIP(hipEventSynchronize(w.e1));        // the caller's arrays and the scratch are not referenced after the return
+  float ms = 0.f;
+  RLH_HIP(hipEventElapsedTime(&ms, w.e0, w.e1));
+  h->update_seconds = 1e-3 * ms;
+  ++h->updates;
+  return 0;
+}
+
+template <typename P, typename I>
+int fsai_update_any(rlh_fsai *h, const char *name, const void *ip, const void *ix, const void *va) {
+  if (h->n == 0 || !h->spd) {               // nothing to solve: a valid update
+    h->update_seconds = 0;
+    ++h->updates;
+    return 0;
+  }
+  switch (h->dtype) {
+    case RLH_S: return fsai_update<float, P, I>(h, name, (const P *)ip, (const I *)ix, (const float *)va);
+    case RLH_D: return fsai_update<double, P, I>(h, name, (const P *)ip, (const I *)ix, (const double *)va);
+    case RLH_C: return fsai_update<c32, P, I>(h, name, (const P *)ip, (const I *)ix, (const c32 *)va);
+    case RLH_Z: return fsai_update<c64, P, I>(h, name, (const P *)ip, (const I *)ix, (const c64 *)va);
   }
   return 1;
 }
@@ -1027,6 +1146,45 @@ extern "C" int rlh_fsfilter_info(rlh_fsai_t h, double *drop, int64_t *removed) {
   RLH_REQUIRE(h && drop && removed, "rlh_fsfilter_info: null handle or output");
   *drop = h->drop;
   *removed = h->removed;
+  return 0;
+}
+
+extern "C" int rlh_fsvalues_update_device(rlh_fsai_t h, int index_bits, const void *d_indptr, const void *d_indices,
+                                          const void *d_values) {
+  constexpr const char *name = "rlh_fsvalues_update_device";
+  if (int rc = require_ready()) return rc;
+  RLH_REQUIRE(h != nullptr, "%s: null handle", name);
+  RLH_REQUIRE(d_indptr, "%s: null indptr", name);
+  RLH_REQUIRE(index_bits == 32 || index_bits == 64, "%s: index_bits must be 32 or 64, got %d", name, index_bits);
+  return index_bits == 32 ? fsai_update_any<int32_t, int32_t>(h, name, d_indptr, d_indices, d_values)
+                          : fsai_update_any<int64_t, int64_t>(h, name, d_indptr, d_indices, d_values);
+}
+
+extern "C" int rlh_fsvalues_update(rlh_fsai_t h, const int64_t *indptr, const int32_t *indices, const void *values) {
+  constexpr const char *name = "rlh_fsvalues_update";
+  if (int rc = require_ready()) return rc;
+  RLH_REQUIRE(h != nullptr, "%s: null handle", name);
+  RLH_REQUIRE(indptr, "%s: null indptr", name);
+  // what decides how much is uploaded is checked here; everything else by the kernels, as for device arrays
+  const int64_t n = h->n;
+  RLH_REQUIRE(indptr[0] == 0, "%s: indptr[0] must be 0", name);
+  for (int64_t r = 0; r < n; ++r) RLH_REQUIRE(indptr[r + 1] >= indptr[r], "%s: indptr decreases at row %lld", name, (long long)r);
+  const int64_t nnz = indptr[n], es = dtype_size(h->dtype);
+  RLH_REQUIRE(nnz == 0 || (indices && values), "%s: null indices or values", name);
+  if (n == 0) return fsai_update_any<int64_t, int32_t>(h, name, indptr, indices, values);
+  DevBuf<int64_t> d_ip;
+  DevBuf<int32_t> d_ix;
+  DevBuf<void> d_va;
+  if (int rc = d_ip.upload(indptr, (size_t)(n + 1) * 8)) return rc;
+  if (int rc = d_ix.upload(indices, (size_t)nnz * 4, 4)) return rc;
+  if (int rc = d_va.upload(values, (size_t)(nnz * es), 16)) return rc;
+  return fsai_update_any<int64_t, int32_t>(h, name, d_ip, d_ix, d_va);
+}
+
+extern "C" int rlh_fsvalues_info(rlh_fsai_t h, int64_t *updates, double *seconds) {
+  RLH_REQUIRE(h, "rlh_fsvalues_info: null handle");
+  if (updates) *updates = h->updates;
+  if (seconds) *seconds = h->update_seconds;
   return 0;
 }
 

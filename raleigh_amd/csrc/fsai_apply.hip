@@ -33,6 +33,9 @@
 // the last tile are written as zeros and never stored to Y.  X is gathered and Y written column-major with lanes on
 // consecutive rows, at element alignment.  No atomics, no LDS: the order of every sum is fixed by the layout.
 //
+// New values (rlh_fsvalues_plan): after the handle's values were updated on its kept pattern, fsap_fill runs again on the
+// plan's kept layouts, once fsap_same_rows has found every row as long in the layout as in the handle; W and the structure stay.
+//
 // Row shards (rlh_fsshard_*, at the end of the file): the same layout and the same two products on a rank's rows of G
 // and of G^H, as the compile-time variant SHARD of fsap_product; the halo rows of W travel between the two products.
 #include "fsai.h"
@@ -213,6 +216,15 @@ __global__ __launch_bounds__(kBlock) void fsap_check(LayoutView L, ApplyStatus *
   }
 }
 
+// A kept layout against the row pointers of the matrix whose values are to refill it (rlh_fsvalues_plan): row r must
+// hold as many entries, sliced part and tail together, as the matrix stores there -- then fsap_fill stays inside both
+constexpr int kRefillBlocksPerCu = 8;
+__global__ __launch_bounds__(kBlock) void fsap_same_rows(LayoutView L, const int64_t *__restrict__ ip, ApplyStatus *st) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < L.n; r += stride)
+    if (ip[r + 1] - ip[r] != (int64_t)L.rlen[r] + (L.tptr[r + 1] - L.tptr[r])) build_error(st, kErrLength, r);
+}
+
 // ---------------------------------------------------------------- the products
 template <typename Wt> struct alignas(16) WRow { Wt e[kVT]; };
 
@@ -306,6 +318,7 @@ __global__ __launch_bounds__(kBlock) void fsap_product(LayoutView L, int64_t m, 
 // ---------------------------------------------------------------- the host side
 struct Layout {
   int64_t n = 0, ncol = 0, slices = 0, slots = 0, tail = 0;
+  int64_t nnz = 0;                   // entries of the matrix it was built from
   DevBuf<int64_t> off, tptr;
   DevBuf<int32_t> width, rlen, col, tcol;
   DevBuf<void> val, tval;
@@ -330,6 +343,12 @@ int report(const ApplyStatus &s, const char *which, int64_t nnz, const char *ent
   return 1;
 }
 
+// columns and values (rounded once to V) of the CSR arrays a into the slots and tails of a layout whose structure stands
+template <typename T, typename V> void fill_layout(Layout &L, const SpdArrays &a) {
+  hipLaunchKernelGGL((fsap_fill<T, V>), dim3(blocks_for(L.slices, kWaves, 1 << 20)), dim3(kBlock), 0, ctx().stream, L.view(), a.indptr,
+                     a.idx, (const T *)a.val, L.col.get(), (V *)L.val.get(), L.tcol.get(), (V *)L.tval.get());
+}
+
 // The layout of one orientation (a: its CSR arrays in device memory, `which` names it and `entry` the entry point in
 // messages).
 template <typename T, typename V> int build_layout(Layout &L, const SpdArrays &a, const char *which, const char *entry) {
@@ -340,6 +359,7 @@ template <typename T, typename V> int build_layout(Layout &L, const SpdArrays &a
   L.n = n;
   L.ncol = a.cols;
   L.slices = slices;
+  L.nnz = a.nnz;
   if (int rc = L.off.alloc(slices + 1)) return rc;
   if (int rc = L.width.alloc(slices)) return rc;
   if (int rc = L.rlen.alloc(n)) return rc;
@@ -367,8 +387,7 @@ template <typename T, typename V> int build_layout(Layout &L, const SpdArrays &a
     if (int rc = L.tcol.alloc(L.tail)) return rc;
     if (int rc = L.tval.alloc((size_t)L.tail * sizeof(V))) return rc;
   }
-  hipLaunchKernelGGL((fsap_fill<T, V>), dim3(grid), blk, 0, st, L.view(), a.indptr, a.idx, (const T *)a.val, L.col.get(),
-                     (V *)L.val.get(), L.tcol.get(), (V *)L.tval.get());
+  fill_layout<T, V>(L, a);
   ApplyStatus hs{};
   hs.err = kNoError;
   RLH_HIP(hipMemcpyAsync(status, &hs, sizeof hs, hipMemcpyHostToDevice, st));
@@ -546,6 +565,54 @@ extern "C" int rlh_fsapply_info(rlh_fsapply_t p, int *work, int64_t *stored_slot
 }
 
 extern "C" int rlh_fsapply_destroy(rlh_fsapply_t p) { return plan_destroy(p); }
+
+namespace rlh {
+namespace {
+
+// the values of a (and its columns, which are the layout's own) into a layout made from a matrix of the same rows
+template <typename T, typename V> int refill_layout(Layout &L, const SpdArrays &a, const char *which, const char *entry) {
+  hipStream_t st = ctx().stream;
+  DevBuf<ApplyStatus> status;
+  if (int rc = status.alloc(1)) return rc;
+  ApplyStatus hs{};
+  hs.err = kNoError;
+  RLH_HIP(hipMemcpyAsync(status, &hs, sizeof hs, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(fsap_same_rows, dim3(blocks_for(L.n, kBlock, (int64_t)ctx().num_cu * kRefillBlocksPerCu)), dim3(kBlock), 0, st,
+                     L.view(), a.indptr, status.get());
+  RLH_HIP(hipGetLastError());
+  RLH_HIP(hipMemcpyAsync(&hs, status, sizeof hs, hipMemcpyDeviceToHost, st));
+  RLH_HIP(hipStreamSynchronize(st));
+  if (hs.err != kNoError) {
+    set_error("%s: row %lld of %s has another length in the plan than in the handle", entry,
+              (long long)(hs.err & (((unsigned long long)1 << 56) - 1)), which);
+    return 1;
+  }
+  fill_layout<T, V>(L, a);
+  RLH_HIP(hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+}  // namespace rlh
+
+extern "C" int rlh_fsvalues_plan(rlh_fsapply_t p, rlh_fsai_t h) {
+  constexpr const char *kEntry = "rlh_fsvalues_plan";
+  if (int rc = require_ready()) return rc;
+  RLH_REQUIRE(p != nullptr, "%s: null plan", kEntry);
+  RLH_REQUIRE(h != nullptr, "%s: null handle", kEntry);
+  RLH_REQUIRE(p->dtype == h->dtype, "%s: the plan's dtype (%d) is not the handle's (%d)", kEntry, p->dtype, h->dtype);
+  RLH_REQUIRE(p->n_own == h->n, "%s: the plan has %lld rows, the handle %lld", kEntry, (long long)p->n_own, (long long)h->n);
+  if (h->n == 0 || !h->spd) return 0;
+  const SpdArrays g = spd_arrays(h->spd, 0), gh = spd_arrays(h->spd, 1);
+  RLH_REQUIRE(p->g.nnz == g.nnz && p->gh.nnz == gh.nnz, "%s: the plan holds %lld entries of G, the handle %lld", kEntry,
+              (long long)p->g.nnz, (long long)g.nnz);
+  return with_types(p->dtype, p->work, [&](auto t, auto v, auto) {
+    using T = decltype(t);
+    using V = decltype(v);
+    if (int rc = refill_layout<T, V>(p->g, g, "G", kEntry)) return rc;
+    return refill_layout<T, V>(p->gh, gh, "G^H", kEntry);
+  });
+}
 
 // ---------------------------------------------------------------- the application on a row shard (rlh_fsshard_*)
 namespace rlh {

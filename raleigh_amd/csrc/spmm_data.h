@@ -15,4 +15,10 @@ struct SpdArrays {
 };
 SpdArrays spd_arrays(const rlh_spd *h, int transp);
 
+// New values on the structure the operator has: d_values (DEVICE memory, nnz values of the operator's type in the
+// order of A's entries) are copied into A's value array and their conjugates written to the matching places of A^H --
+// the bits rlh_spd_create_device would make from the same A.  Index arrays and partitions are not touched; nothing is
+// allocated.  Asynchronous on the library stream: d_values must live until the stream has passed this point.
+int spd_set_values(rlh_spd *h, const void *d_values);
+
 }  // namespace rlh

@@ -18,6 +18,8 @@
 //   4. deinterleave: Yi -> Y by columns (coalesced stores) with the rank-one epilogue Y[:, j] -= c[j] u.
 // The partition (the row at which each subgroup starts) depends on the matrix alone and is built with the
 // handle.  Every offset that scales with nnz or rows x vectors is 64-bit.
+// spd_set_values (spmm_data.h) gives an operator new values on the structure it has: A's values are copied, those of
+// A^H written by spd_conj_values; index arrays and partitions stay.
 #include "common.h"
 #include "device_build.h"
 #include "spmm_data.h"
@@ -535,6 +537,47 @@ int create_device_impl(rlh_spd *h, int64_t M, int64_t N, const I *ip, const I *i
   return 0;
 }
 
+// ---------------------------------------------------------------- new values on the structure the operator has
+constexpr int kValuesBlocksPerCu = 8;   // grid of spd_conj_values: at most this many workgroups per CU
+
+// Entry k of A^H is (j, i): j the last row of A^H with tp[j] <= k (tp[N] = nnz > k; empty rows share their start with
+// the row that holds k and come before it), i = tx[k].  It takes the conjugate of A's entry (i, j), found by a binary
+// search for column j in the sorted row i of A: every place is written once, by one thread, from one value -- the
+// bits spd_scatter makes.  A thread per entry in a grid-stride loop; no atomics, no LDS.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void spd_conj_values(int64_t N, int64_t nnz, const int64_t *__restrict__ ip,
+                                                          const int32_t *__restrict__ ix, const T *__restrict__ va,
+                                                          const int64_t *__restrict__ tp, const int32_t *__restrict__ tx,
+                                                          T *__restrict__ tv) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < nnz; k += stride) {
+    int64_t lo = 0, hi = N;                // invariant: tp[lo] <= k < tp[hi]
+    while (hi - lo > 1) {
+      const int64_t mid = (lo + hi) / 2;
+      if (tp[mid] <= k) lo = mid; else hi = mid;
+    }
+    const int64_t j = lo, i = tx[k];
+    int64_t f = ip[i];
+    const int64_t fe = ip[i + 1];
+    for (int64_t e = fe; f < e;) {         // the first entry of row i whose column is not below j
+      const int64_t mid = (f + e) / 2;
+      if ((int64_t)ix[mid] < j) f = mid + 1; else e = mid;
+    }
+    if (f < fe && (int64_t)ix[f] == j) tv[k] = dev_conj(va[f]);
+  }
+}
+
+template <typename T> int set_values_impl(rlh_spd *h, const void *d_values) {
+  Side &a = h->side[0], &b = h->side[1];
+  hipStream_t st = ctx().stream;
+  RLH_HIP(hipMemcpyAsync(a.val, d_values, sizeof(T) * a.nnz, hipMemcpyDeviceToDevice, st));
+  const int64_t most = (int64_t)ctx().num_cu * kValuesBlocksPerCu;
+  hipLaunchKernelGGL(spd_conj_values<T>, dim3(blocks_for(b.nnz, kBlock, most)), dim3(kBlock), 0, st, b.rows, b.nnz, a.indptr.get(),
+                     a.idx.get(), (const T *)a.val.get(), b.indptr.get(), b.idx.get(), (T *)b.val.get());
+  RLH_HIP(hipGetLastError());
+  return 0;
+}
+
 // sums of squares of the rows in float64, entry by entry in the stored order (what numpy.bincount forms on the
 // host: the same bits for real data), the modulus first, as numpy.abs forms it, then squared
 // (the compiler must not contract these into fused multiply-adds: NumPy rounds every product and every sum)
@@ -676,6 +719,17 @@ rlh::SpdArrays rlh::spd_arrays(const rlh_spd *h, int transp) {
   a.rows = s.rows; a.cols = s.cols; a.nnz = s.nnz;
   a.indptr = s.indptr; a.idx = s.idx; a.val = s.val;
   return a;
+}
+
+int rlh::spd_set_values(rlh_spd *h, const void *d_values) {
+  if (!h->side[0].nnz) return 0;
+  switch (h->dtype) {
+    case RLH_S: return set_values_impl<float>(h, d_values);
+    case RLH_D: return set_values_impl<double>(h, d_values);
+    case RLH_C: return set_values_impl<c32>(h, d_values);
+    case RLH_Z: return set_values_impl<c64>(h, d_values);
+  }
+  return 1;
 }
 
 using namespace rlh;

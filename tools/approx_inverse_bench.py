@@ -25,13 +25,22 @@
                same run against the unfiltered build of the same pattern arguments -- and, with --work, each filtered
                build's plan against the unfiltered build's plan of the same work form
 
+  update       --update: for every build above (and, with --work, its plan) the construction against `update_values` with
+               re-valued copies of the same matrix (every off-diagonal entry of the upper triangle times a factor in
+               [0.5, 1), every diagonal entry times one in [1, 2), the lower triangle mirrored: the structure stays, the
+               matrix stays positive definite), taking turns in the same run: device seconds (events: the whole build /
+               the whole update) and host wall seconds (with a plan: its creation / its refill included).  Then a
+               sequence of five re-valued matrices solved with a fresh preconditioner each time against ONE preconditioner
+               built on the first and updated for each: partial_hevp(which=10) seconds with the set-up of every step
+               included, and the iterations of every step.  Stops after these lines.
+
 Every timing is repeated --repeats times and reported as fastest .. slowest; "A beats B" means A's slowest repeat is
 faster than B's fastest, anything else is "no winner".  Nothing here is a threshold.  --setup-only stops after the
 set-up lines (for comparing two builds of the library on one machine).
 
     python tools/approx_inverse_bench.py [--out profiles/r11_approx_inverse_levels.txt] [--levels 1,2,3]
                                          [--adaptive 1:4:4,1:4:8,2:2:4] [--work native,float32,bf16] [--drop 0.01,0.02,0.05]
-                                         [--m 16] [--calls 20] [--repeats 5] [--setup-only]
+                                         [--m 16] [--calls 20] [--repeats 5] [--setup-only] [--update [--sequence-repeats 5]]
 """
 import argparse
 import ctypes
@@ -61,6 +70,8 @@ def main():
     ap.add_argument('--work', default='', help="work forms of the application ('native', 'float32', 'bf16'), comma separated")
     ap.add_argument('--drop', default='', help='post-filtration thresholds in (0, 1), comma separated')
     ap.add_argument('--setup-only', action='store_true', help='set-up timings only')
+    ap.add_argument('--update', action='store_true', help='construction against update_values, and a sequence of matrices')
+    ap.add_argument('--sequence-repeats', type=int, default=None, help='repeats of the sequence of --update (default: --repeats)')
     ap.add_argument('--m', type=int, default=16)
     ap.add_argument('--calls', type=int, default=20)
     ap.add_argument('--repeats', type=int, default=5)
@@ -106,6 +117,77 @@ def main():
         if max(tb) < min(ta):
             return '%s loses to %s (fastest %.4g > slowest %.4g)' % (a, b, min(ta), max(tb))
         return 'no winner between %s and %s (the ranges overlap)' % (a, b)
+
+    def device_tensor(M):
+        out = torch.sparse_csr_tensor(torch.from_numpy(M.indptr.astype(np.int32)), torch.from_numpy(M.indices.astype(np.int32)),
+                                      torch.from_numpy(M.data), size=M.shape).to('cuda')
+        torch.cuda.synchronize()
+        return out
+
+    def revalued(M, seed):
+        rng = np.random.default_rng(seed)
+        u = sp.triu(M, format='coo')
+        factor = np.where(u.row == u.col, rng.uniform(1.0, 2.0, u.nnz), rng.uniform(0.5, 1.0, u.nnz))
+        up = sp.csr_matrix((u.data * factor, (u.row, u.col)), shape=M.shape)
+        out = sp.csr_matrix(up + sp.triu(up, k=1).T)
+        out.sort_indices()
+        assert np.array_equal(out.indptr, M.indptr) and np.array_equal(out.indices, M.indices)
+        return out
+
+    def update_lines(A, t, kwargs, names):
+        """--update: see the module docstring."""
+        seq_repeats = args.sequence_repeats or args.repeats
+        copies = [device_tensor(revalued(A, 100 + k)) for k in range(5)]
+
+        def solve(mat, prec):
+            np.random.seed(1)
+            opt = Options()
+            opt.max_iter = 5000
+            lmd, x, status = partial_hevp(mat, T=prec, which=10, tol=1e-6, verb=-1, opt=opt)
+            return partial_hevp.last['iterations'] if status is not None and status >= 0 else -1
+
+        for kw, name in zip(kwargs, names):
+            for w in [None] + works:
+                label = name if w is None else '%s work=%s' % (name, w)
+                build_dev, build_wall, upd_dev, upd_wall = [], [], [], []
+                for r in range(args.repeats):               # construction and update take turns
+                    _lib.check(L.rlh_sync())
+                    t0 = time.perf_counter()
+                    T = ApproximateInverse(t, work=w, **kw)
+                    _lib.check(L.rlh_sync())
+                    build_wall.append(time.perf_counter() - t0)
+                    build_dev.append(T.setup_seconds)
+                    t0 = time.perf_counter()
+                    T.update_values(copies[r % len(copies)])
+                    _lib.check(L.rlh_sync())
+                    upd_wall.append(time.perf_counter() - t0)
+                    upd_dev.append(T.update_seconds)
+                    del T
+                say('   update  %-42s construction device %s s, host wall %s s; update_values device %s s, host wall %s s'
+                    % (label, span(build_dev, fmt='%.4f'), span(build_wall, fmt='%.4f'), span(upd_dev, fmt='%.4f'),
+                       span(upd_wall, fmt='%.4f')))
+                say('           ' + verdict('update_values', 'the construction', upd_dev, build_dev) + ' [device]')
+                say('           ' + verdict('update_values', 'the construction', upd_wall, build_wall) + ' [host wall]')
+                # ---- the sequence: a fresh preconditioner for every matrix against one that is updated
+                fresh_s, kept_s, fresh_its, kept_its = [], [], None, None
+                for _ in range(seq_repeats):
+                    _lib.check(L.rlh_sync())
+                    t0 = time.perf_counter()
+                    fresh_its = [solve(c, ApproximateInverse(c, work=w, **kw)) for c in copies]
+                    _lib.check(L.rlh_sync())
+                    fresh_s.append(time.perf_counter() - t0)
+                    t0 = time.perf_counter()
+                    T = ApproximateInverse(copies[0], work=w, **kw)
+                    kept_its = [solve(copies[0], T)]
+                    for c in copies[1:]:
+                        T.update_values(c)
+                        kept_its.append(solve(c, T))
+                    _lib.check(L.rlh_sync())
+                    kept_s.append(time.perf_counter() - t0)
+                    del T
+                say('   sequence %-41s five matrices, set-up included: fresh each time %s s, iterations %s; built once and '
+                    'updated %s s, iterations %s' % (label, span(fresh_s, fmt='%.4f'), fresh_its, span(kept_s, fmt='%.4f'), kept_its))
+                say('           ' + verdict('built once and updated', 'fresh each time', kept_s, fresh_s) + ' [five solves with their set-ups]')
 
     say('# ApproximateInverse against IncompleteLU and no preconditioner, float64, m = %d' % m)
     say('# %s, %d calls per timing, %d repeats, fastest .. slowest; written by tools/approx_inverse_bench.py'
@@ -161,6 +243,12 @@ def main():
         if args.setup_only:
             say()
             del T, Ts, t
+            continue
+        if args.update:
+            del T, Ts
+            update_lines(A, t, kwargs, names)
+            say()
+            del t
             continue
         # ---- the same builds with a plan of their own application
         work_names = []                                     # (name with work, name without)
