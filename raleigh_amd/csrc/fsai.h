@@ -1,5 +1,5 @@
 // What fsai.hip (the build, rlh_fsai_*) and fsai_apply.hip (the two-kernel application, rlh_fsapply_*) share: the
-// handle of an approximate inverse and the host side of the exclusive scan of device_build.h.
+// handle of an approximate inverse (both take the exclusive scan from device_build.h).
 #pragma once
 
 #include "device_build.h"
@@ -17,20 +17,3 @@ struct rlh_fsai {
   rlh_spd_t spd = nullptr;          // G and G^H with their partitions
   rlh::DevBuf<char> work;           // the n x m block between the two products
 };
-
-namespace rlh {
-namespace {
-
-// out[0 .. n] = exclusive scan of in[0 .. n) on the library stream; bsum: (n + kScanTile - 1) / kScanTile + 1 entries
-int exclusive_scan(int64_t n, const int64_t *in, int64_t *bsum, int64_t *out) {
-  hipStream_t st = ctx().stream;
-  const int64_t nb = (n + kScanTile - 1) / kScanTile;
-  hipLaunchKernelGGL(scan_tile_sums, dim3((unsigned)nb), dim3(kBlock), 0, st, n, in, bsum);
-  hipLaunchKernelGGL(scan_of_sums, dim3(1), dim3(kBlock), 0, st, nb, bsum);
-  hipLaunchKernelGGL(scan_tiles, dim3((unsigned)nb), dim3(kBlock), 0, st, n, nb, in, bsum, out);
-  RLH_HIP(hipGetLastError());
-  return 0;
-}
-
-}  // namespace
-}  // namespace rlh

@@ -67,43 +67,15 @@ constexpr int kShort = 8;                      // rows of at most kShort kept en
 constexpr int kMaxRow = 64;
 constexpr int kMaxLevels = 8;
 constexpr int kSetupBlocksPerCu = 8;           // grid of a set-up kernel: at most this many workgroups per CU
-enum { kErrDiag = 6, kErrPartner = 7, kErrNotPd = 8 };
+enum { kErrDiag = 6, kErrNotPd = 8 };          // beside the shared codes (device_build.h): a missing diagonal wins over a missing partner
 
-struct FsaiStatus : BuildStatus {
-  long long row, col;                          // row and column of the entry a partner error points at
+struct FsaiStatus : PartnerStatus {
   unsigned long long truncated;                // rows cut to max_row
   int longest;                                 // longest row of G
   unsigned long long limited;                  // adaptive build: rows max_row held back (those cut are among them)
   unsigned long long removed;                  // post-filtration: entries of G dropped
   int kept_longest;                            // post-filtration: longest row of the filtered G
 };
-
-__device__ __forceinline__ bool failed(const BuildStatus *st) { return *(const volatile unsigned long long *)&st->err != kNoError; }
-
-template <typename P, typename I>
-__global__ __launch_bounds__(kBlock) void fsai_check_columns(int64_t n, const P *__restrict__ ip, const I *__restrict__ ix,
-                                                             BuildStatus *st) {
-  if (failed(st)) return;
-  const int lane = threadIdx.x & 63;
-  const int64_t waves = (int64_t)gridDim.x * (kBlock / 64);
-  for (int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); r < n; r += waves) {
-    const int64_t kb = (int64_t)ip[r], ke = (int64_t)ip[r + 1];
-    for (int64_t k = kb + lane; k < ke; k += 64) {
-      const int64_t c = (int64_t)ix[k];
-      if (c < 0 || c >= n) build_error(st, kErrRange, r);
-      else if (k > kb && (int64_t)ix[k - 1] >= c) build_error(st, kErrOrder, r);
-    }
-  }
-}
-
-// the first entry of [lo, hi) whose column is not below c (rows are sorted)
-__device__ __forceinline__ int64_t lower_bound_col(const int32_t *__restrict__ ix, int64_t lo, int64_t hi, int64_t c) {
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) / 2;
-    if ((int64_t)ix[mid] < c) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
 
 // The rows of a build go to bins by their kept entries k: 8, 16, 32 or 64 lanes per row (two bins: 8 or 64).  Two
 // scans carry the three running counts of rows with k <= 8, k <= 16 (high half of the first key) and k <= 32; with two
@@ -166,19 +138,6 @@ __global__ __launch_bounds__(kBlock) void fsai_count(int64_t n, int max_row, int
       bin_keys(k + grow < max_row ? k + grow : max_row, four, &keya[i], &keyb[i]);
     }
   }
-}
-
-// row and column of the entry a partner error points at (one thread)
-__global__ void fsai_resolve_error(int64_t n, const int64_t *__restrict__ ip, const int32_t *__restrict__ ix, FsaiStatus *st) {
-  if (st->err == kNoError || (int)(st->err >> 56) != kErrPartner) return;
-  const int64_t k = (int64_t)(st->err & (((unsigned long long)1 << 56) - 1));
-  int64_t lo = 0, hi = n;                  // the last row with ip[row] <= k (ip[0] = 0 <= k < ip[n])
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) / 2;
-    if (ip[mid] <= k) lo = mid; else hi = mid;
-  }
-  st->row = lo;
-  st->col = (long long)ix[k];
 }
 
 // level 1: the columns of G (a slice of A's row) and the rows of the bins
@@ -672,7 +631,7 @@ struct FsaiScratch {
   DevBuf<FsaiStatus> status;
   DevBuf<int64_t> cnt, ka, kb;            // per row: kept entries and the keys of the bin,
   DevBuf<int64_t> gp, sa, sb, bsum;       // their exclusive scans and the scans' tile sums
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  StreamTimer timer;
   int alloc_rows(int64_t n) {             // everything above but the status record, for n rows
     for (DevBuf<int64_t> *p : {&cnt, &ka, &kb})
       if (int rc = p->alloc(n)) return rc;
@@ -680,32 +639,15 @@ struct FsaiScratch {
       if (int rc = p->alloc(n + 1)) return rc;
     return bsum.alloc((n + kScanTile - 1) / kScanTile + 1);
   }
-  ~FsaiScratch() {
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  }
 };
 
-// What the kernels found wrong, as the message of `name`.  cap: the entries the index and value arrays can hold.
+// What the kernels found wrong, as the message of `name`: this build's own codes here, the shared ones by report_input
+// (device_build.h).  cap: the entries the index and value arrays can hold.
 int report(const char *name, const FsaiStatus &s, int64_t cap) {
-  const int code = (int)(s.err >> 56);
-  const long long pos = (long long)(s.err & (((unsigned long long)1 << 56) - 1));
-  switch (code) {
-    case kErrFirst: set_error("%s: indptr[0] must be 0", name); break;
-    case kErrDecreasing: set_error("%s: indptr decreases at row %lld", name, pos); break;
-    case kErrLast:
-      set_error("%s: indptr's last entry (%lld) is not the number of stored entries (the index and value arrays "
-                "hold at most %lld)", name, s.nnz, (long long)cap);
-      break;
-    case kErrRange: set_error("%s: column index out of range in row %lld", name, pos); break;
-    case kErrOrder: set_error("%s: the columns of row %lld must ascend strictly (no duplicates)", name, pos); break;
-    case kErrDiag: set_error("%s: row %lld does not store its diagonal entry", name, pos); break;
-    case kErrPartner:
-      set_error("%s: the stored structure is not symmetric: entry (%lld, %lld) has no partner (%lld, %lld); the "
-                "device build creates no entries", name, s.row, s.col, s.col, s.row);
-      break;
-    default: set_error("%s: local block of row %lld is not positive definite", name, pos);
-  }
+  if (report_input(name, s, cap)) return 1;
+  const long long pos = (long long)(s.err & kPosMask);
+  if ((int)(s.err >> 56) == kErrDiag) set_error("%s: row %lld does not store its diagonal entry", name, pos);
+  else set_error("%s: local block of row %lld is not positive definite", name, pos);
   return 1;
 }
 
@@ -750,62 +692,21 @@ int pattern_totals(const char *name, int64_t n, const FsaiScratch &w, int64_t ca
   return 0;
 }
 
-// The caller's arrays once they have passed the checks on them as they came: indptr as int64 and columns as int32 (the
-// caller's own arrays where they already are, else converted copies that live as long as this record).  cap: the
-// entries the index and value arrays can hold; nnz: indptr's last entry.
-struct FsaiInput {
-  const int64_t *ip64 = nullptr;
-  const int32_t *ix32 = nullptr;
-  DevBuf<int64_t> indptr;
-  DevBuf<int32_t> cols;
-  int64_t cap = INT64_MAX, nnz = 0;
-};
-
-// The checks of a build and of an update on ip, ix, va (device arrays, n >= 1): indptr, then the columns of every row.
-// Allocates and initialises w.status; *hs is the record as the host saw it last.
+// The checks of a build and of an update on ip, ix, va (device arrays, n >= 1) and the arrays as the kernels read them:
+// the four steps of device_build.h in a row.  *hs is the record as the host saw it last.
 template <typename T, typename P, typename I>
-int checked_input(const char *name, int64_t n, const P *ip, const I *ix, const T *va, FsaiScratch &w, FsaiStatus *hs, FsaiInput *in) {
-  hipStream_t st = ctx().stream;
-  const dim3 blk(kBlock);
-  int64_t cap = INT64_MAX;
-  const int64_t room_p = bytes_from(ip), room_i = bytes_from(ix), room_v = bytes_from(va);
-  RLH_REQUIRE(room_p < 0 || room_p >= (int64_t)sizeof(P) * (n + 1), "%s: the indptr array holds fewer than n + 1 entries", name);
-  if (!ix || !va) cap = 0;
-  if (room_i >= 0) cap = std::min<int64_t>(cap, room_i / (int64_t)sizeof(I));
-  if (room_v >= 0) cap = std::min<int64_t>(cap, room_v / (int64_t)sizeof(T));
-  in->cap = cap;
-  if (int rc = w.status.alloc(1)) return rc;
-  *hs = FsaiStatus{};
-  hs->err = kNoError;
-  RLH_HIP(hipMemcpyAsync(w.status, hs, sizeof *hs, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(spd_check_indptr<P>, dim3(blocks_for(n + 1, kBlock, 4096)), blk, 0, st, n, ip, cap, w.status);
-  hipLaunchKernelGGL((fsai_check_columns<P, I>), dim3(blocks_for(n, kBlock / 64, 8192)), blk, 0, st, n, ip, ix, w.status);
-  RLH_HIP(hipGetLastError());
-  RLH_HIP(hipMemcpyAsync(hs, w.status, sizeof *hs, hipMemcpyDeviceToHost, st));
-  RLH_HIP(hipStreamSynchronize(st));
-  if (hs->err != kNoError) return report(name, *hs, cap);
-  const int64_t nnz = in->nnz = hs->nnz;
-  if constexpr (std::is_same<P, int64_t>::value) {
-    in->ip64 = ip;
-  } else {
-    if (int rc = in->indptr.alloc(n + 1)) return rc;
-    hipLaunchKernelGGL((spd_convert_index<P, int64_t>), dim3(blocks_for(n + 1, kBlock, 4096)), blk, 0, st, n + 1, ip, in->indptr.get());
-    in->ip64 = in->indptr;
-  }
-  if constexpr (std::is_same<I, int32_t>::value) {
-    in->ix32 = ix;
-  } else {
-    if (int rc = in->cols.alloc(std::max<int64_t>(nnz, 1))) return rc;
-    if (nnz) hipLaunchKernelGGL((spd_convert_index<I, int32_t>), dim3(blocks_for(nnz, kBlock, 8192)), blk, 0, st, nnz, ix, in->cols.get());
-    in->ix32 = in->cols;
-  }
-  return 0;
+int checked_input(const char *name, int64_t n, const P *ip, const I *ix, const T *va, FsaiScratch &w, FsaiStatus *hs, CsrInput *in) {
+  if (int rc = input_cap(name, "n", n, ip, ix, va, &in->cap)) return rc;
+  if (int rc = launch_input_checks<false>(n, n, ip, ix, in->cap, w.status, hs)) return rc;
+  if (int rc = fetch_input_status(name, w.status.get(), hs, in->cap)) return rc;
+  in->nnz = hs->nnz;
+  return normalise_indices(n, ip, ix, in);
 }
 
 // Every row solved on its pattern, bin by bin (the pattern of gp and `columns`, the bins as they stand, the values to
 // `values`); the host waits and reports what the kernels found.
 template <typename T>
-int solve_rows(const char *name, int64_t n, const Bins &bins, const FsaiInput &in, const T *va, const int64_t *gp, const int32_t *columns,
+int solve_rows(const char *name, int64_t n, const Bins &bins, const CsrInput &in, const T *va, const int64_t *gp, const int32_t *columns,
                T *values, const FsaiScratch &w, FsaiStatus *hs) {
   hipStream_t st = ctx().stream;
   for_each_bin(bins, n, [&](auto lanes, int64_t count, const int32_t *list) {
@@ -827,11 +728,9 @@ int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T 
   hipStream_t st = ctx().stream;
   const dim3 blk(kBlock);
   FsaiScratch w;
-  RLH_HIP(hipEventCreate(&w.e0));
-  RLH_HIP(hipEventCreate(&w.e1));
-  RLH_HIP(hipEventRecord(w.e0, st));
+  if (int rc = w.timer.start()) return rc;
   FsaiStatus hs{};
-  FsaiInput in;
+  CsrInput in;
   if (int rc = checked_input(name, n, ip, ix, va, w, &hs, &in)) return rc;
   const int64_t cap = in.cap;
   const int64_t *ip64 = in.ip64;
@@ -843,7 +742,7 @@ int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T 
   if (int rc = start.alloc(n)) return rc;
   hipLaunchKernelGGL(fsai_count, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, max_row, levels == 1 ? 1 : 0, four, grow, ip64,
                      ix32, w.cnt, w.ka, w.kb, start, w.status);
-  hipLaunchKernelGGL(fsai_resolve_error, dim3(1), dim3(1), 0, st, n, ip64, ix32, w.status);
+  hipLaunchKernelGGL((resolve_partner<int64_t, int32_t>), dim3(1), dim3(1), 0, st, n, ip64, ix32, w.status);
   if (levels > 1)
     hipLaunchKernelGGL(fsai_pattern_count, dim3(blocks_for(n, kBlock / 64, most)), blk, 0, st, n, max_row, levels, four, grow, ip64,
                        ix32, w.cnt, w.ka, w.kb, w.status);
@@ -938,11 +837,8 @@ int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T 
     rc = rlh_spd_create_device(&h->spd, h->dtype, n, n, 64, w.gp, gi64, gv);
   }
   if (rc) return rc;
-  RLH_HIP(hipEventRecord(w.e1, st));
-  RLH_HIP(hipEventSynchronize(w.e1));        // the caller's arrays and the scratch are not referenced after the return
-  float ms = 0.f;
-  RLH_HIP(hipEventElapsedTime(&ms, w.e0, w.e1));
-  h->setup_seconds = 1e-3 * ms;
+  if (int rc2 = w.timer.stop()) return rc2;   // the caller's arrays and the scratch are not referenced after the return
+  h->setup_seconds = w.timer.seconds();
   return 0;
 }
 
@@ -968,11 +864,9 @@ int fsai_update(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T
   hipStream_t st = ctx().stream;
   const dim3 blk(kBlock);
   FsaiScratch w;
-  RLH_HIP(hipEventCreate(&w.e0));
-  RLH_HIP(hipEventCreate(&w.e1));
-  RLH_HIP(hipEventRecord(w.e0, st));
+  if (int rc = w.timer.start()) return rc;
   FsaiStatus hs{};
-  FsaiInput in;
+  CsrInput in;
   if (int rc = checked_input(name, n, ip, ix, va, w, &hs, &in)) return rc;
   const SpdArrays g = spd_arrays(h->spd, 0);
   const unsigned grid = blocks_for(n, kBlock, (int64_t)ctx().num_cu * kSetupBlocksPerCu);
@@ -991,11 +885,8 @@ int fsai_update(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T
   if (int rc = solve_rows<T>(name, n, bins, in, va, g.indptr, g.idx, gv, w, &hs)) return rc;
   // ---- every row succeeded: the new values go to the operator
   if (int rc = spd_set_values(h->spd, gv)) return rc;
-  RLH_HIP(hipEventRecord(w.e1, st));
-  RLH_HIP(hipEventSynchronize(w.e1));        // the caller's arrays and the scratch are not referenced after the return
-  float ms = 0.f;
-  RLH_HIP(hipEventElapsedTime(&ms, w.e0, w.e1));
-  h->update_seconds = 1e-3 * ms;
+  if (int rc = w.timer.stop()) return rc;    // the caller's arrays and the scratch are not referenced after the return
+  h->update_seconds = w.timer.seconds();
   ++h->updates;
   return 0;
 }
@@ -1063,24 +954,31 @@ int create_device(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, int in
   });
 }
 
-int create_host(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
-                const void *values, const FsaiPlan &plan) {
-  if (int rc = require_ready()) return rc;
-  if (int rc = check_create_args(name, ph, dtype, n, indptr, plan)) return rc;
-  // what decides how much is uploaded is checked here; everything else by the kernels, as for device arrays
+// Host arrays (indptr not null): what decides how much is uploaded is checked here, everything else by the kernels, as
+// for device arrays; then the three arrays go to the device (n == 0: nothing to upload)
+struct UploadedCsr {
+  DevBuf<int64_t> ip;
+  DevBuf<int32_t> ix;
+  DevBuf<void> va;
+};
+int upload_csr(const char *name, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices, const void *values, UploadedCsr *d) {
   RLH_REQUIRE(indptr[0] == 0, "%s: indptr[0] must be 0", name);
   for (int64_t r = 0; r < n; ++r) RLH_REQUIRE(indptr[r + 1] >= indptr[r], "%s: indptr decreases at row %lld", name, (long long)r);
   const int64_t nnz = indptr[n], es = dtype_size(dtype);
   RLH_REQUIRE(nnz == 0 || (indices && values), "%s: null indices or values", name);
-  return make_handle(ph, dtype, n, plan, [&](rlh_fsai *h) {
-    DevBuf<int64_t> d_ip;
-    DevBuf<int32_t> d_ix;
-    DevBuf<void> d_va;
-    if (int rc = d_ip.upload(indptr, (size_t)(n + 1) * 8)) return rc;
-    if (int rc = d_ix.upload(indices, (size_t)nnz * 4, 4)) return rc;
-    if (int rc = d_va.upload(values, (size_t)(nnz * es), 16)) return rc;
-    return fsai_build_any<int64_t, int32_t>(h, name, d_ip, d_ix, d_va, plan);
-  });
+  if (n == 0) return 0;
+  if (int rc = d->ip.upload(indptr, (size_t)(n + 1) * 8)) return rc;
+  if (int rc = d->ix.upload(indices, (size_t)nnz * 4, 4)) return rc;
+  return d->va.upload(values, (size_t)(nnz * es), 16);
+}
+
+int create_host(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
+                const void *values, const FsaiPlan &plan) {
+  if (int rc = require_ready()) return rc;
+  if (int rc = check_create_args(name, ph, dtype, n, indptr, plan)) return rc;
+  UploadedCsr d;
+  if (int rc = upload_csr(name, dtype, n, indptr, indices, values, &d)) return rc;
+  return make_handle(ph, dtype, n, plan, [&](rlh_fsai *h) { return fsai_build_any<int64_t, int32_t>(h, name, d.ip, d.ix, d.va, plan); });
 }
 
 }  // namespace
@@ -1165,20 +1063,9 @@ extern "C" int rlh_fsvalues_update(rlh_fsai_t h, const int64_t *indptr, const in
   if (int rc = require_ready()) return rc;
   RLH_REQUIRE(h != nullptr, "%s: null handle", name);
   RLH_REQUIRE(indptr, "%s: null indptr", name);
-  // what decides how much is uploaded is checked here; everything else by the kernels, as for device arrays
-  const int64_t n = h->n;
-  RLH_REQUIRE(indptr[0] == 0, "%s: indptr[0] must be 0", name);
-  for (int64_t r = 0; r < n; ++r) RLH_REQUIRE(indptr[r + 1] >= indptr[r], "%s: indptr decreases at row %lld", name, (long long)r);
-  const int64_t nnz = indptr[n], es = dtype_size(h->dtype);
-  RLH_REQUIRE(nnz == 0 || (indices && values), "%s: null indices or values", name);
-  if (n == 0) return fsai_update_any<int64_t, int32_t>(h, name, indptr, indices, values);
-  DevBuf<int64_t> d_ip;
-  DevBuf<int32_t> d_ix;
-  DevBuf<void> d_va;
-  if (int rc = d_ip.upload(indptr, (size_t)(n + 1) * 8)) return rc;
-  if (int rc = d_ix.upload(indices, (size_t)nnz * 4, 4)) return rc;
-  if (int rc = d_va.upload(values, (size_t)(nnz * es), 16)) return rc;
-  return fsai_update_any<int64_t, int32_t>(h, name, d_ip, d_ix, d_va);
+  UploadedCsr d;
+  if (int rc = upload_csr(name, h->dtype, h->n, indptr, indices, values, &d)) return rc;
+  return fsai_update_any<int64_t, int32_t>(h, name, d.ip, d.ix, d.va);     // (n == 0: a valid update that reads nothing)
 }
 
 extern "C" int rlh_fsvalues_info(rlh_fsai_t h, int64_t *updates, double *seconds) {

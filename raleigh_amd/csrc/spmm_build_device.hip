@@ -46,43 +46,10 @@ static_assert(kGroupCap == kWideRows, "one thread per group of a block");
 
 struct BlockRec { int32_t width, ng; };
 
-// the status record of this build: the shared one (device_build.h) and what only this build reports
-struct CsrStatus : BuildStatus {
-  long long row, col;             // row and column of the entry a partner error points at
+// the status record of this build: the shared one with the partner's place (device_build.h) and what only this build reports
+struct CsrStatus : PartnerStatus {
   int differ;                     // some pair of rows (2 i, 2 i + 1) differs in its columns
 };
-constexpr int kErrPartner = 6;
-
-__device__ __forceinline__ bool failed(const BuildStatus *st) { return *(const volatile unsigned long long *)&st->err != kNoError; }
-
-// columns inside [0, N) and strictly ascending within each row: one wave per row
-template <typename I>
-__global__ __launch_bounds__(kBlock) void csr_check_columns(int64_t M, int64_t N, const I *__restrict__ ip,
-                                                            const I *__restrict__ ix, BuildStatus *st) {
-  if (failed(st)) return;
-  const int lane = threadIdx.x & 63;
-  const int64_t waves = (int64_t)gridDim.x * (kBlock / 64);
-  for (int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); r < M; r += waves) {
-    const int64_t kb = (int64_t)ip[r], ke = (int64_t)ip[r + 1];
-    for (int64_t k = kb + lane; k < ke; k += 64) {
-      const int64_t c = (int64_t)ix[k];
-      if (c < 0 || c >= N) build_error(st, kErrRange, r);
-      else if (k > kb && (int64_t)ix[k - 1] >= c) build_error(st, kErrOrder, r);
-    }
-  }
-}
-
-// the entry of row j with column i (rows are sorted): its index, or -1
-template <typename P, typename I>
-__device__ __forceinline__ int64_t find_entry(const P *__restrict__ ip, const I *__restrict__ ix, int64_t j, int64_t i) {
-  int64_t lo = (int64_t)ip[j], hi = (int64_t)ip[j + 1];
-  const int64_t end = hi;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) / 2;
-    if ((int64_t)ix[mid] < i) lo = mid + 1; else hi = mid;
-  }
-  return (lo < end && (int64_t)ix[lo] == i) ? lo : -1;
-}
 
 // mirror_upper: every entry off the diagonal has its partner on the other side
 template <typename I>
@@ -98,20 +65,6 @@ __global__ __launch_bounds__(kBlock) void csr_check_partners(int64_t M, const I 
       if (j != r && find_entry(ip, ix, j, r) < 0) build_error(st, kErrPartner, k);
     }
   }
-}
-
-// row and column of the entry a partner error points at (one thread)
-template <typename I>
-__global__ void csr_resolve_error(int64_t M, const I *__restrict__ ip, const I *__restrict__ ix, CsrStatus *st) {
-  if (st->err == kNoError || (int)(st->err >> 56) != kErrPartner) return;
-  const int64_t k = (int64_t)(st->err & (((unsigned long long)1 << 56) - 1));
-  int64_t lo = 0, hi = M;                  // the last row with ip[row] <= k (ip[0] = 0 <= k < ip[M])
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) / 2;
-    if ((int64_t)ip[mid] <= k) lo = mid; else hi = mid;
-  }
-  st->row = lo;
-  st->col = (long long)ix[k];
 }
 
 // the pairing rule of wide_build: rows 2 q and 2 q + 1 hold the same columns, for every complete pair
@@ -287,8 +240,9 @@ __global__ __launch_bounds__(kWideRows) void wide_fill(int64_t n, bool mirror, c
 
 struct CsrScratch {                 // released when the build returns, however it returns
   DevBuf<CsrStatus> status;
-  DevBuf<int64_t> indptr, widths, bsum;
-  DevBuf<int32_t> cols, groups;
+  CsrInput in;
+  DevBuf<int64_t> widths, bsum;
+  DevBuf<int32_t> groups;
   DevBuf<BlockRec> rec;
 };
 
@@ -314,10 +268,7 @@ int sell_build_device(rlh_csr *h, CsrScratch &w, bool mirror, const int64_t *ip,
     if (int rc = w.widths.alloc((size_t)ns)) return rc;
     if (int rc = w.bsum.alloc((size_t)(nb + 1))) return rc;
     hipLaunchKernelGGL(sell_widths, dim3(blocks_for(ns, kBlock, INT32_MAX)), dim3(kBlock), 0, st, n, ns, ip, w.widths);
-    hipLaunchKernelGGL(scan_tile_sums, dim3((unsigned)nb), dim3(kBlock), 0, st, ns, w.widths, w.bsum);
-    hipLaunchKernelGGL(scan_of_sums, dim3(1), dim3(kBlock), 0, st, nb, w.bsum);
-    hipLaunchKernelGGL(scan_tiles, dim3((unsigned)nb), dim3(kBlock), 0, st, ns, nb, w.widths, w.bsum, h->slice_ptr);
-    RLH_HIP(hipGetLastError());
+    if (int rc = exclusive_scan(ns, w.widths, w.bsum, h->slice_ptr)) return rc;
     RLH_HIP(hipMemcpyAsync(&padded, h->slice_ptr + ns, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     RLH_HIP(hipStreamSynchronize(st));
   } else {
@@ -429,71 +380,32 @@ int wide_build_device(rlh_csr *h, CsrScratch &w, Lap &lap, bool mirror, bool for
 
 template <typename T, typename I>
 int csr_create_device_impl(rlh_csr *h, const I *ip, const I *ix, const T *va, bool mirror, bool want_sell, bool force_wide) {
-  const int64_t es = sizeof(T), M = h->n_rows, N = h->n_cols;
+  constexpr const char *name = "rlh_csr_create_device";
+  const int64_t M = h->n_rows, N = h->n_cols;
   hipStream_t st = ctx().stream;
   const dim3 blk(kBlock);
   CsrScratch w;
   Lap lap;
-  // ---- the checks: one status record comes back
-  int64_t cap = INT64_MAX;
-  const int64_t room_p = bytes_from(ip), room_i = bytes_from(ix), room_v = bytes_from(va);
-  RLH_REQUIRE(room_p < 0 || room_p >= (int64_t)sizeof(I) * (M + 1), "rlh_csr_create_device: the indptr array holds fewer than n_rows + 1 entries");
-  if (!ix || !va) cap = 0;
-  if (room_i >= 0) cap = std::min<int64_t>(cap, room_i / (int64_t)sizeof(I));
-  if (room_v >= 0) cap = std::min<int64_t>(cap, room_v / es);
+  // ---- the checks: the shared ones (device_build.h), then this build's own on the same record; one record comes back
+  CsrInput &in = w.in;
+  CsrStatus hs;
+  if (int rc = input_cap(name, "n_rows", M, ip, ix, va, &in.cap)) return rc;
   const bool real = std::is_same<T, float>::value || std::is_same<T, double>::value;
   const bool pair_test = real && env_int("RLH_WIDE_PAIR", 1) != 0 && !want_sell;
-  if (int rc = w.status.alloc(1)) return rc;
-  CsrStatus hs{{kNoError, 0}, 0, 0, 0};
-  RLH_HIP(hipMemcpyAsync(w.status, &hs, sizeof hs, hipMemcpyHostToDevice, st));
-  const unsigned row_waves = blocks_for(M, kBlock / 64, 8192);
-  hipLaunchKernelGGL(spd_check_indptr<I>, dim3(blocks_for(M + 1, kBlock, 4096)), blk, 0, st, M, ip, cap, w.status);
-  hipLaunchKernelGGL(csr_check_columns<I>, dim3(row_waves), blk, 0, st, M, N, ip, ix, w.status);
+  if (int rc = launch_input_checks<false>(M, N, ip, ix, in.cap, w.status, &hs)) return rc;
   if (mirror) {
-    hipLaunchKernelGGL(csr_check_partners<I>, dim3(row_waves), blk, 0, st, M, ip, ix, w.status);
-    hipLaunchKernelGGL(csr_resolve_error<I>, dim3(1), dim3(1), 0, st, M, ip, ix, w.status);
+    hipLaunchKernelGGL(csr_check_partners<I>, dim3(blocks_for(M, kBlock / 64, 8192)), blk, 0, st, M, ip, ix, w.status);
+    hipLaunchKernelGGL((resolve_partner<I, I>), dim3(1), dim3(1), 0, st, M, ip, ix, w.status);
   }
   if (pair_test) hipLaunchKernelGGL(csr_pair_test<I>, dim3(blocks_for(M / 2, kBlock, 8192)), blk, 0, st, M / 2, ip, ix, w.status);
   RLH_HIP(hipGetLastError());
-  RLH_HIP(hipMemcpyAsync(&hs, w.status, sizeof hs, hipMemcpyDeviceToHost, st));
-  RLH_HIP(hipStreamSynchronize(st));
-  if (hs.err != kNoError) {
-    const int code = (int)(hs.err >> 56);
-    const long long pos = (long long)(hs.err & (((unsigned long long)1 << 56) - 1));
-    switch (code) {
-      case kErrFirst: set_error("rlh_csr_create_device: indptr[0] must be 0"); break;
-      case kErrDecreasing: set_error("rlh_csr_create_device: indptr decreases at row %lld", pos); break;
-      case kErrLast:
-        set_error("rlh_csr_create_device: indptr's last entry (%lld) is not the number of stored entries (the index "
-                  "and value arrays hold at most %lld)", hs.nnz, (long long)cap);
-        break;
-      case kErrRange: set_error("rlh_csr_create_device: column index out of range in row %lld", pos); break;
-      case kErrOrder:
-        set_error("rlh_csr_create_device: the columns of row %lld must ascend strictly (no duplicates)", pos);
-        break;
-      default:
-        set_error("rlh_csr_create_device: the stored structure is not symmetric: entry (%lld, %lld) has no partner "
-                  "(%lld, %lld); the device build creates no entries", hs.row, hs.col, hs.col, hs.row);
-    }
-    return 1;
-  }
-  h->nnz = hs.nnz;
+  if (int rc = fetch_input_status(name, w.status.get(), &hs, in.cap)) return rc;
+  h->nnz = in.nnz = hs.nnz;
   if (int rc = lap("argument checks")) return rc;
   // ---- indptr as int64 and columns as int32 (the caller's own arrays where they already are)
-  const int64_t *ip64;
-  const int32_t *ix32;
-  if constexpr (std::is_same<I, int64_t>::value) {
-    ip64 = ip;
-    if (int rc = w.cols.alloc((size_t)std::max<int64_t>(h->nnz, 1))) return rc;
-    if (h->nnz) hipLaunchKernelGGL((spd_convert_index<I, int32_t>), dim3(blocks_for(h->nnz, kBlock, 8192)), blk, 0, st, h->nnz, ix, w.cols);
-    ix32 = w.cols;
-  } else {
-    if (int rc = w.indptr.alloc((size_t)(M + 1))) return rc;
-    hipLaunchKernelGGL((spd_convert_index<I, int64_t>), dim3(blocks_for(M + 1, kBlock, 4096)), blk, 0, st, M + 1, ip, w.indptr);
-    ip64 = w.indptr;
-    ix32 = ix;
-  }
-  RLH_HIP(hipGetLastError());
+  if (int rc = normalise_indices(M, ip, ix, &in)) return rc;
+  const int64_t *ip64 = in.ip64;
+  const int32_t *ix32 = in.ix32;
   if (!want_sell) {
     const bool paired = pair_test && !hs.differ && h->nnz >= 16 * M;
     if (int rc = wide_build_device<T>(h, w, lap, mirror, force_wide, paired, ip64, ix32, va)) return rc;

@@ -322,24 +322,6 @@ int create_impl(rlh_spd *h, int64_t M, int64_t N, const int64_t *ip, const int32
 // chunk walks its rows in order with the lanes on the entries of ONE row -- a canonical row has distinct
 // columns, so no two lanes take the same cursor and every entry's place is fixed by the matrix alone.
 
-// columns inside [0, N) and strictly ascending within each row: one wave per row; nothing is read when indptr
-// has failed its check
-template <typename I>
-__global__ __launch_bounds__(kBlock) void spd_check_columns(int64_t M, int64_t N, const I *__restrict__ ip,
-                                                            const I *__restrict__ ix, BuildStatus *st) {
-  if (*(volatile unsigned long long *)&st->err != kNoError) return;
-  const int lane = threadIdx.x & 63;
-  const int64_t waves = (int64_t)gridDim.x * (kBlock / 64);
-  for (int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); r < M; r += waves) {
-    const int64_t kb = (int64_t)ip[r], ke = (int64_t)ip[r + 1];
-    for (int64_t k = kb + lane; k < ke; k += 64) {
-      const int64_t c = (int64_t)ix[k];
-      if (c < 0 || c >= N) build_error(st, kErrRange, k);
-      else if (k > kb && (int64_t)ix[k - 1] >= c) build_error(st, kErrOrder, k);
-    }
-  }
-}
-
 // row_at[g], g <= G: partition() on the device, one binary search per subgroup
 __global__ __launch_bounds__(kBlock) void spd_partition(int64_t rows, int64_t nnz, int64_t G, const int64_t *__restrict__ indptr,
                                                         int32_t *__restrict__ row_at) {
@@ -433,14 +415,6 @@ int alloc_side(Side &s, int64_t rows, int64_t cols, int64_t nnz, int64_t es) {
   return s.row_at.alloc(s.G + 1);
 }
 
-struct BuildScratch {               // the timing events: destroyed when the build returns, however it returns
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  ~BuildScratch() {
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  }
-};
-
 // the number of row chunks: about kChunkNnz entries each, the C x N table of places within the cap
 // (RLH_SPD_TABLE_BYTES, 512 MB as transpose_host caps its own), at least one
 constexpr int64_t kChunkNnz = 8192;
@@ -457,40 +431,16 @@ int create_device_impl(rlh_spd *h, int64_t M, int64_t N, const I *ip, const I *i
   const int64_t es = sizeof(T);
   hipStream_t st = ctx().stream;
   const dim3 blk(kBlock);
-  BuildScratch w;
+  StreamTimer timer;
   DevBuf<BuildStatus> status;
   DevBuf<int64_t> rstart, cnt, tot, bsum;
-  // ---- the checks: one status record comes back
-  int64_t cap = INT64_MAX;
-  const int64_t room_p = bytes_from(ip), room_i = bytes_from(ix), room_v = bytes_from(va);
-  RLH_REQUIRE(room_p < 0 || room_p >= (int64_t)sizeof(I) * (M + 1), "rlh_spd_create_device: the indptr array holds fewer than n_rows + 1 entries");
-  if (!ix || !va) cap = 0;
-  if (room_i >= 0) cap = std::min<int64_t>(cap, room_i / (int64_t)sizeof(I));
-  if (room_v >= 0) cap = std::min<int64_t>(cap, room_v / es);
-  if (int rc = status.alloc(1)) return rc;
-  BuildStatus hs{kNoError, 0};
-  RLH_HIP(hipMemcpyAsync(status, &hs, sizeof hs, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(spd_check_indptr<I>, dim3(blocks_for(M + 1, kBlock, 4096)), blk, 0, st, M, ip, cap, status);
-  hipLaunchKernelGGL(spd_check_columns<I>, dim3(blocks_for(M, kBlock / 64, 8192)), blk, 0, st, M, N, ip, ix, status);
-  RLH_HIP(hipGetLastError());
-  RLH_HIP(hipMemcpyAsync(&hs, status, sizeof hs, hipMemcpyDeviceToHost, st));
-  RLH_HIP(hipStreamSynchronize(st));
-  if (hs.err != kNoError) {
-    const int code = (int)(hs.err >> 56);
-    const long long pos = (long long)(hs.err & (((unsigned long long)1 << 56) - 1));
-    switch (code) {
-      case kErrFirst: set_error("rlh_spd_create_device: indptr[0] must be 0"); break;
-      case kErrDecreasing: set_error("rlh_spd_create_device: indptr decreases at row %lld", pos); break;
-      case kErrLast:
-        set_error("rlh_spd_create_device: indptr's last entry (%lld) is not the number of stored entries (the index "
-                  "and value arrays hold at most %lld)", hs.nnz, (long long)cap);
-        break;
-      case kErrRange: set_error("rlh_spd_create_device: column index out of range at entry %lld", pos); break;
-      default:
-        set_error("rlh_spd_create_device: the columns of a row must ascend strictly (no duplicates): entry %lld", pos);
-    }
-    return 1;
-  }
+  // ---- the checks (device_build.h; what they find is placed by its entry): one status record comes back
+  constexpr const char *name = "rlh_spd_create_device";
+  int64_t cap;
+  BuildStatus hs;
+  if (int rc = input_cap(name, "n_rows", M, ip, ix, va, &cap)) return rc;
+  if (int rc = launch_input_checks<true>(M, N, ip, ix, cap, status, &hs)) return rc;
+  if (int rc = fetch_input_status(name, status.get(), &hs, cap, true)) return rc;
   const int64_t nnz = hs.nnz;
   // ---- A: indptr as int64, columns as int32, the values
   Side &a = h->side[0], &b = h->side[1];
@@ -510,30 +460,22 @@ int create_device_impl(rlh_spd *h, int64_t M, int64_t N, const I *ip, const I *i
   if (int rc = cnt.alloc(std::max<int64_t>(C * N, 1))) return rc;
   if (int rc = tot.alloc(std::max<int64_t>(N, 1))) return rc;
   if (int rc = bsum.alloc(nb + 1)) return rc;
-  RLH_HIP(hipEventCreate(&w.e0));
-  RLH_HIP(hipEventCreate(&w.e1));
-  RLH_HIP(hipEventRecord(w.e0, st));
+  if (int rc = timer.start()) return rc;
   RLH_HIP(hipMemsetAsync(cnt, 0, std::max<int64_t>(8 * C * N, 8), st));
   hipLaunchKernelGGL(spd_chunk_rows, dim3(blocks_for(C + 1, kBlock, INT32_MAX)), blk, 0, st, M, nnz, C, a.indptr, rstart);
   const int S = (int)std::max<int64_t>(1, std::min<int64_t>(64, 2048 / C));
   if (nnz && N)
     hipLaunchKernelGGL(spd_count, dim3((unsigned)(C * S)), blk, 0, st, N, S, a.indptr, rstart, a.idx, (unsigned long long *)cnt);
   if (N) hipLaunchKernelGGL(spd_column_totals, dim3(blocks_for(N, kBlock, INT32_MAX)), blk, 0, st, N, C, cnt, tot);
-  if (nb) hipLaunchKernelGGL(scan_tile_sums, dim3((unsigned)nb), blk, 0, st, N, tot, bsum);
-  hipLaunchKernelGGL(scan_of_sums, dim3(1), blk, 0, st, nb, bsum);
-  if (nb) hipLaunchKernelGGL(scan_tiles, dim3((unsigned)nb), blk, 0, st, N, nb, tot, bsum, b.indptr);
-  else RLH_HIP(hipMemsetAsync(b.indptr, 0, 8, st));
+  if (int rc = exclusive_scan(N, tot, bsum, b.indptr)) return rc;
   if (N) hipLaunchKernelGGL(spd_chunk_places, dim3(blocks_for(N, kBlock, INT32_MAX)), blk, 0, st, N, C, b.indptr, cnt);
   if (nnz && N)
     hipLaunchKernelGGL(spd_scatter<T>, dim3((unsigned)C), dim3(64), 0, st, a.indptr, rstart, a.idx, (const T *)a.val, N, cnt,
                        b.idx, (T *)b.val);
   hipLaunchKernelGGL(spd_partition, dim3(blocks_for(b.G + 1, kBlock, INT32_MAX)), blk, 0, st, N, nnz, b.G, b.indptr, b.row_at);
   RLH_HIP(hipGetLastError());
-  RLH_HIP(hipEventRecord(w.e1, st));
-  RLH_HIP(hipEventSynchronize(w.e1));
-  float ms = 0.f;
-  RLH_HIP(hipEventElapsedTime(&ms, w.e0, w.e1));
-  h->transpose_seconds = 1e-3 * ms;
+  if (int rc = timer.stop()) return rc;
+  h->transpose_seconds = timer.seconds();
   return 0;
 }
 

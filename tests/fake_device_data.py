@@ -10,6 +10,7 @@ import scipy.sparse as sp
 
 from fake_lib import _DT, _addr, _flat
 import fake_byte_data
+import fake_csr_input
 import fake_sparse_data
 
 
@@ -26,19 +27,13 @@ class FakeDeviceDataLib(fake_byte_data.FakeByteDataLib, fake_sparse_data.FakeSpa
             return self._fail('rlh_spd_create_device: index_bits must be 32 or 64')
         it = np.int32 if index_bits == 32 else np.int64
         ip = _flat(indptr, it, n_rows + 1).astype(np.int64)
-        if ip[0] != 0:
-            return self._fail('rlh_spd_create_device: indptr[0] must be 0')
-        if np.any(np.diff(ip) < 0):
-            return self._fail('rlh_spd_create_device: indptr decreases')
+        if msg := fake_csr_input.indptr_message('rlh_spd_create_device: ', ip, terse=True):
+            return self._fail(msg)
         nnz = int(ip[-1])
         ix = _flat(indices, it, nnz).astype(np.int64)
         va = _flat(values, _DT[code], nnz).copy()
-        if nnz and (ix.min() < 0 or ix.max() >= n_cols):
-            return self._fail('rlh_spd_create_device: column index out of range')
-        inner = np.ones(nnz, dtype=bool)
-        inner[ip[:-1][np.diff(ip) > 0]] = False             # the first entry of every row
-        if nnz > 1 and np.any((np.diff(ix) <= 0) & inner[1:]):
-            return self._fail('rlh_spd_create_device: the columns of a row must ascend strictly')
+        if msg := fake_csr_input.columns_message('rlh_spd_create_device: ', ip, ix, n_cols, terse=True):
+            return self._fail(msg)
         h = self._next_handle
         self._next_handle += 1
         a = sp.csr_matrix((va, ix.astype(np.int32), ip), shape=(n_rows, n_cols))

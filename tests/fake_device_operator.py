@@ -6,6 +6,7 @@ import numpy as np
 import scipy.sparse as sp
 
 from fake_lib import _DT, _Csr, _flat
+import fake_csr_input
 import fake_device_data
 from fake_device_data import as_device  # noqa: F401
 
@@ -30,23 +31,14 @@ class FakeDeviceOperatorLib(fake_device_data.FakeDeviceDataLib):
             return self._fail(name + 'mirror_upper needs a square matrix, got %d x %d' % (n_rows, n_cols))
         it = np.int32 if index_bits == 32 else np.int64
         ip = _flat(indptr, it, n_rows + 1).astype(np.int64)
-        if ip[0] != 0:
-            return self._fail(name + 'indptr[0] must be 0')
-        d = np.diff(ip)
-        if np.any(d < 0):
-            return self._fail(name + 'indptr decreases at row %d' % int(np.argmax(d < 0)))
+        if msg := fake_csr_input.indptr_message(name, ip):
+            return self._fail(msg)
         nnz = int(ip[-1])
         ix = _flat(indices, it, nnz).astype(np.int64)
         va = _flat(values, _DT[code], nnz).copy()
-        rows = np.repeat(np.arange(n_rows), d)
-        bad = (ix < 0) | (ix >= n_cols)
-        if bad.any():
-            return self._fail(name + 'column index out of range in row %d' % int(rows[np.argmax(bad)]))
-        if nnz > 1:
-            bad = (np.diff(ix) <= 0) & (rows[1:] == rows[:-1])
-            if bad.any():
-                return self._fail(name + 'the columns of row %d must ascend strictly (no duplicates)'
-                                  % int(rows[1:][np.argmax(bad)]))
+        if msg := fake_csr_input.columns_message(name, ip, ix, n_cols):
+            return self._fail(msg)
+        rows = np.repeat(np.arange(n_rows), np.diff(ip))
         a = sp.csr_matrix((va, ix.astype(np.int32), ip), shape=(n_rows, n_cols))
         if mirror_upper:
             stored = set(zip(rows.tolist(), ix.tolist()))

@@ -17,6 +17,7 @@ import numpy as np
 import scipy.sparse as sp
 
 from fake_lib import _DT, _addr, _block, _flat
+import fake_csr_input
 import fake_device_operator
 from fake_device_operator import as_device  # noqa: F401
 
@@ -130,20 +131,9 @@ class FakeFsaiLib(fake_device_operator.FakeDeviceOperatorLib):
 
     def _fsai_build(self, name, ph, code, n, ip, ix, va, max_row, levels=1, steps=0, step_size=0):
         # ---- the checks, on the arrays as they came
-        if ip[0] != 0:
-            return self._fail(name + ': indptr[0] must be 0')
-        d = np.diff(ip)
-        if np.any(d < 0):
-            return self._fail(name + ': indptr decreases at row %d' % int(np.argmax(d < 0)))
-        nnz = int(ip[-1])
-        rows = np.repeat(np.arange(n), d)
-        bad = (ix < 0) | (ix >= n)
-        if bad.any():
-            return self._fail(name + ': column index out of range in row %d' % int(rows[bad].min()))
-        if nnz > 1:
-            bad = (np.diff(ix) <= 0) & (rows[1:] == rows[:-1])
-            if bad.any():
-                return self._fail(name + ': the columns of row %d must ascend strictly (no duplicates)' % int(rows[1:][bad].min()))
+        if msg := fake_csr_input.message(name + ': ', ip, ix, n):
+            return self._fail(msg)
+        rows = np.repeat(np.arange(n), np.diff(ip))
         stored = set(zip(rows.tolist(), ix.tolist()))
         for i in range(n):
             if (i, i) not in stored:

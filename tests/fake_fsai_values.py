@@ -13,6 +13,7 @@ import numpy as np
 import scipy.sparse as sp
 
 from fake_lib import _DT, _addr, _flat
+import fake_csr_input
 import fake_fsai
 import fake_fsai_shard
 from fake_fsai_work import stored_type
@@ -25,23 +26,9 @@ class FakeFsaiValuesLib(fake_fsai_shard.FakeFsaiShardLib):
         """The checks on the arrays as they came, the solves, the commit.  cap: the entries the index and value arrays
         can hold (None: not known)."""
         n = f.g.shape[0]
-        if ip[0] != 0:
-            return self._fail(name + ': indptr[0] must be 0')
-        d = np.diff(ip)
-        if np.any(d < 0):
-            return self._fail(name + ': indptr decreases at row %d' % int(np.argmax(d < 0)))
-        nnz = int(ip[-1])
-        if cap is not None and nnz > cap:
-            return self._fail(name + ": indptr's last entry (%d) is not the number of stored entries (the index and value "
-                              'arrays hold at most %d)' % (nnz, cap))
-        rows = np.repeat(np.arange(n), d)
-        bad = (ix < 0) | (ix >= n)
-        if bad.any():
-            return self._fail(name + ': column index out of range in row %d' % int(rows[bad].min()))
-        if nnz > 1:
-            bad = (np.diff(ix) <= 0) & (rows[1:] == rows[:-1])
-            if bad.any():
-                return self._fail(name + ': the columns of row %d must ascend strictly (no duplicates)' % int(rows[1:][bad].min()))
+        if msg := fake_csr_input.message(name + ': ', ip, ix, n, cap):
+            return self._fail(msg)
+        rows = np.repeat(np.arange(n), np.diff(ip))
         has_diag = np.zeros(n, dtype=bool)
         has_diag[rows[rows == ix]] = True
         if not has_diag.all():
@@ -94,11 +81,8 @@ class FakeFsaiValuesLib(fake_fsai_shard.FakeFsaiShardLib):
         f = self._fsai[_addr(h)]
         n = f.g.shape[0]
         ip = _flat(indptr, np.int64, n + 1).copy()
-        if ip[0] != 0:
-            return self._fail(name + ': indptr[0] must be 0')
-        d = np.diff(ip)
-        if np.any(d < 0):
-            return self._fail(name + ': indptr decreases at row %d' % int(np.argmax(d < 0)))
+        if msg := fake_csr_input.indptr_message(name + ': ', ip):
+            return self._fail(msg)
         nnz = int(ip[-1])
         if nnz and not (_addr(indices) and _addr(values)):
             return self._fail(name + ': null indices or values')

@@ -171,19 +171,22 @@ def test_rejections_of_the_device_build():
         b[i], b[j] = a[j], a[i]
         return b
 
-    bad = {'indptr[0] = 1': dict(indptr=changed(ip, 0, 1)),
-           'indptr decreasing': dict(indptr=changed(ip, 5, ip[6] + 1)),
-           'wrong last entry': dict(indptr=changed(ip, -1, ip[-1] + 10 ** 7)),
-           'column = n_cols': dict(indices=changed(ix, k, A.shape[1])),
-           'negative column': dict(indices=changed(ix, k, -1)),
-           'equal columns': dict(indices=changed(ix, k + 1, ix[k])),
-           'descending columns': dict(indices=swapped(ix, k, k + 1))}
+    name = 'rlh_spd_create_device: '
+    last = "indptr's last entry (%d) is not the number of stored entries" % (ip[-1] + 10 ** 7)
+    order = 'the columns of a row must ascend strictly (no duplicates): entry %d' % (k + 1)
+    bad = {'indptr[0] = 1': (dict(indptr=changed(ip, 0, 1)), 'indptr[0] must be 0'),
+           'indptr decreasing': (dict(indptr=changed(ip, 5, ip[6] + 1)), 'indptr decreases at row 5'),
+           'wrong last entry': (dict(indptr=changed(ip, -1, ip[-1] + 10 ** 7)), last),
+           'column = n_cols': (dict(indices=changed(ix, k, A.shape[1])), 'column index out of range at entry %d' % k),
+           'negative column': (dict(indices=changed(ix, k, -1)), 'column index out of range at entry %d' % k),
+           'equal columns': (dict(indices=changed(ix, k + 1, ix[k])), order),
+           'descending columns': (dict(indices=swapped(ix, k, k + 1)), order)}
     for bits in (32, 64):
-        for what, kw in bad.items():
+        for what, (kw, text) in bad.items():
             rc, h = _create_device(A, dt, bits, **kw)
-            msg = _lib.library().rlh_last_error()
+            msg = _lib.library().rlh_last_error().decode()
             assert rc != 0 and not h.value, (what, bits)
-            assert b'rlh_spd_create_device' in msg and len(msg) > 30, (what, msg)
+            assert msg.startswith(name + text) and (msg == name + text or what == 'wrong last entry'), (what, msg)
         rc, h = _create_device(A, dt, bits)                 # a valid create straight afterwards
         _check(rc)
         x = np.ones((1, A.shape[1]))
