@@ -561,6 +561,38 @@ int rlh_fsfilter_create(rlh_fsai_t *h, int dtype, int64_t n, const int64_t *indp
                              const void *values, int max_row, int levels, int steps, int step_size, double drop);
 /* the threshold a handle was filtered with and the entries that removed (0, 0: a handle of the other forms) */
 int rlh_fsfilter_info(rlh_fsai_t h, double *drop, int64_t *removed);
+/* ---- prefiltration by value: rlh_fsthreshold_create and rlh_fsthreshold_create_device make a handle of the same kind
+ *      (rlh_fsai_t: every rlh_fsai_*, rlh_fsfilter_info, rlh_fsapply_* and rlh_fsvalues_* call takes it) whose level
+ *      pattern is that of the STRONG entries of A (Chow's a-priori patterns of the thresholded matrix).
+ * Only the upper triangle of A is read.  For a stored entry (i, j), j < i, the partner a_ji stored in row j decides:
+ * the entry is strong iff
+ *   |a_ji|^2 >= (tau^2 * a_ii) * a_jj,      tau = prefilter,
+ * evaluated in double on the widened values: |z|^2 = re * re + im * im (each product and the sum rounded on its own),
+ * a_ii and a_jj the real parts of the stored diagonals, tau^2 = tau * tau, the right-hand side formed in exactly that
+ * order with i the row; no division and no square root.  A comparison that involves a NaN is false: the entry is weak.
+ * The diagonal is always a member.  In exact arithmetic the rule is |a_ij| >= tau sqrt(a_ii a_jj), which does not
+ * change under A -> D A D, D diagonal positive; with every d_i a power of two the evaluation itself is exact and the
+ * patterns are equal.
+ * With L_tau(i) = {i} and the strong stored j < i of row i: P_1(i) = L_tau(i), P_{l+1}(i) the union of L_tau(j) over j
+ * in P_l(i); after every level the pattern is cut to its max_row largest columns, as for the forms above
+ * (truncated_rows, longest_row and the bins keep their meaning).  Where nothing is cut the patterns are nested in the
+ * level and in tau.
+ * Everything after the pattern is that of the forms above, on the FULL matrix: the local block is S = A[P, P] with all
+ * its stored entries, weak ones included (they shape the pattern, not the matrix); enrichment (steps > 0; steps == 0:
+ * none, step_size is then ignored) takes its candidates from the stored rows of A; drop (0: none) filters the computed
+ * G as rlh_fsfilter_create does; rlh_fsvalues_update* keeps the pattern and does not apply the rule again.
+ * prefilter must be finite with 0 < prefilter < 1.  The decisions read A alone, every row's members are written in
+ * ascending order by ranks: G is the same bits in every run, for both index widths, from host or device arrays and for
+ * both settings of RLH_FSAI_BINS.  With no weak entry G is bit for bit that of the forms above.
+ * rlh_fsthreshold_info: the threshold a handle was built with and the stored entries below the diagonal that were not
+ * strong (0, 0: a handle of the other forms). */
+int rlh_fsthreshold_create_device(rlh_fsai_t *h, int dtype, int64_t n, int index_bits, const void *d_indptr,
+                                  const void *d_indices, const void *d_values, int max_row, int levels, int steps,
+                                  int step_size, double drop, double prefilter);
+int rlh_fsthreshold_create(rlh_fsai_t *h, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
+                           const void *values, int max_row, int levels, int steps, int step_size, double drop,
+                           double prefilter);
+int rlh_fsthreshold_info(rlh_fsai_t h, double *prefilter, int64_t *weak_entries);
 /* Y = G^H (G X) for column-major DEVICE blocks of m vectors (leading dimensions >= n; Y may be X): two sparse
  * products (the kernels of rlh_spd_apply, bit-identical from call to call) through an n x m workspace of the handle,
  * which grows when a wider block than before arrives (that call synchronises the stream once); otherwise

@@ -129,6 +129,10 @@ SIGNATURES = {
     'rlh_fsfilter_create_device': [ctypes.POINTER(_p), _int, _i64, _int, _p, _p, _p, _int, _int, _int, _int, ctypes.c_double],
     'rlh_fsfilter_create': [ctypes.POINTER(_p), _int, _i64, _p, _p, _p, _int, _int, _int, _int, ctypes.c_double],
     'rlh_fsfilter_info': [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i64)],
+    'rlh_fsthreshold_create_device': [ctypes.POINTER(_p), _int, _i64, _int, _p, _p, _p, _int, _int, _int, _int, ctypes.c_double,
+                                      ctypes.c_double],
+    'rlh_fsthreshold_create': [ctypes.POINTER(_p), _int, _i64, _p, _p, _p, _int, _int, _int, _int, ctypes.c_double, ctypes.c_double],
+    'rlh_fsthreshold_info': [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i64)],
     'rlh_fsai_apply': [_p, _i64, _p, _i64, _p, _i64],
     'rlh_fsai_info': [_p, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                       ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)],

@@ -655,14 +655,15 @@ class ShardedApproximateInverse:
 
     The two constructors take what those of ShardedSparseMatrix take: the same global SciPy matrix on every rank
     (upper triangle significant), or with ``from_local_rows`` this rank's rows of the full matrix with global columns.
-    max_row, levels, steps, step_size and drop are the arguments of ApproximateInverse; work is 'native', 'float32' or
+    max_row, levels, steps, step_size, drop and prefilter are the arguments of ApproximateInverse; work is 'native', 'float32' or
     'bf16' as there (there is no None: the sharded form has only the plan).
 
     Set-up (host SciPy, the device builder, object collectives -- nothing of it runs per application).  With H the
     global columns below r0 that the rank's rows of A store and E = H + [r0, r1) ascending, the rank runs
     ApproximateInverse on A[E, E] and keeps the last r1 - r0 rows; the rows H of A come from their owners.  At
     ``levels=1, steps=0`` (any drop) every pattern lies inside E, and the rows are those of the single-GPU G bit for
-    bit.  With more levels or enrichment steps the pattern is the one the builder finds INSIDE A[E, E]: G is still
+    bit; so they are with a prefilter, whose rule for the entry (i, j) of an own row reads a_ji, a_ii and a_jj, all of
+    them in A[E, E].  With more levels or enrichment steps the pattern is the one the builder finds INSIDE A[E, E]: G is still
     lower triangular with a positive diagonal, every row the Kaporin minimiser on its pattern, T Hermitian positive
     definite -- but the pattern depends on the partition (level patterns that reach through deeper halos are not
     built).  The entries g_ij whose column j belongs to a lower rank are sent to that rank once.
@@ -682,7 +683,8 @@ class ShardedApproximateInverse:
 
     WORK = WORK
 
-    def __init__(self, matrix, comm, offsets=None, max_row=64, levels=1, steps=0, step_size=1, work='native', drop=0.0):
+    def __init__(self, matrix, comm, offsets=None, max_row=64, levels=1, steps=0, step_size=1, work='native', drop=0.0,
+                 prefilter=0.0):
         self._plan = None
         check_work(work, matrix.dtype)
         full = full_from_upper(matrix)
@@ -690,11 +692,11 @@ class ShardedApproximateInverse:
         off = partition(n, comm.size) if offsets is None else offsets
         r0, r1 = int(off[comm.rank]), int(off[comm.rank + 1])
         self._setup(scs.csr_matrix(full[r0:r1, :]), r0, n, comm, off, lambda ids: scs.csr_matrix(full[ids, :]),
-                    dict(max_row=max_row, levels=levels, steps=steps, step_size=step_size, drop=drop), work)
+                    dict(max_row=max_row, levels=levels, steps=steps, step_size=step_size, drop=drop, prefilter=prefilter), work)
 
     @classmethod
     def from_local_rows(cls, rows, row0, n, comm, offsets, max_row=64, levels=1, steps=0, step_size=1, work='native',
-                        drop=0.0):
+                        drop=0.0, prefilter=0.0):
         """From this rank's rows [row0, row0 + rows.shape[0]) of the FULL (both triangles) matrix with global column
         indices; the rows of lower ranks that the build needs come from their owners."""
         self = cls.__new__(cls)
@@ -721,7 +723,7 @@ class ShardedApproximateInverse:
                 parts.append(scs.csr_matrix((va, ix, ip), shape=(len(ask[p]), n)))
             return scs.vstack(parts, format='csr') if parts else scs.csr_matrix((0, n), dtype=rows.dtype)
         self._setup(rows, row0, n, comm, offsets, rows_of,
-                    dict(max_row=max_row, levels=levels, steps=steps, step_size=step_size, drop=drop), work)
+                    dict(max_row=max_row, levels=levels, steps=steps, step_size=step_size, drop=drop, prefilter=prefilter), work)
         return self
 
     def _setup(self, loc, r0, n, comm, off, rows_of, build, work):
@@ -748,15 +750,16 @@ class ShardedApproximateInverse:
         a_ext.sort_indices()
         T = ApproximateInverse(a_ext, work=None, **build)
         self.levels, self.steps, self.step_size, self.drop = T.levels, T.steps, T.step_size, T.drop
+        self.prefilter = T.prefilter
         g_own = scs.csr_matrix(T.csr()[below.size:, :])
         dropped = T.dropped_entries
         del T
         if self.drop and below.size:                           # the builder's count includes the rows of lower ranks
-            if self.levels == 1 and self.steps == 0:           # (the unfiltered pattern is known: the stored columns j <= i)
+            if self.levels == 1 and self.steps == 0 and not self.prefilter:      # (the unfiltered pattern is known: the stored columns j <= i)
                 rows_a = np.repeat(np.arange(r0, r1, dtype=np.int64), np.diff(loc.indptr))
                 lower = np.bincount(rows_a[cols <= rows_a] - r0, minlength=n_own)
                 dropped = int(np.minimum(lower, int(build['max_row'])).sum()) - int(g_own.nnz)
-            else:                                              # (it is not: the same build unfiltered, for its row lengths)
+            else:                                              # (it is not: the same build, prefilter included, without drop, for its row lengths)
                 plain = ApproximateInverse(a_ext, work=None, **dict(build, drop=0.0))
                 dropped = int(plain.csr()[below.size:, :].nnz) - int(g_own.nnz)
                 del plain

@@ -40,6 +40,13 @@ __device__ __forceinline__ void build_error(BuildStatus *st, int code, int64_t p
 // failed its check
 __device__ __forceinline__ bool failed(const BuildStatus *st) { return *(const volatile unsigned long long *)&st->err != kNoError; }
 
+// The same for a kernel that records errors itself, `first` being the smallest code it records: only a smaller code, that
+// of an earlier check, ends it.  What another workgroup of its own launch has found meanwhile must not end a workgroup
+// that starts later: the record is to hold the smallest of all findings, whatever the order in which the workgroups run.
+__device__ __forceinline__ bool failed_before(const BuildStatus *st, int first) {
+  return (int)(*(const volatile unsigned long long *)&st->err >> 56) < first;
+}
+
 // indptr[0] == 0, non-decreasing, the last entry within [0, cap] (cap: the entries the index and value arrays
 // can hold): then every indptr[r] lies in [0, cap] and the kernels below stay inside the arrays
 template <typename I>
@@ -61,7 +68,7 @@ __global__ __launch_bounds__(kBlock) void spd_check_indptr(int64_t M, const I *_
 template <bool BY_ENTRY, typename P, typename I>
 __global__ __launch_bounds__(kBlock) void check_columns(int64_t M, int64_t N, const P *__restrict__ ip, const I *__restrict__ ix,
                                                         BuildStatus *st) {
-  if (failed(st)) return;
+  if (failed_before(st, kErrRange)) return;
   const int lane = threadIdx.x & 63;
   const int64_t waves = (int64_t)gridDim.x * (kBlock / 64);
   for (int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); r < M; r += waves) {

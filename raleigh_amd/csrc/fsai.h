@@ -12,6 +12,8 @@ struct rlh_fsai {
   double setup_seconds = 0;
   double drop = 0;                  // post-filtration: the threshold (0: none) and the entries it removed
   int64_t removed = 0;
+  double prefilter = 0;             // prefiltration: the threshold (0: none) and the lower entries of A it found weak
+  int64_t weak = 0;
   int64_t updates = 0;              // rlh_fsvalues_update*: the successful ones and the device seconds of the last
   double update_seconds = 0;
   rlh_spd_t spd = nullptr;          // G and G^H with their partitions

@@ -19,6 +19,12 @@
 //                   steps on: a descending selection without a sort, at most max_row + 1 steps per level.  Capping
 //                   to the max_row largest after every level gives the capped final pattern: what a dropped column
 //                   j reaches is <= j, below every kept column, and the kept ones are in the next union themselves.
+//   prefiltration   (the rlh_fsthreshold_* entry points only, between the checks and the pattern) fsai_diagonal, then
+//                   fsai_strong<T, false>, 8 lanes per row: the lower entries whose partner above the diagonal is large
+//                   against prefilter in a scaling-invariant measure are counted per row; one scan, one wait for the
+//                   size and for what the checks found, and fsai_strong<T, true> writes the strong lower structure
+//                   (a CSR of the strong entries, the diagonal last in each row).  The pattern kernels of every level,
+//                   1 included, walk it in place of A; everything after the pattern reads the caller's arrays.
 //   enrichment      (the _adaptive entry points only) fsai_enrich<T, LANES>: `steps` times per row, solve on the pattern
 //                   and take the (at most step_size) columns below i, stored in a member's row, that lower the row's
 //                   Kaporin functional most.  The rows are binned by their capacity min(max_row, k + steps *
@@ -75,6 +81,7 @@ struct FsaiStatus : PartnerStatus {
   unsigned long long limited;                  // adaptive build: rows max_row held back (those cut are among them)
   unsigned long long removed;                  // post-filtration: entries of G dropped
   int kept_longest;                            // post-filtration: longest row of the filtered G
+  unsigned long long weak;                     // prefiltration: stored entries below the diagonal that are not strong
 };
 
 // The rows of a build go to bins by their kept entries k: 8, 16, 32 or 64 lanes per row (two bins: 8 or 64).  Two
@@ -111,7 +118,7 @@ __global__ __launch_bounds__(kBlock) void fsai_count(int64_t n, int max_row, int
                                                      const int32_t *__restrict__ ix, int64_t *__restrict__ cnt,
                                                      int64_t *__restrict__ keya, int64_t *__restrict__ keyb,
                                                      int64_t *__restrict__ start, FsaiStatus *st) {
-  if (failed(st)) return;
+  if (failed_before(st, kErrDiag)) return;
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
     const int64_t kb = ip[i], ke = ip[i + 1];
@@ -158,7 +165,7 @@ __global__ __launch_bounds__(kBlock) void fsai_kept_rows(int64_t n, int four, co
                                                          const int32_t *__restrict__ ix, const int64_t *__restrict__ gp,
                                                          int64_t *__restrict__ cnt, int64_t *__restrict__ keya,
                                                          int64_t *__restrict__ keyb, FsaiStatus *st) {
-  if (failed(st)) return;
+  if (failed_before(st, kErrDiag)) return;
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
     const int64_t ke = ip[i + 1], d = lower_bound_col(ix, ip[i], ke, i);
@@ -605,6 +612,66 @@ __global__ __launch_bounds__(kBlock) void fsai_filter(int64_t n, double drop2, i
   }
 }
 
+// ---------------------------------------------------------------- prefiltration: the strong lower structure
+constexpr int kStrongLanes = 8;                // lanes per row of fsai_strong: 32 rows per workgroup
+
+// |a|^2 as re^2 + im^2, each product and the sum rounded on its own
+__device__ __forceinline__ double abs2_plain(double a) { return a * a; }
+__device__ __forceinline__ double abs2_plain(c64 a) {
+#pragma clang fp contract(off)
+  const double r = a.re * a.re, s = a.im * a.im;
+  return r + s;
+}
+
+// Row i of A by a group of kStrongLanes lanes: the stored entry (i, j), j < i, is strong iff its partner a_ji (row j,
+// above the diagonal: nothing below it is read) has |a_ji|^2 >= (tau2 * a_ii) * a_jj -- tau2 = prefilter * prefilter,
+// all in double, no division and no square root; false where a NaN takes part, and where the partner is missing (then
+// fsai_count has recorded the error).  FILL = false: cnt[i] = the members of L_tau(i), the strong columns and the
+// diagonal; the weak entries go to st->weak.  FILL = true (the same decisions again, after the scan sp of the counts):
+// the strong columns in their order (ranks from the group's ballot) and then i go to six[sp[i] ..): the CSR of the
+// strong lower triangle, the diagonal last in each row, which the pattern kernels walk in place of A.  The groups of
+// a wave run different trip counts: nothing but the ballot crosses lanes, and a group reads only its own bits of it.
+template <typename T, bool FILL>
+__global__ __launch_bounds__(kBlock) void fsai_strong(int64_t n, double tau2, const int64_t *__restrict__ ip,
+                                                      const int32_t *__restrict__ ix, const T *__restrict__ va,
+                                                      const double *__restrict__ diag, int64_t *__restrict__ cnt,
+                                                      const int64_t *__restrict__ sp, int32_t *__restrict__ six, FsaiStatus *st) {
+  if (!FILL && failed(st)) return;
+  constexpr int kRows = kBlock / kStrongLanes;
+  const int lane = threadIdx.x % kStrongLanes;
+  const int base = (threadIdx.x & 63) - lane;          // the group's first lane within its wave
+  for (int64_t i = (int64_t)blockIdx.x * kRows + threadIdx.x / kStrongLanes; i < n; i += (int64_t)gridDim.x * kRows) {
+    const int64_t kb = ip[i], d = lower_bound_col(ix, kb, ip[i + 1], i);      // [kb, d): the entries below the diagonal
+    const double bar = tau2 * diag[i];
+    const int64_t s0 = FILL ? sp[i] : 0, room = FILL ? sp[i + 1] - s0 : 0;
+    int64_t kept = 0;
+    for (int64_t e0 = kb; e0 < d; e0 += kStrongLanes) {
+      const int64_t e = e0 + lane;
+      bool strong = false;
+      int32_t j = 0;
+      if (e < d) {
+        j = ix[e];
+        const int64_t je = ip[j + 1], f = lower_bound_col(ix, ip[j], je, i);
+        strong = f < je && (int64_t)ix[f] == i && abs2_plain(widen(va[f])) >= bar * diag[j];
+      }
+      const unsigned mine = (unsigned)(__ballot(strong) >> base) & ((1u << kStrongLanes) - 1);
+      if (FILL && strong) {
+        const int64_t at = kept + __popc(mine & ((1u << lane) - 1));
+        if (at < room) six[s0 + at] = j;               // (always: the decisions are the counting pass's)
+      }
+      kept += __popc(mine);
+    }
+    if (lane == 0) {
+      if (FILL) {
+        if (kept < room) six[s0 + kept] = (int32_t)i;
+      } else {
+        cnt[i] = kept + 1;
+        if (kept < d - kb) atomicAdd(&st->weak, (unsigned long long)(d - kb - kept));
+      }
+    }
+  }
+}
+
 // ---------------------------------------------------------------- the host side
 // RLH_FSAI_BINS=0: the two bins of 8 and 64 lanes per row
 int four_bins() {
@@ -621,6 +688,8 @@ struct FsaiPlan {
   int steps, step_size;
   double drop = 0.0;
   bool filtered = false;
+  double prefilter = 0.0;                              // rlh_fsthreshold_create*, whose prefilter is checked; the others leave it 0
+  bool thresholded = false;
   int four = four_bins();
   int grow() const { return steps * step_size; }       // what enrichment can add to a row
 };
@@ -740,12 +809,46 @@ int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T 
   DevBuf<int64_t> start;
   if (int rc = w.alloc_rows(n)) return rc;
   if (int rc = start.alloc(n)) return rc;
-  hipLaunchKernelGGL(fsai_count, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, max_row, levels == 1 ? 1 : 0, four, grow, ip64,
-                     ix32, w.cnt, w.ka, w.kb, start, w.status);
+  const bool strong = plan.prefilter > 0;
+  hipLaunchKernelGGL(fsai_count, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, max_row, levels == 1 && !strong ? 1 : 0, four,
+                     grow, ip64, ix32, w.cnt, w.ka, w.kb, start, w.status);
   hipLaunchKernelGGL((resolve_partner<int64_t, int32_t>), dim3(1), dim3(1), 0, st, n, ip64, ix32, w.status);
-  if (levels > 1)
-    hipLaunchKernelGGL(fsai_pattern_count, dim3(blocks_for(n, kBlock / 64, most)), blk, 0, st, n, max_row, levels, four, grow, ip64,
-                       ix32, w.cnt, w.ka, w.kb, w.status);
+  // the structure the pattern is the power of: A's own arrays, or (prefiltration) the strong lower triangle
+  const int64_t *pat_ip = ip64;
+  const int32_t *pat_ix = ix32;
+  DevBuf<double> strong_diag;
+  DevBuf<int64_t> strong_ip;
+  DevBuf<int32_t> strong_ix;
+  if (strong) {
+    // ---- prefiltration: every lower entry is decided by value (counts in w.cnt, which the pattern overwrites later),
+    // the counts are scanned, the host waits once for the size and for what the checks found, and the strong lower
+    // structure is filled.  The pattern kernels of every level, 1 included, walk it in place of A.
+    const double tau2 = plan.prefilter * plan.prefilter;
+    const unsigned grid = blocks_for(n, kBlock / kStrongLanes, most);
+    if (int rc = strong_diag.alloc(n)) return rc;
+    if (int rc = strong_ip.alloc(n + 1)) return rc;
+    hipLaunchKernelGGL(fsai_diagonal<T>, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, ip64, ix32, va, strong_diag.get());
+    hipLaunchKernelGGL((fsai_strong<T, false>), dim3(grid), blk, 0, st, n, tau2, ip64, ix32, va, (const double *)strong_diag,
+                       w.cnt.get(), (const int64_t *)nullptr, (int32_t *)nullptr, w.status.get());
+    RLH_HIP(hipGetLastError());
+    if (int rc = exclusive_scan(n, w.cnt, w.bsum, strong_ip)) return rc;
+    int64_t members = 0;
+    RLH_HIP(hipMemcpyAsync(&hs, w.status, sizeof hs, hipMemcpyDeviceToHost, st));
+    RLH_HIP(hipMemcpyAsync(&members, strong_ip + n, 8, hipMemcpyDeviceToHost, st));
+    RLH_HIP(hipStreamSynchronize(st));
+    if (hs.err != kNoError) return report(name, hs, cap);
+    RLH_REQUIRE(members >= n && members <= in.nnz && (int64_t)hs.weak + members <= in.nnz, "%s: inconsistent row counts of the pattern", name);
+    if (int rc = strong_ix.alloc(members)) return rc;
+    hipLaunchKernelGGL((fsai_strong<T, true>), dim3(grid), blk, 0, st, n, tau2, ip64, ix32, va, (const double *)strong_diag,
+                       (int64_t *)nullptr, (const int64_t *)strong_ip, strong_ix.get(), w.status.get());
+    RLH_HIP(hipGetLastError());
+    pat_ip = strong_ip;
+    pat_ix = strong_ix;
+    h->weak = (int64_t)hs.weak;
+  }
+  if (levels > 1 || strong)
+    hipLaunchKernelGGL(fsai_pattern_count, dim3(blocks_for(n, kBlock / 64, most)), blk, 0, st, n, max_row, levels, four, grow, pat_ip,
+                       pat_ix, w.cnt, w.ka, w.kb, w.status);
   int64_t gnnz = 0;
   Bins bins{};
   if (int rc = pattern_totals(name, n, w, cap, n, n * (int64_t)max_row, &hs, &gnnz, &bins)) return rc;
@@ -753,10 +856,10 @@ int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T 
   if (int rc = gi.alloc(gnnz)) return rc;
   if (int rc = bin_rows.alloc(n)) return rc;
   bins.rows = bin_rows;
-  if (levels == 1)
+  if (levels == 1 && !strong)
     hipLaunchKernelGGL(fsai_fill, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, ix32, start, w.gp, gi, bins);
   else
-    hipLaunchKernelGGL(fsai_pattern_fill, dim3(blocks_for(n, kBlock / 64, most)), blk, 0, st, n, max_row, levels, ip64, ix32, w.gp,
+    hipLaunchKernelGGL(fsai_pattern_fill, dim3(blocks_for(n, kBlock / 64, most)), blk, 0, st, n, max_row, levels, pat_ip, pat_ix, w.gp,
                        gi, bins);
   DevBuf<int64_t> capacity, sp;
   DevBuf<int32_t> slab, level;
@@ -922,6 +1025,8 @@ int check_create_args(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, co
                 kMaxStepSize, plan.step_size);
   }
   if (plan.filtered) RLH_REQUIRE(plan.drop > 0.0 && plan.drop < 1.0, "%s: drop must lie in (0, 1), got %g", name, plan.drop);
+  if (plan.thresholded)
+    RLH_REQUIRE(plan.prefilter > 0.0 && plan.prefilter < 1.0, "%s: prefilter must lie in (0, 1), got %g", name, plan.prefilter);
   RLH_REQUIRE(indptr, "%s: null indptr", name);
   return 0;
 }
@@ -935,6 +1040,7 @@ template <typename Build> int make_handle(rlh_fsai_t *ph, int dtype, int64_t n, 
   h->steps = plan.steps;
   h->step_size = plan.step_size;
   h->drop = plan.drop;
+  h->prefilter = plan.prefilter;
   if (int rc = n > 0 ? build(h) : 0) {
     rlh_fsai_destroy(h);
     return rc;
@@ -1044,6 +1150,36 @@ extern "C" int rlh_fsfilter_info(rlh_fsai_t h, double *drop, int64_t *removed) {
   RLH_REQUIRE(h && drop && removed, "rlh_fsfilter_info: null handle or output");
   *drop = h->drop;
   *removed = h->removed;
+  return 0;
+}
+
+// steps == 0: no enrichment; drop == 0: no post-filtration (anything else, a NaN included, is checked as a drop)
+static FsaiPlan thresholded_plan(int max_row, int levels, int steps, int step_size, double drop, double prefilter) {
+  FsaiPlan plan = filtered_plan(max_row, levels, steps, step_size, drop);
+  plan.filtered = !(drop == 0.0);
+  plan.prefilter = prefilter;
+  plan.thresholded = true;
+  return plan;
+}
+
+extern "C" int rlh_fsthreshold_create_device(rlh_fsai_t *ph, int dtype, int64_t n, int index_bits, const void *d_indptr,
+                                             const void *d_indices, const void *d_values, int max_row, int levels, int steps,
+                                             int step_size, double drop, double prefilter) {
+  return create_device("rlh_fsthreshold_create_device", ph, dtype, n, index_bits, d_indptr, d_indices, d_values,
+                       thresholded_plan(max_row, levels, steps, step_size, drop, prefilter));
+}
+
+extern "C" int rlh_fsthreshold_create(rlh_fsai_t *ph, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
+                                      const void *values, int max_row, int levels, int steps, int step_size, double drop,
+                                      double prefilter) {
+  return create_host("rlh_fsthreshold_create", ph, dtype, n, indptr, indices, values,
+                     thresholded_plan(max_row, levels, steps, step_size, drop, prefilter));
+}
+
+extern "C" int rlh_fsthreshold_info(rlh_fsai_t h, double *prefilter, int64_t *weak_entries) {
+  RLH_REQUIRE(h && prefilter && weak_entries, "rlh_fsthreshold_info: null handle or output");
+  *prefilter = h->prefilter;
+  *weak_entries = h->weak;
   return 0;
 }
 

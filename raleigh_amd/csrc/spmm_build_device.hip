@@ -55,7 +55,7 @@ struct CsrStatus : PartnerStatus {
 template <typename I>
 __global__ __launch_bounds__(kBlock) void csr_check_partners(int64_t M, const I *__restrict__ ip, const I *__restrict__ ix,
                                                              BuildStatus *st) {
-  if (failed(st)) return;
+  if (failed_before(st, kErrPartner)) return;
   const int lane = threadIdx.x & 63;
   const int64_t waves = (int64_t)gridDim.x * (kBlock / 64);
   for (int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); r < M; r += waves) {

@@ -47,7 +47,9 @@ def partial_hevp(A, B=None, T=None, buckling=False, sigma=0, which=6, tol=1e-4, 
     kernels with the block between the two products kept in the matrix type, float32 or bfloat16 -- the same
     preconditioner up to the rounding of that block, a few iterations more or fewer; ``drop=`` removes the entries
     of the computed G that are small in a scaling-invariant measure and solves every row again on what is left: a
-    cheaper application for a few more iterations; along a sequence of matrices of one size and type
+    cheaper application for a few more iterations; ``prefilter=`` takes the level pattern of the strong entries of
+    the matrix alone, |a_ij| >= prefilter sqrt(a_ii a_jj): fewer entries per row at the same level, and a level
+    pattern of which ``max_row`` cuts less; along a sequence of matrices of one size and type
     ``T.update_values(matrix)`` solves every row again on the pattern T already has, so the pattern is paid for
     once), as `ChebyshevPreconditioner`
     is from the operator; an IncompleteLU preconditioner is a host factorisation and is set up from a SciPy matrix

@@ -2,6 +2,8 @@
 (host ILUT, triangular solves on the GPU) and no preconditioner, in the same run, float64 (GPU box):
 
   (i)  the config-3 FE surrogate (raleigh_amd/synthetic.py)      (ii) lap3d 64^3      -- the sizes of tools/ilu_bench.py
+  (iii) the anisotropic 7-point Laplacian lap3d_rows(N, N, N, 1.0, 0.1, 0.01) at the --lap size (the arguments are mesh
+       widths, the couplings 1, 100 and 10000: three values of |a_ij| / sqrt(a_ii a_jj), 0.495, 0.00495, 0.0000495)
 
   levels       --levels 1,2,3: one ApproximateInverse per level of fill (the pattern of that power of the lower triangle),
                each reported with its longest row, entries per row and truncated rows, next to IncompleteLU and no
@@ -25,6 +27,12 @@
                same run against the unfiltered build of the same pattern arguments -- and, with --work, each filtered
                build's plan against the unfiltered build's plan of the same work form
 
+  prefilter    --prefilter 0.016,iii:0.01,...: every --levels and --adaptive build once more with each `prefilter` (the level
+               pattern of the entries with |a_ij| >= prefilter sqrt(a_ii a_jj) alone), reported with its weak entries and
+               measured like a --drop build against the build of the same pattern arguments without it (set-up,
+               application, with --work each plan against the plan of the same work form, solve).  A value with a prefix
+               i:, ii: or iii: is used on that matrix only; --matrices i,iii runs those matrices only
+
   update       --update: for every build above (and, with --work, its plan) the construction against `update_values` with
                re-valued copies of the same matrix (every off-diagonal entry of the upper triangle times a factor in
                [0.5, 1), every diagonal entry times one in [1, 2), the lower triangle mirrored: the structure stays, the
@@ -40,6 +48,7 @@ set-up lines (for comparing two builds of the library on one machine).
 
     python tools/approx_inverse_bench.py [--out profiles/r11_approx_inverse_levels.txt] [--levels 1,2,3]
                                          [--adaptive 1:4:4,1:4:8,2:2:4] [--work native,float32,bf16] [--drop 0.01,0.02,0.05]
+                                         [--prefilter i:0.016,i:0.02,iii:0.01,iii:0.1] [--matrices i,ii,iii]
                                          [--m 16] [--calls 20] [--repeats 5] [--setup-only] [--update [--sequence-repeats 5]]
 """
 import argparse
@@ -69,6 +78,9 @@ def main():
     ap.add_argument('--adaptive', default='', help='adaptive patterns as LEVELS:STEPS:SIZE, comma separated')
     ap.add_argument('--work', default='', help="work forms of the application ('native', 'float32', 'bf16'), comma separated")
     ap.add_argument('--drop', default='', help='post-filtration thresholds in (0, 1), comma separated')
+    ap.add_argument('--prefilter', default='', help='prefiltration thresholds in (0, 1), comma separated; i:, ii: or iii: in front '
+                                                    'of a value restricts it to that matrix')
+    ap.add_argument('--matrices', default='i,ii,iii', help='the matrices to run, comma separated: i, ii, iii')
     ap.add_argument('--setup-only', action='store_true', help='set-up timings only')
     ap.add_argument('--update', action='store_true', help='construction against update_values, and a sequence of matrices')
     ap.add_argument('--sequence-repeats', type=int, default=None, help='repeats of the sequence of --update (default: --repeats)')
@@ -83,6 +95,9 @@ def main():
     assert all(len(spec) == 3 for spec in adaptive), '--adaptive takes LEVELS:STEPS:SIZE'
     works = [w for w in args.work.split(',') if w]
     drops = [float(v) for v in args.drop.split(',') if v]
+    prefilters = [(v.rpartition(':')[0], float(v.rpartition(':')[2])) for v in args.prefilter.split(',') if v]      # (matrix or '', value)
+    assert all(tag in ('', 'i', 'ii', 'iii') for tag, _ in prefilters), '--prefilter takes values, or i:value, ii:value, iii:value'
+    chosen = [v for v in args.matrices.split(',') if v]
     import torch
     import scipy.sparse as sp
     from raleigh_amd import _lib
@@ -195,8 +210,12 @@ def main():
     say()
     side = args.lap
     cases = [('(i) config-3 FE surrogate', lambda: fe_surrogate()),
-             ('(ii) lap3d %d^3' % side, lambda: lap3d_rows(side, side, side, 1.0, 1.01, 1.02, 0, side ** 3))]
+             ('(ii) lap3d %d^3' % side, lambda: lap3d_rows(side, side, side, 1.0, 1.01, 1.02, 0, side ** 3)),
+             ('(iii) anisotropic lap3d %d^3 (1.0, 0.1, 0.01)' % side, lambda: lap3d_rows(side, side, side, 1.0, 0.1, 0.01, 0, side ** 3))]
     for title, make in cases:
+        tag = title[1:title.index(')')]
+        if tag not in chosen:
+            continue
         A = sp.csr_matrix(make().astype(np.float64))
         A.sort_indices()
         n = A.shape[0]
@@ -217,6 +236,12 @@ def main():
                 kwargs.append(dict(kw, drop=d))
                 names.append('%s drop=%g' % (name, d))
                 drop_names.append((names[-1], name))
+        for kw, name in list(zip(kwargs, names))[:len(plain_names)]:      # (measured like the --drop builds, against the same builds)
+            for own, tau in prefilters:
+                if own in ('', tag):
+                    kwargs.append(dict(kw, prefilter=tau))
+                    names.append('%s prefilter=%g' % (name, tau))
+                    drop_names.append((names[-1], name))
         Ts, walls, devs = {}, {}, {}
         for kw, name in zip(kwargs, names):
             dev_s, wall_s = [], []
@@ -232,7 +257,8 @@ def main():
             say('   set-up  %-29s device %s s, host wall %s s; nnz(G) = %d (%.1f per row, fill %.2f, longest row %d, '
                 '%d rows cut%s), %.1f MB held' % (name, span(dev_s, fmt='%.4f'), span(wall_s, fmt='%.4f'), T.nnz, T.nnz / n, T.fill,
                                                   T.longest_row, T.truncated_rows,
-                                                  ', %d entries dropped' % T.dropped_entries if T.drop else '', T.device_bytes() / 1e6))
+                                                  (', %d entries dropped' % T.dropped_entries if T.drop else '')
+                                                  + (', %d weak entries of A' % T.weak_entries if T.prefilter else ''), T.device_bytes() / 1e6))
         for dname, name in drop_names:
             say('           ' + verdict(dname, name, devs[dname], devs[name]) + ' [set-up, device]')
         for (lv, steps, size), name in zip(adaptive, adaptive_names):
