@@ -214,6 +214,21 @@ def work_element_bytes(work, dtype):
     return ev, (2 if work == 'bf16' else ev)
 
 
+def create_entry(levels, steps, step_size, drop, prefilter):
+    """The library's create call for these (checked) arguments: (stem, the arguments after max_row).  The entry point
+    is stem + '_device' for a tensor on the GPU and stem for host arrays.  Level 1 without anything else goes through
+    the entry points it always had."""
+    if prefilter:
+        return 'rlh_fsthreshold_create', (levels, steps, step_size, drop, prefilter)
+    if drop:
+        return 'rlh_fsfilter_create', (levels, steps, step_size, drop)
+    if steps:
+        return 'rlh_fsai_create_adaptive', (levels, steps, step_size)
+    if levels > 1:
+        return 'rlh_fsai_create_levels', (levels,)
+    return 'rlh_fsai_create', ()
+
+
 class ApproximateInverse:
     """Factorised sparse approximate inverse T = G^H G ~ A^-1 (Kolotilina-Yeremin) of a Hermitian positive definite
     matrix, built AND applied on the device (rlh_fsai_*): the preconditioner for a matrix that already lies on the
@@ -312,23 +327,13 @@ class ApproximateInverse:
         if not 0.0 <= prefilter < 1.0:                      # (false for NaN)
             raise ValueError('prefilter must lie in [0, 1), got %g' % prefilter)
         self.levels, self.steps, self.step_size, self.drop, self.prefilter = levels, steps, step_size, drop, prefilter
-        if prefilter:
-            more, kind = (levels, steps, step_size, drop, prefilter), None      # (rlh_fsthreshold_create*)
-        elif drop:
-            more, kind = (levels, steps, step_size, drop), None      # (rlh_fsfilter_create*)
-        elif steps:
-            more, kind = (levels, steps, step_size), '_adaptive'
-        else:                                               # (level 1 goes through the entry points it always had)
-            more, kind = (() if levels == 1 else (levels,)), ('' if levels == 1 else '_levels')
+        name, more = create_entry(levels, steps, step_size, drop, prefilter)
         self._dtype, self._n, self._nnz_a, bits, pointers, _alive = self._matrix_arrays(matrix)
         code = _lib.DTYPE_CODE[self._dtype]
-        # the entry point and its arguments between the handle and max_row (the arrays they point at live to the call)
+        # the arguments between the handle and max_row (the arrays they point at live to the call)
         if bits is not None:
-            name = ('rlh_fsthreshold_create_device' if prefilter else
-                    'rlh_fsfilter_create_device' if drop else 'rlh_fsai_create%s_device' % kind)
-            args = (code, self._n, bits) + pointers
+            name, args = name + '_device', (code, self._n, bits) + pointers
         else:
-            name = 'rlh_fsthreshold_create' if prefilter else 'rlh_fsfilter_create' if drop else 'rlh_fsai_create' + kind
             args = (code, self._n) + pointers
         h = ctypes.c_void_p()
         check_work(work, self._dtype, none_ok=True)

@@ -12,6 +12,12 @@
 // The build, all on the library stream:
 //   checks          indptr (device_build.h), the columns of every row, then per row: the diagonal is stored and every
 //                   entry below it has its partner above (fsai_count)
+//   prefiltration   (the rlh_fsthreshold_* entry points only, between the checks and the pattern) fsai_diagonal, then
+//                   fsai_strong<T, false>, 8 lanes per row: the lower entries whose partner above the diagonal is large
+//                   against prefilter in a scaling-invariant measure are counted per row; one scan, one wait for the
+//                   size and for what the checks found, and fsai_strong<T, true> writes the strong lower structure
+//                   (a CSR of the strong entries, the diagonal last in each row).  The pattern kernels of every level,
+//                   1 included, walk it in place of A; everything after the pattern reads the caller's arrays.
 //   pattern         kept entries per row, exclusive scans, columns of G and the rows of the bins.  Level 1: a slice
 //                   of A's row (fsai_count, fsai_fill).  Higher levels: one wave per row (fsai_pattern_count, then
 //                   fsai_pattern_fill, which forms the row again).  Lane q walks L(P[q]) downwards from its diagonal;
@@ -19,12 +25,6 @@
 //                   steps on: a descending selection without a sort, at most max_row + 1 steps per level.  Capping
 //                   to the max_row largest after every level gives the capped final pattern: what a dropped column
 //                   j reaches is <= j, below every kept column, and the kept ones are in the next union themselves.
-//   prefiltration   (the rlh_fsthreshold_* entry points only, between the checks and the pattern) fsai_diagonal, then
-//                   fsai_strong<T, false>, 8 lanes per row: the lower entries whose partner above the diagonal is large
-//                   against prefilter in a scaling-invariant measure are counted per row; one scan, one wait for the
-//                   size and for what the checks found, and fsai_strong<T, true> writes the strong lower structure
-//                   (a CSR of the strong entries, the diagonal last in each row).  The pattern kernels of every level,
-//                   1 included, walk it in place of A; everything after the pattern reads the caller's arrays.
 //   enrichment      (the _adaptive entry points only) fsai_enrich<T, LANES>: `steps` times per row, solve on the pattern
 //                   and take the (at most step_size) columns below i, stored in a member's row, that lower the row's
 //                   Kaporin functional most.  The rows are binned by their capacity min(max_row, k + steps *
@@ -49,16 +49,22 @@
 // within their own wave, at points every lane of the group reaches together (the trip counts are the group's k).
 // What a kernel finds wrong goes to the status record (code and the smallest position), never to a trap.
 //
-// The host side follows the kernels.  An entry point makes an FsaiPlan (what the build is asked to do); create_host and
-// create_device check it and run fsai_build inside make_handle.  fsai_build is the one build path: its device arrays are
-// DevBufs (FsaiScratch holds those that pattern_totals works on), pattern_totals is the scan-fetch-wait-check sequence after the level pattern and again after
-// enrichment, and for_each_bin with launch_bin launches the enrichment and the set-up kernels bin by bin.
+// The host side follows the kernels.  An entry point makes an FsaiPlan from its named makers (what the build is asked
+// to do, and so which arguments are checked); create_host and create_device check it and run fsai_build inside
+// make_handle.  fsai_build is the one build path and reads as the list above: the stages are the members of FsaiBuild,
+// the state that owns every array one stage hands to the next -- checks, strong_structure (if prefilter), level_pattern,
+// enrich (if steps), solve, post_filter (if drop), make_operator.  Whether the level pattern is a slice of A's row or
+// the wave-per-row walk is decided once (FsaiBuild::slice).  pattern_totals is the scan-fetch-wait-check sequence on
+// the counts and keys in FsaiScratch; new_columns follows it with the column array of that size, and compact copies the
+// rows into it (fsai_fill): from A's rows at level 1, from the slab of the enrichment, from that of the filter.
+// for_each_bin with launch_bin launches the enrichment and the set-up kernels bin by bin.
 //
-// New values on the kept pattern (rlh_fsvalues_update*, fsai_update): the numeric phase alone.  checked_input (shared with
-// the build: the checks on the arrays as they came), fsai_kept_rows (a stored diagonal, the rows' lengths from the
-// handle's G, the keys of the bins), pattern_totals, fsai_bin_rows, then solve_rows (shared with the build: fsai_setup
-// bin by bin) into a scratch value array, the pattern read from the operator's own arrays of G.  Only when every row
-// succeeded do the values go to G and, conjugated, to G^H (spd_set_values, spmm_data.h); structure and partitions stay.
+// New values on the kept pattern (rlh_fsvalues_update*, fsai_update): the numeric phase alone, from the pieces the
+// stages are made of.  checked_input (the checks on the arrays as they came), fsai_kept_rows (a stored diagonal, the
+// rows' lengths from the handle's G, the keys of the bins), pattern_totals, fsai_bin_rows, then solve_rows (fsai_setup
+// bin by bin, as in the stage solve) into a scratch value array, the pattern read from the operator's own arrays of G.
+// Only when every row succeeded do the values go to G and, conjugated, to G^H (spd_set_values, spmm_data.h); structure
+// and partitions stay.
 #include "fsai.h"
 
 #include <algorithm>
@@ -679,23 +685,32 @@ int four_bins() {
   return (e && e[0] == '0' && e[1] == 0) ? 0 : 1;
 }
 
-// What a build is asked to do, made by the entry points.  adaptive: steps and step_size are checked (the _adaptive entry
-// points, rlh_fsfilter_create* with steps != 0); the others leave both 0.  filtered: rlh_fsfilter_create*,
-// whose drop is checked; the others leave it 0.  four: read from the environment by every create call.
+// What a build is asked to do, made by the entry points from the makers below: an entry point names the arguments it
+// has, and those are the ones check_create_args checks (adaptive: steps and step_size; filtered: drop; thresholded:
+// prefilter).  What an entry point does not have stays 0.  four: read from the environment by every create call.
 struct FsaiPlan {
-  int max_row, levels;
-  bool adaptive;
-  int steps, step_size;
+  int max_row = 0, levels = 1;
+  bool adaptive = false;
+  int steps = 0, step_size = 0;
   double drop = 0.0;
   bool filtered = false;
-  double prefilter = 0.0;                              // rlh_fsthreshold_create*, whose prefilter is checked; the others leave it 0
+  double prefilter = 0.0;
   bool thresholded = false;
   int four = four_bins();
   int grow() const { return steps * step_size; }       // what enrichment can add to a row
+
+  static FsaiPlan of_levels(int max_row, int levels) { FsaiPlan p; p.max_row = max_row; p.levels = levels; return p; }
+  FsaiPlan enriched(int s, int size) const { FsaiPlan p = *this; p.adaptive = true; p.steps = s; p.step_size = size; return p; }
+  FsaiPlan filtered_by(double d) const { FsaiPlan p = *this; p.filtered = true; p.drop = d; return p; }
+  FsaiPlan thresholded_by(double tau) const { FsaiPlan p = *this; p.thresholded = true; p.prefilter = tau; return p; }
+  // steps == 0: no enrichment, step_size is not looked at
+  FsaiPlan enriched_unless_0(int s, int size) const { return s != 0 ? enriched(s, size) : *this; }
+  // drop == 0: no post-filtration (anything else, a NaN included, is checked as a drop)
+  FsaiPlan filtered_unless_0(double d) const { return d == 0.0 ? *this : filtered_by(d); }
 };
 
-// The device arrays that pattern_totals works on and the events of one build: released when the build returns, however
-// it returns.  The other arrays are locals of fsai_build.
+// The device arrays that pattern_totals works on and the events of one build or update: released when it returns,
+// however it returns.
 struct FsaiScratch {
   DevBuf<FsaiStatus> status;
   DevBuf<int64_t> cnt, ka, kb;            // per row: kept entries and the keys of the bin,
@@ -788,47 +803,64 @@ int solve_rows(const char *name, int64_t n, const Bins &bins, const CsrInput &in
   return hs->err != kNoError ? report(name, *hs, in.cap) : 0;
 }
 
-// `name`: the entry point the messages speak for.  ip, ix, va: device arrays, n >= 1.
-template <typename T, typename P, typename I>
-int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T *va, const FsaiPlan &plan) {
+// One build: the arrays its stages hand to each other, and the stages in the order fsai_build runs them.  The state
+// owns every array until the build returns, however it returns (device_release waits for the device); the two releases
+// before that are named where they happen (post_filter, make_operator).  ip, ix, va: device arrays, n >= 1.
+template <typename T> struct FsaiBuild {
+  rlh_fsai *const h;
+  const char *const name;                  // the entry point the messages speak for
+  const T *const va;
+  const FsaiPlan &plan;
   const int64_t n = h->n;
-  const int max_row = plan.max_row, levels = plan.levels, steps = plan.steps, step_size = plan.step_size, four = plan.four;
-  const int grow = plan.grow();
-  hipStream_t st = ctx().stream;
-  const dim3 blk(kBlock);
-  FsaiScratch w;
-  if (int rc = w.timer.start()) return rc;
-  FsaiStatus hs{};
-  CsrInput in;
-  if (int rc = checked_input(name, n, ip, ix, va, w, &hs, &in)) return rc;
-  const int64_t cap = in.cap;
-  const int64_t *ip64 = in.ip64;
-  const int32_t *ix32 = in.ix32;
-  // ---- the pattern
+  // decided once: the level pattern is a slice of A's row (fsai_count tallies, fsai_fill copies from `start` on), or
+  // one wave per row walks pat_ip / pat_ix (fsai_pattern_count, fsai_pattern_fill)
+  const bool slice = plan.levels == 1 && !(plan.prefilter > 0);
+  const hipStream_t st = ctx().stream;
+  const dim3 blk{kBlock};
   const int64_t most = (int64_t)ctx().num_cu * kSetupBlocksPerCu;
+  FsaiScratch w;                           // counts, keys, scans (w.gp: G's row pointers), the status record on the device
+  FsaiStatus hs{};                         // the status record as last fetched
+  CsrInput in;
   DevBuf<int64_t> start;
-  if (int rc = w.alloc_rows(n)) return rc;
-  if (int rc = start.alloc(n)) return rc;
-  const bool strong = plan.prefilter > 0;
-  hipLaunchKernelGGL(fsai_count, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, max_row, levels == 1 && !strong ? 1 : 0, four,
-                     grow, ip64, ix32, w.cnt, w.ka, w.kb, start, w.status);
-  hipLaunchKernelGGL((resolve_partner<int64_t, int32_t>), dim3(1), dim3(1), 0, st, n, ip64, ix32, w.status);
-  // the structure the pattern is the power of: A's own arrays, or (prefiltration) the strong lower triangle
-  const int64_t *pat_ip = ip64;
-  const int32_t *pat_ix = ix32;
-  DevBuf<double> strong_diag;
+  DevBuf<double> strong_diag;              // prefiltration: A's diagonal and the strong lower structure (a CSR)
   DevBuf<int64_t> strong_ip;
   DevBuf<int32_t> strong_ix;
-  if (strong) {
-    // ---- prefiltration: every lower entry is decided by value (counts in w.cnt, which the pattern overwrites later),
-    // the counts are scanned, the host waits once for the size and for what the checks found, and the strong lower
-    // structure is filled.  The pattern kernels of every level, 1 included, walk it in place of A.
+  const int64_t *pat_ip = nullptr;         // the structure the pattern is the power of: A's own arrays (checks) or the
+  const int32_t *pat_ix = nullptr;         // strong lower structure (strong_structure)
+  DevBuf<int32_t> gi, bin_rows;            // G's columns; the rows of the bins
+  DevBuf<T> gv;
+  Bins bins{};
+  int64_t gnnz = 0;                        // the entries of the pattern as it stands
+  DevBuf<int64_t> capacity, sp;            // enrichment: the rows' capacities, their scan, the slab of the enriched
+  DevBuf<int32_t> slab, level;             // patterns and the level patterns the rows grew from
+
+  dim3 by_row() const { return dim3(blocks_for(n, kBlock, 8192)); }
+
+  // ---- checks: the arrays as they came, then per row the diagonal and the partners (fsai_count; for a slice also the
+  // counts, the keys and where the slice begins)
+  template <typename P, typename I> int checks(const P *ip, const I *ix) {
+    if (int rc = checked_input(name, n, ip, ix, va, w, &hs, &in)) return rc;
+    if (int rc = w.alloc_rows(n)) return rc;
+    if (int rc = start.alloc(n)) return rc;
+    if (int rc = bin_rows.alloc(n)) return rc;
+    hipLaunchKernelGGL(fsai_count, by_row(), blk, 0, st, n, plan.max_row, slice ? 1 : 0, plan.four, plan.grow(), in.ip64, in.ix32,
+                       w.cnt, w.ka, w.kb, start, w.status);
+    hipLaunchKernelGGL((resolve_partner<int64_t, int32_t>), dim3(1), dim3(1), 0, st, n, in.ip64, in.ix32, w.status);
+    pat_ip = in.ip64;
+    pat_ix = in.ix32;
+    return 0;
+  }
+
+  // ---- prefiltration: every lower entry is decided by value (counts in w.cnt, which the pattern overwrites later), the
+  // counts are scanned, the host waits once for the size and for what the checks found, and the strong lower structure
+  // is filled.  The pattern kernels of every level, 1 included, walk it in place of A.
+  int strong_structure() {
     const double tau2 = plan.prefilter * plan.prefilter;
-    const unsigned grid = blocks_for(n, kBlock / kStrongLanes, most);
+    const dim3 grid(blocks_for(n, kBlock / kStrongLanes, most));
     if (int rc = strong_diag.alloc(n)) return rc;
     if (int rc = strong_ip.alloc(n + 1)) return rc;
-    hipLaunchKernelGGL(fsai_diagonal<T>, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, ip64, ix32, va, strong_diag.get());
-    hipLaunchKernelGGL((fsai_strong<T, false>), dim3(grid), blk, 0, st, n, tau2, ip64, ix32, va, (const double *)strong_diag,
+    hipLaunchKernelGGL(fsai_diagonal<T>, by_row(), blk, 0, st, n, in.ip64, in.ix32, va, strong_diag.get());
+    hipLaunchKernelGGL((fsai_strong<T, false>), grid, blk, 0, st, n, tau2, in.ip64, in.ix32, va, (const double *)strong_diag,
                        w.cnt.get(), (const int64_t *)nullptr, (int32_t *)nullptr, w.status.get());
     RLH_HIP(hipGetLastError());
     if (int rc = exclusive_scan(n, w.cnt, w.bsum, strong_ip)) return rc;
@@ -836,122 +868,156 @@ int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T 
     RLH_HIP(hipMemcpyAsync(&hs, w.status, sizeof hs, hipMemcpyDeviceToHost, st));
     RLH_HIP(hipMemcpyAsync(&members, strong_ip + n, 8, hipMemcpyDeviceToHost, st));
     RLH_HIP(hipStreamSynchronize(st));
-    if (hs.err != kNoError) return report(name, hs, cap);
+    if (hs.err != kNoError) return report(name, hs, in.cap);
     RLH_REQUIRE(members >= n && members <= in.nnz && (int64_t)hs.weak + members <= in.nnz, "%s: inconsistent row counts of the pattern", name);
     if (int rc = strong_ix.alloc(members)) return rc;
-    hipLaunchKernelGGL((fsai_strong<T, true>), dim3(grid), blk, 0, st, n, tau2, ip64, ix32, va, (const double *)strong_diag,
+    hipLaunchKernelGGL((fsai_strong<T, true>), grid, blk, 0, st, n, tau2, in.ip64, in.ix32, va, (const double *)strong_diag,
                        (int64_t *)nullptr, (const int64_t *)strong_ip, strong_ix.get(), w.status.get());
     RLH_HIP(hipGetLastError());
     pat_ip = strong_ip;
     pat_ix = strong_ix;
     h->weak = (int64_t)hs.weak;
+    return 0;
   }
-  if (levels > 1 || strong)
-    hipLaunchKernelGGL(fsai_pattern_count, dim3(blocks_for(n, kBlock / 64, most)), blk, 0, st, n, max_row, levels, four, grow, pat_ip,
-                       pat_ix, w.cnt, w.ka, w.kb, w.status);
-  int64_t gnnz = 0;
-  Bins bins{};
-  if (int rc = pattern_totals(name, n, w, cap, n, n * (int64_t)max_row, &hs, &gnnz, &bins)) return rc;
-  DevBuf<int32_t> gi, bin_rows;
-  if (int rc = gi.alloc(gnnz)) return rc;
-  if (int rc = bin_rows.alloc(n)) return rc;
-  bins.rows = bin_rows;
-  if (levels == 1 && !strong)
-    hipLaunchKernelGGL(fsai_fill, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, ix32, start, w.gp, gi, bins);
-  else
-    hipLaunchKernelGGL(fsai_pattern_fill, dim3(blocks_for(n, kBlock / 64, most)), blk, 0, st, n, max_row, levels, pat_ip, pat_ix, w.gp,
-                       gi, bins);
-  DevBuf<int64_t> capacity, sp;
-  DevBuf<int32_t> slab, level;
-  if (steps > 0) {
-    // ---- enrichment: so far the bins are those of the capacities and gi holds the level patterns.  The enriched
-    // patterns go to a slab at the scanned capacities; counts, keys and scans are then made again for the final rows.
+
+  // The counts and keys in w become a pattern (pattern_totals: one wait; its entries must lie in [lo, hi]) with a column
+  // array of its size
+  int new_columns(int64_t lo, int64_t hi) {
+    bins.rows = bin_rows;
+    if (int rc = pattern_totals(name, n, w, in.cap, lo, hi, &hs, &gnnz, &bins)) return rc;
+    return gi.alloc(gnnz);
+  }
+
+  // ... and row i of it is copied from src[src_start[i] ..): from A's own rows, from the slab of the enrichment and from
+  // that of the filter (fsai_fill, which also writes the rows of the bins)
+  int compact(const int32_t *src, const int64_t *src_start, int64_t lo, int64_t hi) {
+    if (int rc = new_columns(lo, hi)) return rc;
+    hipLaunchKernelGGL(fsai_fill, by_row(), blk, 0, st, n, src, src_start, w.gp.get(), gi.get(), bins);
+    return 0;
+  }
+
+  // ---- the level pattern: counts, scans, the columns of G and the rows of the bins (a slice: fsai_count has made the
+  // counts and keys)
+  int level_pattern() {
+    const int64_t hi = n * (int64_t)plan.max_row;
+    const dim3 grid(blocks_for(n, kBlock / 64, most));
+    if (!slice)
+      hipLaunchKernelGGL(fsai_pattern_count, grid, blk, 0, st, n, plan.max_row, plan.levels, plan.four, plan.grow(), pat_ip, pat_ix,
+                         w.cnt, w.ka, w.kb, w.status);
+    if (int rc = slice ? compact(in.ix32, start, n, hi) : new_columns(n, hi)) return rc;
+    if (!slice) hipLaunchKernelGGL(fsai_pattern_fill, grid, blk, 0, st, n, plan.max_row, plan.levels, pat_ip, pat_ix, w.gp, gi, bins);
+    h->truncated = (int64_t)hs.truncated;
+    h->longest = hs.longest;
+    return 0;
+  }
+
+  // ---- enrichment: so far the bins are those of the capacities and gi holds the level patterns.  The enriched patterns
+  // go to a slab at the scanned capacities (one wait, for their total); counts, keys and scans are then made again for
+  // the final rows and the slab is compacted.
+  int enrich() {
     if (int rc = capacity.alloc(n)) return rc;
     if (int rc = sp.alloc(n + 1)) return rc;
-    hipLaunchKernelGGL(fsai_capacity, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, max_row, grow, w.cnt, capacity);
+    hipLaunchKernelGGL(fsai_capacity, by_row(), blk, 0, st, n, plan.max_row, plan.grow(), w.cnt, capacity);
     if (int rc = exclusive_scan(n, capacity, w.bsum, sp)) return rc;
     int64_t room = 0;
     RLH_HIP(hipMemcpyAsync(&room, sp + n, 8, hipMemcpyDeviceToHost, st));
     RLH_HIP(hipStreamSynchronize(st));
-    RLH_REQUIRE(room >= gnnz && room <= n * (int64_t)max_row, "%s: inconsistent row counts of the pattern", name);
+    RLH_REQUIRE(room >= gnnz && room <= n * (int64_t)plan.max_row, "%s: inconsistent row counts of the pattern", name);
     if (int rc = slab.alloc(room)) return rc;
-    level = std::move(gi);                         // the level patterns the rows grow from
+    level = std::move(gi);                 // the level patterns the rows grow from
     for_each_bin(bins, n, [&](auto lanes, int64_t count, const int32_t *list) {
       constexpr int kLanes = decltype(lanes)::value;
-      launch_bin<T, kLanes>(fsai_enrich<T, kLanes>, count, list, max_row, steps, step_size, four, ip64, ix32, va, w.gp.get(), (const int32_t *)level,
-                            sp.get(), slab.get(), w.cnt.get(), w.ka.get(), w.kb.get(), w.status.get());
+      launch_bin<T, kLanes>(fsai_enrich<T, kLanes>, count, list, plan.max_row, plan.steps, plan.step_size, plan.four, in.ip64, in.ix32, va,
+                            w.gp.get(), (const int32_t *)level, sp.get(), slab.get(), w.cnt.get(), w.ka.get(), w.kb.get(),
+                            w.status.get());
     });
     RLH_HIP(hipGetLastError());
-    const int64_t before = gnnz;                   // (the kernels above are done with w.gp when the scans write it)
-    if (int rc = pattern_totals(name, n, w, cap, before, room, &hs, &gnnz, &bins)) return rc;
-    hs.truncated = hs.limited;
-    if (int rc = gi.alloc(gnnz)) return rc;
-    hipLaunchKernelGGL(fsai_fill, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, slab, sp, w.gp, gi, bins);
+    if (int rc = compact(slab, sp, gnnz, room)) return rc;      // (the kernels above are done with w.gp when the scans write it)
+    h->truncated = (int64_t)hs.limited;    // of an enriched build: the rows max_row held back
+    h->longest = hs.longest;
+    return 0;
   }
-  h->nnz = gnnz;
-  h->truncated = (int64_t)hs.truncated;
-  h->longest = hs.longest;
-  DevBuf<T> gv;
-  if (int rc = gv.alloc(gnnz)) return rc;
-  // ---- the rows, bin by bin (the pattern of w.gp and gi, the bins as they stand)
-  if (int rc = solve_rows<T>(name, n, bins, in, va, w.gp, gi, gv, w, &hs)) return rc;
-  if (plan.drop > 0) {
-    // ---- post-filtration: the kept columns of every row go to a slab at the row's old offset; counts, keys and scans
-    // are made again, the slab is compacted (fsai_fill again) and every row is solved once more on what is left, in
-    // the bin of its new length.  A principal sub-block of a positive definite block is positive definite.
+
+  // ---- the rows, bin by bin (the pattern of w.gp and gi, the bins as they stand): one wait
+  int solve() {
+    if (int rc = gv.alloc(gnnz)) return rc;
+    return solve_rows<T>(name, n, bins, in, va, w.gp, gi, gv, w, &hs);
+  }
+
+  // ---- post-filtration: the kept columns of every row go to a slab at the row's old offset; counts, keys and scans are
+  // made again, the slab is compacted and every row is solved once more on what is left, in the bin of its new length.
+  // A principal sub-block of a positive definite block is positive definite.  The unfiltered G and the stage's own
+  // arrays are released when the stage returns: the second solve has waited then, the stream is idle.
+  int post_filter() {
     DevBuf<double> diag;
-    DevBuf<int32_t> kept_cols, gi_kept;
-    DevBuf<T> gv_kept;
+    DevBuf<int32_t> kept_cols;
     if (int rc = diag.alloc(n)) return rc;
     if (int rc = kept_cols.alloc(gnnz)) return rc;
-    hipLaunchKernelGGL(fsai_diagonal<T>, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, ip64, ix32, va, diag.get());
-    hipLaunchKernelGGL(fsai_filter<T>, dim3(blocks_for(n, kBlock / kFilterLanes, most)), blk, 0, st, n, plan.drop * plan.drop, four,
+    hipLaunchKernelGGL(fsai_diagonal<T>, by_row(), blk, 0, st, n, in.ip64, in.ix32, va, diag.get());
+    hipLaunchKernelGGL(fsai_filter<T>, dim3(blocks_for(n, kBlock / kFilterLanes, most)), blk, 0, st, n, plan.drop * plan.drop, plan.four,
                        (const int64_t *)w.gp, (const int32_t *)gi, (const T *)gv, (const double *)diag, kept_cols.get(),
                        w.cnt.get(), w.ka.get(), w.kb.get(), w.status.get());
     RLH_HIP(hipGetLastError());
-    DevBuf<int64_t> old_gp = std::move(w.gp);      // (where the rows lie in the slab; the scans write a new w.gp)
+    const DevBuf<int64_t> old_gp = std::move(w.gp);      // (where the rows lie in the slab; the scans write a new w.gp)
+    const DevBuf<int32_t> old_gi = std::move(gi);
+    const DevBuf<T> old_gv = std::move(gv);
     if (int rc = w.gp.alloc(n + 1)) return rc;
     const int64_t before = gnnz;
-    if (int rc = pattern_totals(name, n, w, cap, n, before, &hs, &gnnz, &bins)) return rc;
+    if (int rc = compact(kept_cols, old_gp, n, before)) return rc;
     RLH_REQUIRE((int64_t)hs.removed == before - gnnz, "%s: inconsistent row counts of the pattern", name);
-    if (int rc = gi_kept.alloc(gnnz)) return rc;
-    if (int rc = gv_kept.alloc(gnnz)) return rc;
-    hipLaunchKernelGGL(fsai_fill, dim3(blocks_for(n, kBlock, 8192)), blk, 0, st, n, kept_cols, old_gp, w.gp, gi_kept, bins);
-    if (int rc = solve_rows<T>(name, n, bins, in, va, w.gp, gi_kept, gv_kept, w, &hs)) return rc;
-    gi = std::move(gi_kept);                       // (the stream is idle: nothing reads the unfiltered G any more)
-    gv = std::move(gv_kept);
-    h->nnz = gnnz;
-    h->longest = hs.kept_longest;
     h->removed = (int64_t)hs.removed;
+    h->longest = hs.kept_longest;
+    return solve();
   }
-  // ---- G and G^H as one sparse data operator (it copies the arrays: 32-bit row pointers where they can hold nnz)
-  int rc;
-  DevBuf<int32_t> gp32;
-  DevBuf<int64_t> gi64;
-  if (gnnz < INT32_MAX) {
-    if (int rc2 = gp32.alloc(n + 1)) return rc2;
-    hipLaunchKernelGGL((spd_convert_index<int64_t, int32_t>), dim3(blocks_for(n + 1, kBlock, 4096)), blk, 0, st, n + 1, w.gp, gp32);
-    RLH_HIP(hipGetLastError());
-    rc = rlh_spd_create_device(&h->spd, h->dtype, n, n, 32, gp32, gi, gv);
-  } else {
-    in.cols.reset();                  // (the set-up was the last to read the converted columns)
-    if (int rc2 = gi64.alloc(gnnz)) return rc2;
-    hipLaunchKernelGGL((spd_convert_index<int32_t, int64_t>), dim3(blocks_for(gnnz, kBlock, 8192)), blk, 0, st, gnnz, gi, gi64);
-    rc = rlh_spd_create_device(&h->spd, h->dtype, n, n, 64, w.gp, gi64, gv);
+
+  // ---- G and G^H as one sparse data operator (it copies the arrays: 32-bit row pointers where they can hold nnz).  What
+  // else the handle reports, each stage has written when it made it.
+  int make_operator() {
+    int rc;
+    DevBuf<int32_t> gp32;
+    DevBuf<int64_t> gi64;
+    if (gnnz < INT32_MAX) {
+      if (int rc2 = gp32.alloc(n + 1)) return rc2;
+      hipLaunchKernelGGL((spd_convert_index<int64_t, int32_t>), dim3(blocks_for(n + 1, kBlock, 4096)), blk, 0, st, n + 1, w.gp, gp32);
+      RLH_HIP(hipGetLastError());
+      rc = rlh_spd_create_device(&h->spd, h->dtype, n, n, 32, gp32, gi, gv);
+    } else {
+      in.cols.reset();                  // (the set-up was the last to read the converted columns)
+      if (int rc2 = gi64.alloc(gnnz)) return rc2;
+      hipLaunchKernelGGL((spd_convert_index<int32_t, int64_t>), dim3(blocks_for(gnnz, kBlock, 8192)), blk, 0, st, gnnz, gi, gi64);
+      rc = rlh_spd_create_device(&h->spd, h->dtype, n, n, 64, w.gp, gi64, gv);
+    }
+    if (rc) return rc;
+    if (int rc2 = w.timer.stop()) return rc2;   // the caller's arrays and the scratch are not referenced after the return
+    h->setup_seconds = w.timer.seconds();
+    h->nnz = gnnz;
+    return 0;
   }
-  if (rc) return rc;
-  if (int rc2 = w.timer.stop()) return rc2;   // the caller's arrays and the scratch are not referenced after the return
-  h->setup_seconds = w.timer.seconds();
-  return 0;
+};
+
+template <typename T, typename P, typename I>
+int fsai_build(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T *va, const FsaiPlan &plan) {
+  FsaiBuild<T> b{h, name, va, plan};
+  if (int rc = b.w.timer.start()) return rc;
+  if (int rc = b.checks(ip, ix)) return rc;
+  if (plan.prefilter > 0)
+    if (int rc = b.strong_structure()) return rc;
+  if (int rc = b.level_pattern()) return rc;
+  if (plan.steps > 0)
+    if (int rc = b.enrich()) return rc;
+  if (int rc = b.solve()) return rc;
+  if (plan.drop > 0)
+    if (int rc = b.post_filter()) return rc;
+  return b.make_operator();
 }
 
-template <typename P, typename I>
-int fsai_build_any(rlh_fsai *h, const char *name, const void *ip, const void *ix, const void *va, const FsaiPlan &plan) {
-  switch (h->dtype) {
-    case RLH_S: return fsai_build<float, P, I>(h, name, (const P *)ip, (const I *)ix, (const float *)va, plan);
-    case RLH_D: return fsai_build<double, P, I>(h, name, (const P *)ip, (const I *)ix, (const double *)va, plan);
-    case RLH_C: return fsai_build<c32, P, I>(h, name, (const P *)ip, (const I *)ix, (const c32 *)va, plan);
-    case RLH_Z: return fsai_build<c64, P, I>(h, name, (const P *)ip, (const I *)ix, (const c64 *)va, plan);
+// f(values as const T *) for the T of `dtype`
+template <typename F> int with_values(int dtype, const void *va, F f) {
+  switch (dtype) {
+    case RLH_S: return f((const float *)va);
+    case RLH_D: return f((const double *)va);
+    case RLH_C: return f((const c32 *)va);
+    case RLH_Z: return f((const c64 *)va);
   }
   return 1;
 }
@@ -995,19 +1061,13 @@ int fsai_update(rlh_fsai *h, const char *name, const P *ip, const I *ix, const T
 }
 
 template <typename P, typename I>
-int fsai_update_any(rlh_fsai *h, const char *name, const void *ip, const void *ix, const void *va) {
+int update_as(rlh_fsai *h, const char *name, const void *ip, const void *ix, const void *va) {
   if (h->n == 0 || !h->spd) {               // nothing to solve: a valid update
     h->update_seconds = 0;
     ++h->updates;
     return 0;
   }
-  switch (h->dtype) {
-    case RLH_S: return fsai_update<float, P, I>(h, name, (const P *)ip, (const I *)ix, (const float *)va);
-    case RLH_D: return fsai_update<double, P, I>(h, name, (const P *)ip, (const I *)ix, (const double *)va);
-    case RLH_C: return fsai_update<c32, P, I>(h, name, (const P *)ip, (const I *)ix, (const c32 *)va);
-    case RLH_Z: return fsai_update<c64, P, I>(h, name, (const P *)ip, (const I *)ix, (const c64 *)va);
-  }
-  return 1;
+  return with_values(h->dtype, va, [&](auto *v) { return fsai_update(h, name, (const P *)ip, (const I *)ix, v); });
 }
 
 constexpr int kMaxSteps = 63, kMaxStepSize = 16;
@@ -1055,8 +1115,10 @@ int create_device(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, int in
   if (int rc = check_create_args(name, ph, dtype, n, d_indptr, plan)) return rc;
   RLH_REQUIRE(index_bits == 32 || index_bits == 64, "%s: index_bits must be 32 or 64, got %d", name, index_bits);
   return make_handle(ph, dtype, n, plan, [&](rlh_fsai *h) {
-    return index_bits == 32 ? fsai_build_any<int32_t, int32_t>(h, name, d_indptr, d_indices, d_values, plan)
-                            : fsai_build_any<int64_t, int64_t>(h, name, d_indptr, d_indices, d_values, plan);
+    return with_values(dtype, d_values, [&](auto *va) {
+      return index_bits == 32 ? fsai_build(h, name, (const int32_t *)d_indptr, (const int32_t *)d_indices, va, plan)
+                              : fsai_build(h, name, (const int64_t *)d_indptr, (const int64_t *)d_indices, va, plan);
+    });
   });
 }
 
@@ -1084,7 +1146,9 @@ int create_host(const char *name, rlh_fsai_t *ph, int dtype, int64_t n, const in
   if (int rc = check_create_args(name, ph, dtype, n, indptr, plan)) return rc;
   UploadedCsr d;
   if (int rc = upload_csr(name, dtype, n, indptr, indices, values, &d)) return rc;
-  return make_handle(ph, dtype, n, plan, [&](rlh_fsai *h) { return fsai_build_any<int64_t, int32_t>(h, name, d.ip, d.ix, d.va, plan); });
+  return make_handle(ph, dtype, n, plan, [&](rlh_fsai *h) {
+    return with_values(dtype, d.va, [&](auto *va) { return fsai_build(h, name, d.ip.get(), d.ix.get(), va, plan); });
+  });
 }
 
 }  // namespace
@@ -1094,56 +1158,49 @@ using namespace rlh;
 
 extern "C" int rlh_fsai_create_device(rlh_fsai_t *ph, int dtype, int64_t n, int index_bits, const void *d_indptr,
                                       const void *d_indices, const void *d_values, int max_row) {
-  return create_device("rlh_fsai_create_device", ph, dtype, n, index_bits, d_indptr, d_indices, d_values, {max_row, 1, false, 0, 0});
+  return create_device("rlh_fsai_create_device", ph, dtype, n, index_bits, d_indptr, d_indices, d_values, FsaiPlan::of_levels(max_row, 1));
 }
 
 extern "C" int rlh_fsai_create_levels_device(rlh_fsai_t *ph, int dtype, int64_t n, int index_bits, const void *d_indptr,
                                              const void *d_indices, const void *d_values, int max_row, int levels) {
   return create_device("rlh_fsai_create_levels_device", ph, dtype, n, index_bits, d_indptr, d_indices, d_values,
-                       {max_row, levels, false, 0, 0});
+                       FsaiPlan::of_levels(max_row, levels));
 }
 
 extern "C" int rlh_fsai_create(rlh_fsai_t *ph, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
                                const void *values, int max_row) {
-  return create_host("rlh_fsai_create", ph, dtype, n, indptr, indices, values, {max_row, 1, false, 0, 0});
+  return create_host("rlh_fsai_create", ph, dtype, n, indptr, indices, values, FsaiPlan::of_levels(max_row, 1));
 }
 
 extern "C" int rlh_fsai_create_levels(rlh_fsai_t *ph, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
                                       const void *values, int max_row, int levels) {
-  return create_host("rlh_fsai_create_levels", ph, dtype, n, indptr, indices, values, {max_row, levels, false, 0, 0});
+  return create_host("rlh_fsai_create_levels", ph, dtype, n, indptr, indices, values, FsaiPlan::of_levels(max_row, levels));
 }
 
 extern "C" int rlh_fsai_create_adaptive_device(rlh_fsai_t *ph, int dtype, int64_t n, int index_bits, const void *d_indptr,
                                                const void *d_indices, const void *d_values, int max_row, int levels, int steps,
                                                int step_size) {
   return create_device("rlh_fsai_create_adaptive_device", ph, dtype, n, index_bits, d_indptr, d_indices, d_values,
-                       {max_row, levels, true, steps, step_size});
+                       FsaiPlan::of_levels(max_row, levels).enriched(steps, step_size));
 }
 
 extern "C" int rlh_fsai_create_adaptive(rlh_fsai_t *ph, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
                                         const void *values, int max_row, int levels, int steps, int step_size) {
-  return create_host("rlh_fsai_create_adaptive", ph, dtype, n, indptr, indices, values, {max_row, levels, true, steps, step_size});
-}
-
-// steps == 0: no enrichment, step_size is not looked at
-static FsaiPlan filtered_plan(int max_row, int levels, int steps, int step_size, double drop) {
-  FsaiPlan plan{max_row, levels, steps != 0, steps, steps != 0 ? step_size : 0};
-  plan.drop = drop;
-  plan.filtered = true;
-  return plan;
+  return create_host("rlh_fsai_create_adaptive", ph, dtype, n, indptr, indices, values,
+                     FsaiPlan::of_levels(max_row, levels).enriched(steps, step_size));
 }
 
 extern "C" int rlh_fsfilter_create_device(rlh_fsai_t *ph, int dtype, int64_t n, int index_bits, const void *d_indptr,
                                                const void *d_indices, const void *d_values, int max_row, int levels, int steps,
                                                int step_size, double drop) {
   return create_device("rlh_fsfilter_create_device", ph, dtype, n, index_bits, d_indptr, d_indices, d_values,
-                       filtered_plan(max_row, levels, steps, step_size, drop));
+                       FsaiPlan::of_levels(max_row, levels).enriched_unless_0(steps, step_size).filtered_by(drop));
 }
 
 extern "C" int rlh_fsfilter_create(rlh_fsai_t *ph, int dtype, int64_t n, const int64_t *indptr, const int32_t *indices,
                                         const void *values, int max_row, int levels, int steps, int step_size, double drop) {
   return create_host("rlh_fsfilter_create", ph, dtype, n, indptr, indices, values,
-                     filtered_plan(max_row, levels, steps, step_size, drop));
+                     FsaiPlan::of_levels(max_row, levels).enriched_unless_0(steps, step_size).filtered_by(drop));
 }
 
 extern "C" int rlh_fsfilter_info(rlh_fsai_t h, double *drop, int64_t *removed) {
@@ -1153,13 +1210,8 @@ extern "C" int rlh_fsfilter_info(rlh_fsai_t h, double *drop, int64_t *removed) {
   return 0;
 }
 
-// steps == 0: no enrichment; drop == 0: no post-filtration (anything else, a NaN included, is checked as a drop)
 static FsaiPlan thresholded_plan(int max_row, int levels, int steps, int step_size, double drop, double prefilter) {
-  FsaiPlan plan = filtered_plan(max_row, levels, steps, step_size, drop);
-  plan.filtered = !(drop == 0.0);
-  plan.prefilter = prefilter;
-  plan.thresholded = true;
-  return plan;
+  return FsaiPlan::of_levels(max_row, levels).enriched_unless_0(steps, step_size).filtered_unless_0(drop).thresholded_by(prefilter);
 }
 
 extern "C" int rlh_fsthreshold_create_device(rlh_fsai_t *ph, int dtype, int64_t n, int index_bits, const void *d_indptr,
@@ -1190,8 +1242,8 @@ extern "C" int rlh_fsvalues_update_device(rlh_fsai_t h, int index_bits, const vo
   RLH_REQUIRE(h != nullptr, "%s: null handle", name);
   RLH_REQUIRE(d_indptr, "%s: null indptr", name);
   RLH_REQUIRE(index_bits == 32 || index_bits == 64, "%s: index_bits must be 32 or 64, got %d", name, index_bits);
-  return index_bits == 32 ? fsai_update_any<int32_t, int32_t>(h, name, d_indptr, d_indices, d_values)
-                          : fsai_update_any<int64_t, int64_t>(h, name, d_indptr, d_indices, d_values);
+  return index_bits == 32 ? update_as<int32_t, int32_t>(h, name, d_indptr, d_indices, d_values)
+                          : update_as<int64_t, int64_t>(h, name, d_indptr, d_indices, d_values);
 }
 
 extern "C" int rlh_fsvalues_update(rlh_fsai_t h, const int64_t *indptr, const int32_t *indices, const void *values) {
@@ -1201,7 +1253,7 @@ extern "C" int rlh_fsvalues_update(rlh_fsai_t h, const int64_t *indptr, const in
   RLH_REQUIRE(indptr, "%s: null indptr", name);
   UploadedCsr d;
   if (int rc = upload_csr(name, h->dtype, h->n, indptr, indices, values, &d)) return rc;
-  return fsai_update_any<int64_t, int32_t>(h, name, d.ip, d.ix, d.va);     // (n == 0: a valid update that reads nothing)
+  return update_as<int64_t, int32_t>(h, name, d.ip, d.ix, d.va);     // (n == 0: a valid update that reads nothing)
 }
 
 extern "C" int rlh_fsvalues_info(rlh_fsai_t h, int64_t *updates, double *seconds) {

@@ -1,5 +1,5 @@
 """Post-filtration of the approximate inverse by value (rlh_fsfilter_create*, rlh_fsfilter_info,
-ApproximateInverse(drop=...)): cases shared by the CPU tier (tests/fake_fsai_filter.py) and the GPU tier.  Matrices,
+ApproximateInverse(drop=...)): cases shared by the CPU tier (tests/fake_fsai.py) and the GPU tier.  Matrices,
 helpers and the bound of the defining property (`check_row`, `beta`) come from tests/_fsai_cases.py (`base`), the level
 and adaptive patterns of the unfiltered build from the oracles of tests/_fsai_levels_cases.py (`lv`) and
 tests/_fsai_adaptive_cases.py (`ad`).

@@ -1,5 +1,5 @@
 """The approximate inverse on row-sharded blocks (rlh_fsshard_*, ShardedApproximateInverse): cases shared by the CPU tier
-(tests/fake_fsai_shard.py) and the GPU tier.  Matrices, helpers and the bound of an application come from
+(tests/fake_fsai.py) and the GPU tier.  Matrices, helpers and the bound of an application come from
 tests/_fsai_work_cases.py and tests/_fsai_cases.py.
 
 The raw-ABI cases run in ONE process without collectives: the test plays all the shards.  G is the level-1 build of the

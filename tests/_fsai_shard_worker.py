@@ -1,5 +1,5 @@
 """Worker of tests/test_fsai_shard_dist.py: launched by torch.distributed.run with the gloo backend (CPU); installs
-tests/fake_fsai_shard.py as the C-ABI library and checks ShardedApproximateInverse on real ranks, the same global data on
+tests/fake_fsai.py as the C-ABI library and checks ShardedApproximateInverse on real ranks, the same global data on
 every rank (tests/_fsai_shard_cases.py: the class, on a process group)."""
 import os
 import sys
@@ -14,8 +14,8 @@ sys.path.insert(0, HERE)
 def main():
     import torch.distributed as dist
     dist.init_process_group('gloo')
-    import fake_fsai_shard
-    fake_fsai_shard.install()
+    import fake_fsai
+    fake_fsai.install()
     import _fsai_shard_cases as cases
     from raleigh_amd.algebra.hip.dist import Comm, partition
     comm = Comm()

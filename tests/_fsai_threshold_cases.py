@@ -1,5 +1,5 @@
 """Prefiltration of the approximate inverse's pattern by value (rlh_fsthreshold_create*, rlh_fsthreshold_info,
-ApproximateInverse(prefilter=...)): cases shared by the CPU tier (tests/fake_fsai_threshold.py) and the GPU tier.
+ApproximateInverse(prefilter=...)): cases shared by the CPU tier (tests/fake_fsai.py) and the GPU tier.
 Matrices, helpers and the bound of the defining property (`check_row`, `beta`) come from tests/_fsai_cases.py (`base`),
 the banded and Laplacian matrices and the idea of the pattern oracle from tests/_fsai_levels_cases.py (`lv`), the matrix
 names and `wide_dense` from tests/_fsai_filter_cases.py (`fl`), the raw update from tests/_fsai_values_cases.py (`vl`).

@@ -1,5 +1,5 @@
 """Worker of tests/test_fsai_threshold_dist.py: launched by torch.distributed.run with the gloo backend (CPU); installs
-tests/fake_fsai_threshold.py as the C-ABI library and checks ShardedApproximateInverse(prefilter=...) on real ranks, the
+tests/fake_fsai.py as the C-ABI library and checks ShardedApproximateInverse(prefilter=...) on real ranks, the
 same global data on every rank (tests/_fsai_threshold_cases.py: row shards)."""
 import os
 import sys
@@ -14,8 +14,8 @@ sys.path.insert(0, HERE)
 def main():
     import torch.distributed as dist
     dist.init_process_group('gloo')
-    import fake_fsai_threshold
-    fake = fake_fsai_threshold.install()
+    import fake_fsai
+    fake = fake_fsai.install()
     import _fsai_shard_cases as shard_cases
     import _fsai_threshold_cases as cases
     from raleigh_amd.algebra.hip.dist import Comm, partition

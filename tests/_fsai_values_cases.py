@@ -1,5 +1,5 @@
 """New matrix values on the pattern an approximate inverse already has (rlh_fsvalues_update*, rlh_fsvalues_plan,
-rlh_fsvalues_info, ApproximateInverse.update_values): cases shared by the CPU tier (tests/fake_fsai_values.py) and the
+rlh_fsvalues_info, ApproximateInverse.update_values): cases shared by the CPU tier (tests/fake_fsai.py) and the
 GPU tier.  Matrices, helpers and the bound of the defining property (`check_row`) come from tests/_fsai_cases.py (`base`),
 the configurations and the longdouble operator (`wide_dense`) from tests/_fsai_filter_cases.py (`fl`).
 

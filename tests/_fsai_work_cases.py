@@ -1,5 +1,5 @@
 """The approximate inverse's own application (rlh_fsapply_*, ApproximateInverse(work=...)): cases shared by the CPU tier
-(tests/fake_fsai_work.py) and the GPU tier.  Matrices and helpers come from tests/_fsai_cases.py.
+(tests/fake_fsai.py) and the GPU tier.  Matrices and helpers come from tests/_fsai_cases.py.
 
 THE BOUND OF AN APPLICATION.  T: the type of X and Y; V: the stored values (G~ = G rounded once to V, which the test
 does itself: the reference is G~^H (G~ X) in longdouble, so rounding G is no error); Wt: the type of W = G~ X.  A row of

@@ -1,11 +1,11 @@
-"""CPU tier: post-filtration of the approximate inverse over tests/fake_fsai_filter.py (a NumPy stand-in for the
+"""CPU tier: post-filtration of the approximate inverse over tests/fake_fsai.py (a NumPy stand-in for the
 rlh_fsfilter_create* and rlh_fsfilter_info entry points; CPU tensors stand for device tensors): the host logic of
 ApproximateInverse(drop=...), the checks and their messages, and the mathematics of the cases in
 tests/_fsai_filter_cases.py, which the GPU tier runs on the real library."""
 
 import pytest
 
-import fake_fsai_filter
+import fake_fsai
 import fake_lib
 import _fsai_filter_cases as cases
 
@@ -16,14 +16,14 @@ NEW = ('fsfilter_create', 'fsfilter_create_device')
 
 @pytest.fixture(autouse=True)
 def fake():
-    f = fake_fsai_filter.install()
+    f = fake_fsai.install()
     yield f
     fake_lib.uninstall()
 
 
 @pytest.fixture
 def device(monkeypatch):
-    fake_fsai_filter.as_device(monkeypatch)
+    fake_fsai.as_device(monkeypatch)
     return 'cpu'
 
 

@@ -1,4 +1,4 @@
-"""CPU tier: the approximate inverse on row shards over tests/fake_fsai_shard.py (a NumPy stand-in for the
+"""CPU tier: the approximate inverse on row shards over tests/fake_fsai.py (a NumPy stand-in for the
 rlh_fsshard_* entry points with the library's rounding model, checks and messages): the cases of
 tests/_fsai_shard_cases.py, which the GPU tier asks of the real library, and the host logic of
 ShardedApproximateInverse on a one-rank gloo group (no halos: gloo has no send to self, so the two virtual ranks of a
@@ -7,7 +7,7 @@ forced run are the GPU tier's; real ranks are tests/test_fsai_shard_dist.py)."""
 import numpy as np
 import pytest
 
-import fake_fsai_shard
+import fake_fsai
 import fake_lib
 import _fsai_shard_cases as cases
 
@@ -16,7 +16,7 @@ torch = pytest.importorskip('torch')
 
 @pytest.fixture(autouse=True)
 def fake():
-    f = fake_fsai_shard.install()
+    f = fake_fsai.install()
     yield f
     fake_lib.uninstall()
 

@@ -1,5 +1,5 @@
 """Multi-process CPU tier: ShardedApproximateInverse on real ranks (gloo, world sizes 2 and 3) over
-tests/fake_fsai_shard.py: the set-up exchanges, both halo exchanges of an application and the driver."""
+tests/fake_fsai.py: the set-up exchanges, both halo exchanges of an application and the driver."""
 
 import os
 import subprocess

@@ -1,11 +1,11 @@
-"""CPU tier: prefiltration of the approximate inverse's pattern over tests/fake_fsai_threshold.py (a NumPy stand-in for
+"""CPU tier: prefiltration of the approximate inverse's pattern over tests/fake_fsai.py (a NumPy stand-in for
 the rlh_fsthreshold_create* and rlh_fsthreshold_info entry points; CPU tensors stand for device tensors): the host logic
 of ApproximateInverse(prefilter=...), the checks and their messages, and the mathematics of the cases in
 tests/_fsai_threshold_cases.py, which the GPU tier runs on the real library."""
 
 import pytest
 
-import fake_fsai_threshold
+import fake_fsai
 import fake_lib
 import _fsai_threshold_cases as cases
 
@@ -16,14 +16,14 @@ NEW = ('fsthreshold_create', 'fsthreshold_create_device')
 
 @pytest.fixture(autouse=True)
 def fake():
-    f = fake_fsai_threshold.install()
+    f = fake_fsai.install()
     yield f
     fake_lib.uninstall()
 
 
 @pytest.fixture
 def device(monkeypatch):
-    fake_fsai_threshold.as_device(monkeypatch)
+    fake_fsai.as_device(monkeypatch)
     return 'cpu'
 
 

@@ -1,4 +1,4 @@
-"""CPU tier: ShardedApproximateInverse(prefilter=...) over tests/fake_fsai_threshold.py, on two real ranks (gloo; the
+"""CPU tier: ShardedApproximateInverse(prefilter=...) over tests/fake_fsai.py, on two real ranks (gloo; the
 worker is tests/_fsai_threshold_worker.py) and on one rank in this process."""
 
 import os
@@ -8,7 +8,7 @@ import sys
 import numpy as np
 import pytest
 
-import fake_fsai_threshold
+import fake_fsai
 import fake_lib
 import _fsai_shard_cases as shard_cases
 import _fsai_threshold_cases as cases
@@ -32,7 +32,7 @@ def test_sharded_prefilter_on_two_ranks():
 
 @pytest.fixture
 def fake():
-    f = fake_fsai_threshold.install()
+    f = fake_fsai.install()
     yield f
     fake_lib.uninstall()
 

@@ -1,11 +1,11 @@
-"""CPU tier: new matrix values on the kept pattern of an approximate inverse over tests/fake_fsai_values.py (a NumPy
+"""CPU tier: new matrix values on the kept pattern of an approximate inverse over tests/fake_fsai.py (a NumPy
 stand-in for the rlh_fsvalues_* entry points; CPU tensors stand for device tensors): the host logic of
 ApproximateInverse.update_values, the checks, their order and messages, and the mathematics of the cases in
 tests/_fsai_values_cases.py, which the GPU tier runs on the real library."""
 
 import pytest
 
-import fake_fsai_values
+import fake_fsai
 import fake_lib
 import _fsai_values_cases as cases
 
@@ -14,14 +14,14 @@ torch = pytest.importorskip('torch')
 
 @pytest.fixture(autouse=True)
 def fake():
-    f = fake_fsai_values.install()
+    f = fake_fsai.install()
     yield f
     fake_lib.uninstall()
 
 
 @pytest.fixture
 def device(monkeypatch):
-    fake_fsai_values.as_device(monkeypatch)
+    fake_fsai.as_device(monkeypatch)
     return 'cpu'
 
 

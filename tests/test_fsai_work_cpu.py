@@ -1,10 +1,10 @@
-"""CPU tier: the approximate inverse's own application over tests/fake_fsai_work.py (a NumPy stand-in for the
+"""CPU tier: the approximate inverse's own application over tests/fake_fsai.py (a NumPy stand-in for the
 rlh_fsapply_* entry points with the library's rounding model): the host logic of ApproximateInverse(work=...), the
 refusals and their messages, and the bounds of tests/_fsai_work_cases.py, which the GPU tier asks of the real library."""
 
 import pytest
 
-import fake_fsai_work
+import fake_fsai
 import fake_lib
 import _fsai_work_cases as cases
 
@@ -13,14 +13,14 @@ torch = pytest.importorskip('torch')
 
 @pytest.fixture(autouse=True)
 def fake():
-    f = fake_fsai_work.install()
+    f = fake_fsai.install()
     yield f
     fake_lib.uninstall()
 
 
 @pytest.fixture
 def device(monkeypatch):
-    fake_fsai_work.as_device(monkeypatch)
+    fake_fsai.as_device(monkeypatch)
     return 'cpu'
 
 
