@@ -240,7 +240,10 @@ int rlh_csr_stacks(rlh_csr_t h, int64_t *stacks, double *staged_per_row, double 
 int rlh_csr_bf16_ready(rlh_csr_t h, int64_t n_own, int64_t ldh, int *ok);
 /* Columns [0, n_own) are read from X, columns [n_own, n_cols) from the halo block
  * H (row c - n_own), which holds the off-shard rows received from other ranks;
- * single GPU: n_own = n_cols, H = NULL. */
+ * single GPU: n_own = n_cols, H = NULL.  A row with at least one stored entry reads only the columns it stores (the
+ * layouts' padding slots point at the row's own first column), so a non-finite element of X reaches only the rows that
+ * reference it.  A row without entries is +0 for finite X; its padding points at the first column its block stages
+ * (column 0 in the sliced layout), and the row is NaN where that element is not finite. */
 int rlh_spmm(rlh_csr_t h, int64_t m, const void *X, int64_t ldx, int64_t n_own,
              const void *H, int64_t ldh, void *Y, int64_t ldy);
 /* One step of the Chebyshev semi-iteration (three-term form) fused with the operator
@@ -261,6 +264,17 @@ int rlh_spmm_part(rlh_csr_t h, int part, int64_t m, const void *X, int64_t ldx, 
 int rlh_spmm_cheb_part(rlh_csr_t h, int part, int64_t m, const void *Y, int64_t ldy, int64_t n_own,
                        const void *H, int64_t ldh, void *P, int64_t ldp, const void *B, int64_t ldb,
                        double cy, double cp, double cb);
+/* What the last rlh_spmm* / rlh_spmm_cheb* call of the process launched (diagnostic; the tests' way of knowing which
+ * kernel ran), as text in buf[0 .. len): the kernel and its template parameters, the grid and the schedule length --
+ *   sell jt=J tt=T tpb=W cheb=0|1       sliced ELL             well epl=E cheb=0|1               1024-row windowed
+ *   stack reg                           stacks, register-staged stack dma pat|vals dtab|idx cheb=0|1   stacks, LDS-DMA ring
+ *   wide nv=N vs=V k=K vec|elem cheb=0|1                       256-row interleaved
+ *   well bf16 / stack bf16 vps=V pat|vals dtab|idx / wide bf16 nv=N vs=V k=K vec|elem     the bfloat16 step
+ * followed by " grid=G len=L" -- or "none" when the call had nothing to launch (m = 0, no rows, an empty part).  The record
+ * is written where the launch is made, not derived from the dispatch rules.  ONE record per process, written without
+ * any synchronisation by every product call: a diagnostic for a single calling thread (the tests), not thread-safe and
+ * not something to build on. */
+int rlh_spmm_last_launch(char *buf, int64_t len);
 /* bfloat16 storage for the device polynomial preconditioner (not in the reference).  A bf16 block
  * is a column-major array of 16-bit words, leading dimension in elements (a multiple of 8), base
  * 16-byte aligned.  pack: Y16 = bf16(scale * X) (round to nearest even) from a float32 / float64

@@ -77,6 +77,7 @@ SIGNATURES = {
     'rlh_spmm_part': [_p, _int, _i64, _p, _i64, _i64, _p, _i64, _p, _i64],
     'rlh_spmm_cheb_part': [_p, _int, _i64, _p, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, ctypes.c_double,
                            ctypes.c_double, ctypes.c_double],
+    'rlh_spmm_last_launch': [ctypes.c_char_p, _i64],
     'rlh_bf16_pack': [_int, _i64, _i64, _p, _i64, ctypes.c_double, _p, _i64],
     'rlh_bf16_unpack': [_int, _i64, _i64, _p, _i64, _p, _i64],
     'rlh_spmm_cheb_bf16': [_p, _i64, _p, _i64, _p, _i64, _p, _i64, ctypes.c_double, ctypes.c_double, ctypes.c_double],

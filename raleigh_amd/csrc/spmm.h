@@ -186,6 +186,25 @@ struct ChebArgs {
   double cy, cp, cb;
 };
 
+// ---- what the last rlh_spmm* / rlh_spmm_cheb* call of the process launched (rlh_spmm_last_launch, diagnostic).  The entry
+// points clear the record, the launch sites fill it in next to the launch they make: a few host stores per call, the
+// text is formatted when it is asked for.  `what` is a printf format of up to four ints (kernel and template parameters).
+// One unsynchronised record per process: for a single calling thread, not thread-safe.
+struct LaunchNote {
+  const char *what = nullptr;            // nullptr: nothing was launched
+  int v[4] = {0, 0, 0, 0};
+  int grid = 0;                          // workgroups
+  int64_t len = 0;                       // schedule positions walked by the grid (sliced layout: slices)
+};
+LaunchNote &launch_note();               // (spmm.hip)
+static inline void note_launch(const char *what, int a, int b, int c, int d, int64_t grid, int64_t len) {
+  LaunchNote &n = launch_note();
+  n.what = what;
+  n.v[0] = a; n.v[1] = b; n.v[2] = c; n.v[3] = d;
+  n.grid = (int)grid;
+  n.len = len;
+}
+
 // ---- the 1024-row windowed layout and its stacks (kernels: spmm.hip; host builder: spmm_build.hip)
 constexpr int kWellRows = 1024;
 template <typename T> struct WellCfg { static constexpr int SMAX = sizeof(T) >= 16 ? 4 : 8; };   // <= 64 KiB per buffer

@@ -122,6 +122,11 @@ __global__ __launch_bounds__(256, (JT * TT >= 64 ? 1 : 2)) void sell_spmm_kernel
   }
 }
 
+LaunchNote &launch_note() {
+  static LaunchNote note;
+  return note;
+}
+
 template <typename T, int JT, int TT>
 static int launch_spmm_t(const rlh_csr *h, int64_t m, const T *X, int64_t ldx, int64_t n_own, const T *H, int64_t ldh,
                        T *Y, int64_t ldy, const ChebArgs<T> *cheb) {
@@ -147,14 +152,18 @@ static int launch_spmm_t(const rlh_csr *h, int64_t m, const T *X, int64_t ldx, i
   if (nb > need) nb = need;
   nb = (nb + 7) / 8 * 8;
   if (cheb) {
-    if constexpr (JT < 32)         // (32 accumulators + the fused epilogue spill: the fused step takes tiles of 16)
+    if constexpr (JT < 32) {       // (32 accumulators + the fused epilogue spill: the fused step takes tiles of 16)
       hipLaunchKernelGGL((sell_spmm_kernel<T, JT, TT, true>), dim3((unsigned)nb), dim3(256), 0, c.stream, h->slice_ptr,
                          h->cols, (const T *)h->vals, h->n_rows, h->n_slices, X, ldx, n_own, H, ldh, Y, ldy, (int)m,
                          chunk < 1 ? 1 : chunk, ntiles, tiles_per_block, *cheb);
-  } else
+      note_launch("sell jt=%d tt=%d tpb=%d cheb=1", JT, TT, tiles_per_block, 0, nb, h->n_slices);
+    }
+  } else {
     hipLaunchKernelGGL((sell_spmm_kernel<T, JT, TT, false>), dim3((unsigned)nb), dim3(256), 0, c.stream, h->slice_ptr,
                        h->cols, (const T *)h->vals, h->n_rows, h->n_slices, X, ldx, n_own, H, ldh, Y, ldy, (int)m,
                        chunk < 1 ? 1 : chunk, ntiles, tiles_per_block, ChebArgs<T>{});
+    note_launch("sell jt=%d tt=%d tpb=%d cheb=0", JT, TT, tiles_per_block, 0, nb, h->n_slices);
+  }
   RLH_HIP(hipGetLastError());
   return 0;
 }
@@ -190,7 +199,8 @@ static int launch_spmm(const rlh_csr *h, int64_t m, const T *X, int64_t ldx, int
 // entry (7x), and the seven reads per row come out of the LDS.
 // (WellCfg and the entry storage of a block, well_val_index / well_idx_index: spmm.h, shared with the host builder)
 // the row's WMAX values and positions (the host pads every row to WMAX slots: value 0 at the position of
-// the row's own first entry, so a padding slot never touches a column the row does not reference)
+// the row's own first entry, so a padding slot of a row with at least one entry never touches a column the row does
+// not reference; an empty row's slots take position 0 of the image)
 template <typename T, int WMAX>
 __device__ __forceinline__ void well_load_entries(const T *__restrict__ vals, const uint16_t *__restrict__ idx,
                                                   int64_t eoff, int tid, int width, T (&v)[WMAX], unsigned (&pos)[WMAX]) {
@@ -1070,6 +1080,7 @@ static int launch_well_we(const rlh_csr *h, int part, int64_t m, const T *X, int
                        h->well_meta, h->well_gsrc, h->well_idx, (const T *)h->well_vals, h->n_rows, h->n_cols,
                        sched, sched_len, X, ldx, n_own, H, ldh, Y, ldy, (int)m,
                        cps_cap < 1 ? 1 : cps_cap, ChebArgs<T>{});
+  note_launch(cheb ? "well epl=%d cheb=1" : "well epl=%d cheb=0", EPL, 0, 0, 0, nb, sched_len);
   RLH_HIP(hipGetLastError());
   return 0;
 }
@@ -1317,6 +1328,9 @@ static int launch_stack_dma(const rlh_csr *h, const int32_t *pat, const int32_t 
                      ctx().stream, h->stk_meta, h->stk_member, h->stk_gsrc, h->stk_idx,
                      pat ? (const T *)h->stk_table : (const T *)h->stk_vals, pat, pat ? h->stk_dtab : nullptr, h->n_rows,
                      sched, sched_len, X, ldx, n_own, H, ldh, Y, ldy, (int)m, cheb);
+  const uint16_t *dtab = h->stk_dtab;
+  note_launch(!pat ? "stack dma vals idx cheb=%d" : dtab ? "stack dma pat dtab cheb=%d" : "stack dma pat idx cheb=%d",
+              CHEB ? 1 : 0, 0, 0, 0, grid, sched_len);
   RLH_HIP(hipGetLastError());
   return 0;
 }
@@ -1355,6 +1369,7 @@ static int launch_stack(const rlh_csr *h, int part, int64_t m, const T *X, int64
     hipLaunchKernelGGL((well_stack_kernel<T, kStkR>), dim3((unsigned)grid), dim3(1024), 2 * kStkBufBytes, c.stream,
                        h->stk_meta, h->stk_member, h->stk_gsrc, h->stk_idx, (const T *)h->stk_vals, h->n_rows, sched,
                        sched_len, X, ldx, Y, ldy, (int)m, cps_cap < 1 ? 1 : cps_cap);
+    note_launch("stack reg", 0, 0, 0, 0, grid, sched_len);
     RLH_HIP(hipGetLastError());
   }
   return 0;
@@ -1551,10 +1566,26 @@ static int launch_stack_cheb_bf16(rlh_csr *h, int part, int64_t m, const unsigne
                      h->stk_meta, h->stk_member, h->stk_gsrc, h->stk_idx,
                      pat ? (const float *)h->stk_table : (const float *)h->stk_vals, pat, pat ? h->stk_dtab : nullptr,
                      h->n_rows, sched, sched_len, Y, ldy, n_own, H, ldh, P, ldp, B, ldb, (int)m, cy, cp, cb);
+  const uint16_t *dtab = h->stk_dtab;
+  note_launch(!pat ? "stack bf16 vps=%d vals idx" : dtab ? "stack bf16 vps=%d pat dtab" : "stack bf16 vps=%d pat idx", VPS, 0, 0, 0,
+              grid, sched_len);
   RLH_HIP(hipGetLastError());
   return 0;
 }
 extern "C" {
+
+int rlh_spmm_last_launch(char *buf, int64_t len) {
+  RLH_REQUIRE(buf != nullptr && len > 0, "rlh_spmm_last_launch: no buffer");
+  const LaunchNote &n = launch_note();
+  if (n.what == nullptr) {
+    snprintf(buf, (size_t)len, "none");
+    return 0;
+  }
+  char kernel[96];
+  snprintf(kernel, sizeof kernel, n.what, n.v[0], n.v[1], n.v[2], n.v[3]);
+  snprintf(buf, (size_t)len, "%s grid=%d len=%lld", kernel, n.grid, (long long)n.len);
+  return 0;
+}
 
 int rlh_csr_layout(rlh_csr_t h, int *layout, int64_t *stored, double *staged_per_slot) {
   RLH_REQUIRE(h != nullptr, "rlh_csr_layout: null handle");
@@ -1580,6 +1611,7 @@ int rlh_csr_bf16_ready(rlh_csr_t h, int64_t n_own, int64_t ldh, int *ok) {
 
 int rlh_spmm_part(rlh_csr_t h, int part, int64_t m, const void *X, int64_t ldx, int64_t n_own, const void *H,
                   int64_t ldh, void *Y, int64_t ldy) {
+  launch_note().what = nullptr;
   if (int rc = require_ready()) return rc;
   RLH_REQUIRE(h != nullptr, "rlh_spmm: null handle");
   RLH_REQUIRE(part >= 0 && part <= 2, "rlh_spmm: part must be 0 (all rows), 1 (interior) or 2 (boundary)");
@@ -1607,6 +1639,7 @@ int rlh_spmm(rlh_csr_t h, int64_t m, const void *X, int64_t ldx, int64_t n_own, 
 
 int rlh_spmm_cheb_part(rlh_csr_t h, int part, int64_t m, const void *Y, int64_t ldy, int64_t n_own, const void *H,
                        int64_t ldh, void *P, int64_t ldp, const void *B, int64_t ldb, double cy, double cp, double cb) {
+  launch_note().what = nullptr;
   if (int rc = require_ready()) return rc;
   RLH_REQUIRE(h != nullptr, "rlh_spmm_cheb: null handle");
   RLH_REQUIRE(part >= 0 && part <= 2, "rlh_spmm_cheb: part must be 0 (all rows), 1 (interior) or 2 (boundary)");
@@ -1635,6 +1668,7 @@ int rlh_spmm_cheb(rlh_csr_t h, int64_t m, const void *Y, int64_t ldy, int64_t n_
 int rlh_spmm_cheb_bf16_part(rlh_csr_t h, int part, int64_t m, const void *Y16, int64_t ldy, int64_t n_own,
                             const void *H16, int64_t ldh, void *P16, int64_t ldp, const void *B16, int64_t ldb,
                             double cy, double cp, double cb) {
+  launch_note().what = nullptr;
   if (int rc = require_ready()) return rc;
   RLH_REQUIRE(h != nullptr, "rlh_spmm_cheb_bf16: null handle");
   RLH_REQUIRE(part >= 0 && part <= 2, "rlh_spmm_cheb_bf16: part must be 0 (all rows), 1 (interior) or 2 (boundary)");
@@ -1678,6 +1712,7 @@ int rlh_spmm_cheb_bf16_part(rlh_csr_t h, int part, int64_t m, const void *Y16, i
                      n_own, H, ldh, P, ldp, B, ldb, (int)m, (float)cy, (float)cp, (float)cb)
   RLH_BF_LAUNCH(8);
 #undef RLH_BF_LAUNCH
+  note_launch("well bf16", 0, 0, 0, 0, nb, sched_len);
   RLH_HIP(hipGetLastError());
   return 0;
 }

@@ -27,7 +27,8 @@ static int csr_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices, 
     for (int l = 0; l < 64; ++l) {
       const int64_t r = s * 64 + l;
       const int64_t b = r < n ? indptr[r] : 0, len = r < n ? indptr[r + 1] - b : 0;
-      // padding entries carry value 0 and a harmless in-range column (the row's first, else 0)
+      // padding entries carry value 0 and an in-range column: the row's first, so that a row with at least one entry
+      // never touches a foreign column; an empty row has none and takes column 0 (0 * x[0]: NaN if x[0] is not finite)
       const int32_t padcol = len > 0 ? indices[b] : 0;
       for (int64_t t = 0; t < w; ++t) {
         const int64_t e = sp[s] + t * 64 + l;
@@ -48,7 +49,9 @@ static int csr_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices, 
 }
 
 // The 8 entry slots of `row` (>= n: no such row) as thread l of the block or stack member whose slots start at eoff; padding slots carry
-// value 0 and the position of the row's own first entry, so that they only ever touch a column the row references (0 * Inf of a foreign column would be NaN)
+// value 0 and the position of the row's own first entry, so that in a row with at least one entry they only ever touch a column the row references
+// (0 * Inf of a foreign column would be NaN).  An EMPTY row has no column of its own: its slots take position 0 of the staged image, so the row is +0
+// for finite vectors and NaN where the element at that position is not finite (pinned by the tests; a select in the kernels' store is not worth that case)
 template <typename T>
 static inline void fill_row_slots(const std::vector<Win> &ws, const int64_t *indptr, const int32_t *indices, const T *values, int64_t row,
                                   int64_t n, int64_t eoff, int l, uint16_t *idx, T *vals) {

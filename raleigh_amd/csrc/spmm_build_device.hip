@@ -21,7 +21,7 @@
 //   wide_fill      positions and values in the storage order of wide_build (spmm_wide_build.hip)
 // A window here is a run of referenced 16-aligned groups, not find_windows_of's hole-bridging merge: windows decide
 // staging positions, not sums.  Slot order (a row's stored order), padding slots (value 0, position of the row's
-// first entry), rows past the end and the pairing rule are those of wide_build: they decide result bits.
+// first entry in rows with at least one entry; position / column 0 in an empty row, which is then 0 * x[there]), rows past the end and the pairing rule are those of wide_build: they decide result bits.
 //
 // mirror_upper: the value of an entry (i, j), j < i, is the conjugate of the stored (j, i), found by binary search
 // in row j inside the fill kernels (no second copy of the values).

@@ -314,6 +314,7 @@ static int wide_launch_nv(rlh_csr *h, int part, int64_t m, const T *X, int64_t l
     hipLaunchKernelGGL((wide_spmm_kernel<T, NV, VS, true, K>), dim3((unsigned)grid), dim3(256 / K * VS), lds, c.stream, a);
   else
     hipLaunchKernelGGL((wide_spmm_kernel<T, NV, VS, false, K>), dim3((unsigned)grid), dim3(256 / K * VS), lds, c.stream, a);
+  note_launch(a.vec ? "wide nv=%d vs=%d k=%d vec cheb=%d" : "wide nv=%d vs=%d k=%d elem cheb=%d", NV, VS, K, cheb ? 1 : 0, grid, sched_len);
   RLH_HIP(hipGetLastError());
   return 0;
 }

@@ -307,6 +307,7 @@ static int wide_bf16_launch(rlh_csr *h, int part, WideBfArgs &a) {
   if (int rc = wide_sched(h, c.num_cu * per_cu, part, a.n_own, &a.sched, &a.sched_len, &grid)) return rc;
   if (a.sched_len == 0 || grid == 0) return 0;
   hipLaunchKernelGGL((wide_cheb_bf16_kernel<NV, VS, K>), dim3((unsigned)grid), dim3(256 / K * VS), lds, c.stream, a);
+  note_launch(a.vec ? "wide bf16 nv=%d vs=%d k=%d vec" : "wide bf16 nv=%d vs=%d k=%d elem", NV, VS, K, 0, grid, a.sched_len);
   RLH_HIP(hipGetLastError());
   return 0;
 }

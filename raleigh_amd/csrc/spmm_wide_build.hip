@@ -84,8 +84,9 @@ int wide_build(rlh_csr *h, const int64_t *indptr, const int32_t *indices, const 
       const int64_t rp_ = r < n ? r : (K > 1 && r - lk < n ? r - lk : -1);
       const int64_t p = rp_ >= 0 ? indptr[rp_] : 0, len = rp_ >= 0 ? indptr[rp_ + 1] - p : 0;
       const bool real_row = r < n;
-      // padding slots carry value 0 and the position of the row's own first entry, so that they
-      // only ever touch a column the row references (0 * Inf of a foreign column would be NaN)
+      // padding slots carry value 0 and the position of the row's own first entry, so that in rows with at
+      // least one entry they only ever touch a column the row references (0 * Inf of a foreign column would be
+      // NaN); an empty row has no such column and takes position 0 of the image: +0 for finite vectors only
       const uint16_t padpos = len > 0 ? (uint16_t)staged_position(ws, indices[p]) : 0;
       for (int t = 0; t < meta[b].nchunks * 8; ++t) {
         const int64_t q = meta[b].eoff + t / 8;

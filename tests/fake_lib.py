@@ -605,6 +605,12 @@ class FakeLib:
         ctypes.cast(b, ctypes.POINTER(ctypes.c_double))[0] = 0.0
         return 0
 
+    def rlh_spmm_last_launch(self, buf, length):
+        # (no kernels here: the stand-in answers `fake` whatever the call was)
+        dst = ctypes.addressof(buf) if isinstance(buf, ctypes.Array) else _addr(buf)
+        ctypes.memmove(dst, b'fake\0', min(int(length), 5))
+        return 0
+
     def _rows_of_part(self, c, part, n_own):
         """Row mask of rlh_spmm_part (granularity here: single rows; the library uses 1024-row blocks)."""
         nr = c.mat.shape[0]
