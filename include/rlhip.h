@@ -672,7 +672,7 @@ int rlh_fsapply_destroy(rlh_fsapply_t p);
  * rlh_fsvalues_plan: refills the values of both layouts of a plan made from that handle from the handle's current
  * arrays, rounded to the plan's V as at creation; W and the layout's structure stay.  A plan that is not refilled
  * keeps applying the old values.  Refused, with a message naming the entry point, when n, the dtype, the entries or
- * the row lengths of plan and handle do not match.  (Row-shard plans have no such call.)
+ * the row lengths of plan and handle do not match.  (Row-shard plans are refilled by rlh_shardvalues_refill, below.)
  * rlh_fsvalues_info: the successful updates of the handle and the device seconds of the last one (events). */
 int rlh_fsvalues_update_device(rlh_fsai_t h, int index_bits, const void *d_indptr, const void *d_indices,
                                const void *d_values);
@@ -718,6 +718,34 @@ int rlh_fsshard_second(rlh_fsshard_t p, int64_t m, void *Y, int64_t ldy);
 int rlh_fsshard_info(rlh_fsshard_t p, int *work, int64_t *stored_slots, int64_t *tail_entries, int64_t *device_bytes,
                      int64_t *w_row_bytes);
 int rlh_fsshard_destroy(rlh_fsshard_t p);
+
+/* ---- new matrix values on a ROW SHARD: a row-shard plan refilled from the builder handle h that made the shard's rows
+ *      of G (the build on the shard's extended block: the rows of lower ranks its rows reference, then its own rows
+ *      from `first_row` on) after rlh_fsvalues_update* has given that handle new values on its kept pattern.  Nothing
+ *      but a status record visits the host.  Positions count entries from the first entry of row first_row of the
+ *      handle's G, indptr[first_row].
+ * rlh_shardvalues_pack: d_out[i] = the handle's value of G at entry indptr[first_row] + d_pos[i], i < count, in the
+ * handle's type: the values that lower ranks own as columns, in the order the caller's position list gives.  d_pos:
+ * DEVICE int64.  A position outside the entries of the rows first_row .. n is not followed: its value arrives as zero
+ * (the contract of rlh_fsshard_pack).  Read-only on the handle; asynchronous on the library stream.
+ * rlh_shardvalues_refill: the rows first_row .. n of the handle's G must be the plan's G_loc entry for entry and in the
+ * same order (the plan keeps its own column numbering).  Entry k of GH_loc, in the CSR order given to
+ * rlh_fsshard_create, becomes the conjugate of the handle's entry d_src[k] (a position as above) where d_src[k] >= 0,
+ * and of d_recv[-1 - d_src[k]] otherwise; d_src: DEVICE int64, one per entry of GH_loc; d_recv: n_recv values of the
+ * handle's type in DEVICE memory (what rlh_shardvalues_pack made on the higher ranks; may be null iff n_recv == 0).  Both
+ * layouts get values only, rounded once to the plan's V as at creation; columns, slots, tails and W are not touched.
+ * The row pointers of GH_loc are not kept by the plan: they are rebuilt from the layout's row lengths in scratch.
+ * Before any write: null arguments, the dtype of plan and handle, n - first_row against the plan's own rows, the
+ * entries of those rows against the plan's G_loc, every row length, and every d_src[k] in [-n_recv, entries) -- a
+ * violation returns non-zero with a message that names the entry point and the smallest offending row or entry, and
+ * the plan applies the bits it applied before.  The scratch lives for the call only: rlh_device_live returns to its
+ * level.  A plan without own rows is a valid refill that does nothing.  Synchronises for the status, and when the
+ * values are in (nothing of the caller's is referenced after the return).
+ * rlh_shardvalues_info: the successful refills of the plan and the device seconds of the last one (events). */
+int rlh_shardvalues_pack(rlh_fsai_t h, int64_t first_row, int64_t count, const int64_t *d_pos, void *d_out);
+int rlh_shardvalues_refill(rlh_fsshard_t p, rlh_fsai_t h, int64_t first_row, const int64_t *d_src, int64_t n_recv,
+                           const void *d_recv);
+int rlh_shardvalues_info(rlh_fsshard_t p, int64_t *updates, double *seconds);
 
 /* ---- profiling aid: HIP-event time of the last `count` kernels ---- */
 int rlh_timer_start(void);

@@ -155,6 +155,9 @@ SIGNATURES = {
     'rlh_fsshard_info': [_p, ctypes.POINTER(_int), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                          ctypes.POINTER(_i64)],
     'rlh_fsshard_destroy': [_p],
+    'rlh_shardvalues_pack': [_p, _i64, _i64, _p, _p],
+    'rlh_shardvalues_refill': [_p, _p, _i64, _p, _i64, _p],
+    'rlh_shardvalues_info': [_p, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)],
     'rlh_timer_start': [],
     'rlh_timer_stop': [ctypes.POINTER(ctypes.c_float)],
 }

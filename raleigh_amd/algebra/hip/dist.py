@@ -679,12 +679,26 @@ class ShardedApproximateInverse:
     columns from the cut on W-halo columns for the rows of G^H below it, and both exchanges run as sends to self.
 
     nnz, longest_row and fill are global (one all-reduce at set-up); dropped_entries covers this rank's rows;
-    setup_seconds is the host wall time of the whole set-up on this rank."""
+    setup_seconds is the host wall time of the whole set-up on this rank.
+
+    ``updatable=True`` (both constructors) keeps what a new matrix on the same pattern needs: the builder on A[E, E]
+    with its handle, H and E, and in device memory the positions of the entries sent to every lower rank (in the order
+    set-up sent them) and the source of every entry of GH_loc -- an own entry of G or a place in the messages of the
+    higher ranks.  `update_values(matrix)` (the same global matrix on every rank) and `update_local_rows(rows)` (this
+    rank's rows) are then collective calls that solve every row again on its kept pattern and refill the plan's two
+    layouts in place (rlh_shardvalues_*), see `update_local_rows`; `updates` counts the successful ones and
+    `update_seconds` is the host wall time of the last; `device_bytes()` includes the builder and those arrays.  Where
+    the pattern came from `levels` alone and the structure of the matrix is unchanged the result is the object a fresh
+    construction on the same partition gives, bit for bit; where it was chosen by value (`steps`, `drop`, `prefilter`) it
+    is the Kaporin minimiser for the new matrix on the pattern chosen for the old one.  ``updatable=False`` (the
+    default) frees the builder after set-up and is the object it always was: an update then raises RuntimeError.  With
+    one rank and forced collectives the entries of the rows from the virtual cut on whose columns lie below it take
+    the route of a lower rank's entries: packed, sent to self, received."""
 
     WORK = WORK
 
     def __init__(self, matrix, comm, offsets=None, max_row=64, levels=1, steps=0, step_size=1, work='native', drop=0.0,
-                 prefilter=0.0):
+                 prefilter=0.0, updatable=False):
         self._plan = None
         check_work(work, matrix.dtype)
         full = full_from_upper(matrix)
@@ -692,11 +706,12 @@ class ShardedApproximateInverse:
         off = partition(n, comm.size) if offsets is None else offsets
         r0, r1 = int(off[comm.rank]), int(off[comm.rank + 1])
         self._setup(scs.csr_matrix(full[r0:r1, :]), r0, n, comm, off, lambda ids: scs.csr_matrix(full[ids, :]),
-                    dict(max_row=max_row, levels=levels, steps=steps, step_size=step_size, drop=drop, prefilter=prefilter), work)
+                    dict(max_row=max_row, levels=levels, steps=steps, step_size=step_size, drop=drop, prefilter=prefilter), work,
+                    updatable)
 
     @classmethod
     def from_local_rows(cls, rows, row0, n, comm, offsets, max_row=64, levels=1, steps=0, step_size=1, work='native',
-                        drop=0.0, prefilter=0.0):
+                        drop=0.0, prefilter=0.0, updatable=False):
         """From this rank's rows [row0, row0 + rows.shape[0]) of the FULL (both triangles) matrix with global column
         indices; the rows of lower ranks that the build needs come from their owners."""
         self = cls.__new__(cls)
@@ -704,29 +719,45 @@ class ShardedApproximateInverse:
         rows = scs.csr_matrix(rows)
         check_work(work, rows.dtype)
         assert rows.shape[1] == n and row0 == int(offsets[comm.rank])
-
-        def rows_of(ids):
-            # two rounds of object collectives: who needs which rows, then the rows themselves
-            owner = np.searchsorted(offsets, ids, side='right') - 1
-            ask = {int(p): ids[owner == p] for p in np.unique(owner)}
-            asks, reply = [None] * comm.size, {}
-            comm.dist.all_gather_object(asks, ask, group=comm.group)
-            for q in range(comm.size):
-                if asks[q] and comm.rank in asks[q]:
-                    sub = scs.csr_matrix(rows[asks[q][comm.rank] - row0, :])
-                    reply[q] = (sub.indptr, sub.indices, sub.data)
-            replies = [None] * comm.size
-            comm.dist.all_gather_object(replies, reply, group=comm.group)
-            parts = []
-            for p in sorted(ask):                              # ascending owner: ascending rows
-                ip, ix, va = replies[p][comm.rank]
-                parts.append(scs.csr_matrix((va, ix, ip), shape=(len(ask[p]), n)))
-            return scs.vstack(parts, format='csr') if parts else scs.csr_matrix((0, n), dtype=rows.dtype)
-        self._setup(rows, row0, n, comm, offsets, rows_of,
-                    dict(max_row=max_row, levels=levels, steps=steps, step_size=step_size, drop=drop, prefilter=prefilter), work)
+        self._setup(rows, row0, n, comm, offsets, lambda ids: cls._rows_from_owners(comm, offsets, rows, row0, n, ids),
+                    dict(max_row=max_row, levels=levels, steps=steps, step_size=step_size, drop=drop, prefilter=prefilter), work,
+                    updatable)
         return self
 
-    def _setup(self, loc, r0, n, comm, off, rows_of, build, work):
+    @staticmethod
+    def _rows_from_owners(comm, offsets, rows, row0, n, ids):
+        """The rows `ids` (global, ascending) of the matrix whose rows from row0 on this rank holds as `rows`, from their
+        owners: two rounds of object collectives -- who needs which rows, then the rows themselves."""
+        owner = np.searchsorted(offsets, ids, side='right') - 1
+        ask = {int(p): ids[owner == p] for p in np.unique(owner)}
+        asks, reply = [None] * comm.size, {}
+        comm.dist.all_gather_object(asks, ask, group=comm.group)
+        for q in range(comm.size):
+            if asks[q] and comm.rank in asks[q]:
+                sub = scs.csr_matrix(rows[asks[q][comm.rank] - row0, :])
+                reply[q] = (sub.indptr, sub.indices, sub.data)
+        replies = [None] * comm.size
+        comm.dist.all_gather_object(replies, reply, group=comm.group)
+        parts = []
+        for p in sorted(ask):                              # ascending owner: ascending rows
+            ip, ix, va = replies[p][comm.rank]
+            parts.append(scs.csr_matrix((va, ix, ip), shape=(len(ask[p]), n)))
+        return scs.vstack(parts, format='csr') if parts else scs.csr_matrix((0, n), dtype=rows.dtype)
+
+    @staticmethod
+    def _extended_block(lower_rows, loc, below, r0, r1):
+        """(E, A[E, E]) for E = below + [r0, r1): the rows `below` (lower_rows) above this rank's rows (loc); a column
+        outside E is left out."""
+        if below.size:
+            ext_ids = np.concatenate([below, np.arange(r0, r1, dtype=np.int64)])
+            a_ext = scs.csr_matrix(scs.vstack([lower_rows, loc], format='csc')[:, ext_ids])
+        else:
+            ext_ids = np.arange(r0, r1, dtype=np.int64)
+            a_ext = scs.csr_matrix(loc[:, r0:r1])
+        a_ext.sort_indices()
+        return ext_ids, a_ext
+
+    def _setup(self, loc, r0, n, comm, off, rows_of, build, work, updatable=False):
         import time
         t_start = time.perf_counter()
         L = self._L = _lib.lib()
@@ -741,18 +772,14 @@ class ShardedApproximateInverse:
         cols = loc.indices.astype(np.int64)
         below = np.unique(cols[cols < r0])
         lower_rows = rows_of(below)
-        if below.size:
-            ext_ids = np.concatenate([below, np.arange(r0, r1, dtype=np.int64)])
-            a_ext = scs.csr_matrix(scs.vstack([lower_rows, loc], format='csc')[:, ext_ids])
-        else:
-            ext_ids = np.arange(r0, r1, dtype=np.int64)
-            a_ext = scs.csr_matrix(loc[:, r0:r1])
-        a_ext.sort_indices()
+        ext_ids, a_ext = self._extended_block(lower_rows, loc, below, r0, r1)
         T = ApproximateInverse(a_ext, work=None, **build)
         self.levels, self.steps, self.step_size, self.drop = T.levels, T.steps, T.step_size, T.drop
         self.prefilter = T.prefilter
         g_own = scs.csr_matrix(T.csr()[below.size:, :])
         dropped = T.dropped_entries
+        self.updatable, self.updates, self.update_seconds = bool(updatable), 0, 0.0
+        self._builder, self._below = (T, below) if updatable else (None, None)    # (not kept: the builder is freed here)
         del T
         if self.drop and below.size:                           # the builder's count includes the rows of lower ranks
             if self.levels == 1 and self.steps == 0 and not self.prefilter:      # (the unfiltered pattern is known: the stored columns j <= i)
@@ -794,6 +821,29 @@ class ShardedApproximateInverse:
         h_idx = np.where(own, hi - r0, n_own + np.searchsorted(w_ids, hi)).astype(np.int32)
         self._n_xhalo, self._n_whalo = int(x_ids.size), int(w_ids.size)
         self._nnz_loc = (int(gi.size), int(hi.size))
+        if updatable:
+            # ---- what an update needs, fixed here: per lower rank the positions (among the own rows' entries of G, in
+            # CSR order) of the entries sent to it, in the order they were sent above; per higher rank the number of
+            # entries it sent; and for entry k of GH_loc its source -- the position of an own entry, or -1 - (its place
+            # in the received messages, higher ranks ascending).  `source` follows the concatenation `parts` through `order`.
+            if forced:                                         # the entries across the cut go pack -> send to self -> receive
+                routed = (grow >= cut) & (gi < cut)
+                sends = [(0, np.flatnonzero(routed))] if routed.any() else []
+                recvs = [(0, int(routed.sum()))] if routed.any() else []
+                source = np.arange(gi.size, dtype=np.int64)
+                source[routed] = -1 - np.arange(int(routed.sum()), dtype=np.int64)
+            else:
+                sends = [(int(p), np.flatnonzero(owner == p)) for p in np.unique(owner[away])]
+                recvs = [(q, int(everyone[q][comm.rank][0].size)) for q in range(comm.rank + 1, comm.size)
+                         if everyone[q] and comm.rank in everyone[q]]
+                n_recv = sum(cnt for _, cnt in recvs)
+                source = np.concatenate([np.flatnonzero(~away), -1 - np.arange(n_recv, dtype=np.int64)])
+            self._value_sends = [(p, self._index_buffer(comm, pos), int(pos.size)) for p, pos in sends]
+            self._value_recvs = recvs
+            self._value_source = self._index_buffer(comm, source[order])
+            es = np.dtype(self._dtype).itemsize
+            self._value_bufs = (comm.buffer(sum(cnt for _, _, cnt in self._value_sends) * es),
+                                comm.buffer(sum(cnt for _, cnt in recvs) * es))
         # ---- the plan and the two exchanges
         plan = ctypes.c_void_p()
         _lib.check(L.rlh_fsshard_create(ctypes.byref(plan), _lib.DTYPE_CODE[self._dtype], self.WORK[work], n_own, self._n_xhalo,
@@ -842,10 +892,122 @@ class ShardedApproximateInverse:
         return scs.csr_matrix((gv, gi.astype(np.int32), gp), shape=(self._n_own, self._n))
 
     def device_bytes(self):
-        """Device memory the plan holds on this rank: the two layouts and W."""
+        """Device memory the plan holds on this rank: the two layouts and W; with ``updatable=True`` also the builder
+        (G and G^H on the extended block, as ApproximateInverse.device_bytes counts them), the index arrays of an
+        update and its two message buffers."""
         nb = ctypes.c_int64()
         _lib.check(self._L.rlh_fsshard_info(self._plan, None, None, None, ctypes.byref(nb), None))
-        return int(nb.value)
+        more = 0
+        if self._builder is not None:
+            more = self._builder.device_bytes() + int(self._value_source.numel()) \
+                + sum(int(b.numel()) for _, b, _ in self._value_sends) + sum(int(b.numel()) for b in self._value_bufs)
+        return int(nb.value) + more
+
+    @staticmethod
+    def _index_buffer(comm, idx):
+        """An int64 index list where the library reads it (device memory under RCCL)."""
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        buf = comm.buffer(idx.nbytes)
+        if idx.size:
+            buf[:idx.nbytes].copy_(comm.torch.from_numpy(idx.view(np.uint8)))
+        return buf
+
+    def update_values(self, matrix):
+        """New matrix values on the kept pattern, from the same global matrix on every rank (as the constructor takes
+        it).  Collective; needs ``updatable=True``.  See `update_local_rows`."""
+        self._need_updatable()
+        refusal = None
+        shape, dtype = getattr(matrix, 'shape', None), getattr(matrix, 'dtype', None)
+        if shape != (self._n, self._n):
+            refusal = ValueError('the preconditioner was built for a matrix of size %d, got one of shape %s' % (self._n, shape))
+        elif np.dtype(dtype) != np.dtype(self._dtype):
+            refusal = ValueError('the preconditioner was built for a matrix of type %s, got one of type %s'
+                                 % (np.dtype(self._dtype).name, np.dtype(dtype).name))
+        self._agree(refusal, 'the new matrix')
+        full = full_from_upper(matrix)
+        r0, r1 = self._r0, self._r0 + self._n_own
+        self._update(scs.csr_matrix(full[r0:r1, :]), lambda ids: scs.csr_matrix(full[ids, :]))
+
+    def update_local_rows(self, rows):
+        """New matrix values on the kept pattern, from this rank's rows of the full matrix with global columns (as
+        `from_local_rows` takes them).  Collective; needs ``updatable=True``.
+
+        The rows of lower ranks come from their owners as at set-up, A'[E, E] is formed with the E of set-up (a
+        position A' does not store is zero, a new column outside E is ignored), the kept builder solves every row
+        again on its pattern (ApproximateInverse.update_values), the entries that lower ranks own as columns are
+        packed and sent as one device message per pair of ranks, and the plan's two layouts get the new values
+        (rlh_shardvalues_*): no pattern walk, no enrichment, no filter, no object collective beyond the fetch of the
+        rows, no transpose, no layout build, no HaloExchange set-up.  The ranks agree twice, each time by one
+        all-reduce: on size and type before anything else, and on the builders' success before any plan is touched.
+        If a rank refuses, that rank raises its own error and every other rank a RuntimeError naming it; `apply` and
+        `csr()` then give what they gave before.  `updates` counts the successful calls; `update_seconds` is the host
+        wall time of the last."""
+        self._need_updatable()
+        refusal = None
+        shape, dtype = getattr(rows, 'shape', None), getattr(rows, 'dtype', None)
+        if shape != (self._n_own, self._n):
+            refusal = ValueError('the preconditioner was built for %d rows of a matrix of size %d, got rows of shape %s'
+                                 % (self._n_own, self._n, shape))
+        elif np.dtype(dtype) != np.dtype(self._dtype):
+            refusal = ValueError('the preconditioner was built for a matrix of type %s, got one of type %s'
+                                 % (np.dtype(self._dtype).name, np.dtype(dtype).name))
+        self._agree(refusal, 'the new rows')
+        rows = scs.csr_matrix(rows)
+        self._update(rows, lambda ids: self._rows_from_owners(self._comm, self._offsets, rows, self._r0, self._n, ids))
+
+    def _need_updatable(self):
+        if self._builder is None:
+            raise RuntimeError('this ShardedApproximateInverse keeps no builder: construct it with updatable=True to update its values')
+
+    def _agree(self, refusal, what):
+        """One all-reduce: every rank learns which ranks refuse.  A refusing rank raises its own error (`refusal`), every
+        other rank a RuntimeError naming the refusing ranks."""
+        c = self._comm
+        flags = np.zeros(c.size, dtype=np.int64)
+        flags[c.rank] = 0 if refusal is None else 1
+        t = c.torch.from_numpy(flags).to(c.device)
+        c.dist.all_reduce(t, group=c.group)
+        if refusal is not None:
+            raise refusal
+        bad = np.flatnonzero(t.cpu().numpy())
+        if bad.size:
+            raise RuntimeError('rank %s refused %s: nothing was updated' % (', '.join(str(int(r)) for r in bad), what))
+
+    def _update(self, loc, rows_of):
+        import time
+        t_start = time.perf_counter()
+        L, c, T = self._L, self._comm, self._builder
+        r0, below = self._r0, self._below
+        loc.sort_indices()
+        _, a_ext = self._extended_block(rows_of(below), loc, below, r0, r0 + self._n_own)
+        refusal = None
+        try:
+            T.update_values(a_ext)
+        except (ValueError, _lib.RlhError) as e:
+            refusal = e
+        self._agree(refusal, 'the new matrix')
+        # ---- the own columns that lower ranks hold: one message per pair of ranks, as HaloExchange posts its rows
+        es = np.dtype(self._dtype).itemsize
+        first, h = int(below.size), T._h
+        sendbuf, recvbuf = self._value_bufs
+        ops, soff, roff = [], 0, 0
+        for p, dpos, cnt in self._value_sends:
+            _lib.check(L.rlh_shardvalues_pack(h, first, cnt, dpos.data_ptr(), sendbuf.data_ptr() + soff))
+            ops.append(c.dist.P2POp(c.dist.isend, sendbuf[soff:soff + cnt * es], p, group=c.group))
+            soff += cnt * es
+        for q, cnt in self._value_recvs:
+            ops.append(c.dist.P2POp(c.dist.irecv, recvbuf[roff:roff + cnt * es], q, group=c.group))
+            roff += cnt * es
+        for w in (c.dist.batch_isend_irecv(ops) if ops else ()):
+            w.wait()
+        n_recv = roff // es
+        _lib.check(L.rlh_shardvalues_refill(self._plan, h, first, self._value_source.data_ptr(), n_recv,
+                                            recvbuf.data_ptr() if n_recv else None))
+        gp, gi, _ = self._g
+        G = T.csr()
+        self._g = (gp, gi, np.ascontiguousarray(G.data[int(G.indptr[first]):], dtype=self._dtype))
+        self.updates += 1
+        self.update_seconds = time.perf_counter() - t_start
 
     def algorithmic_bytes(self, m):
         """This rank's share of one application: its entries of G and G^H at 4 + sizeof V, x read (own and halo rows)

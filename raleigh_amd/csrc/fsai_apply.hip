@@ -36,8 +36,13 @@
 // New values (rlh_fsvalues_plan): after the handle's values were updated on its kept pattern, fsap_fill runs again on the
 // plan's kept layouts, once fsap_same_rows has found every row as long in the layout as in the handle; W and the structure stay.
 //
-// Row shards (rlh_fsshard_*, at the end of the file): the same layout and the same two products on a rank's rows of G
-// and of G^H, as the compile-time variant SHARD of fsap_product; the halo rows of W travel between the two products.
+// Row shards (rlh_fsshard_*): the same layout and the same two products on a rank's rows of G and of G^H, as the
+// compile-time variant SHARD of fsap_product; the halo rows of W travel between the two products.
+//
+// New values on a row shard (rlh_shardvalues_*, at the end of the file): the values of both kept layouts from a builder
+// handle on the shard's extended block, the own columns that higher ranks computed arriving as a packed block.  The
+// plan does NOT keep the row pointers of GH_loc: they are rebuilt from rlen and tptr in scratch at every refill (one
+// pass over n_own rows and a scan), so a plan holds the bytes it always held.
 #include "fsai.h"
 #include "spmm.h"
 
@@ -410,6 +415,8 @@ struct FsPlan {
   int dtype = 0, work = 0;
   int64_t n_own = 0, n_xhalo = 0, n_whalo = 0;
   int64_t m_first = -1, placed = 0;  // the vectors of the last rlh_fsshard_first (-1: none yet), the halo rows placed since
+  int64_t refills = 0;               // rlh_shardvalues_refill: the successful ones and the device seconds of the last
+  double refill_seconds = 0;
   Layout g, gh;                      // G for the first product, G^H for the second
   DevBuf<char> w;                    // W = G X
   int64_t wrows() const { return n_own + n_whalo; }
@@ -766,3 +773,208 @@ extern "C" int rlh_fsshard_info(rlh_fsshard_t p, int *work, int64_t *stored_slot
 }
 
 extern "C" int rlh_fsshard_destroy(rlh_fsshard_t p) { return plan_destroy(p); }
+
+// ---------------------------------------------------------------- new values on a row shard (rlh_shardvalues_*)
+namespace rlh {
+namespace {
+
+enum { kErrSource = 5 };                      // (after kErrLength: a row of another length is reported first)
+
+// out[i] = the handle's value at entry ip[0] + pos[i] (ip: the handle's row pointers from first_row on, `rows` rows); a
+// position outside those rows' entries is not followed
+template <typename T>
+__global__ __launch_bounds__(kBlock) void shv_pack(int64_t count, int64_t rows, const int64_t *__restrict__ ip,
+                                                   const int64_t *__restrict__ pos, const T *__restrict__ va, T *__restrict__ out) {
+  const int64_t base = ip[0], entries = ip[rows] - base, stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += stride) {
+    const int64_t q = pos[i];
+    T v = zero_of(T());
+    if (q >= 0 && q < entries) v = va[base + q];
+    out[i] = v;
+  }
+}
+
+// What a refill checks before it writes (one launch, one status record): the entries of the handle's rows (st->nnz),
+// every row of G_loc as long in the layout as in the handle (fsap_same_rows from an offset), every source of GH_loc in
+// [-n_recv, entries)
+__global__ __launch_bounds__(kBlock) void shv_check(LayoutView G, const int64_t *__restrict__ ip, int64_t nsrc,
+                                                    const int64_t *__restrict__ src, int64_t n_recv, ApplyStatus *st) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock, first = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t entries = ip[G.n] - ip[0];
+  if (first == 0) st->nnz = entries;
+  for (int64_t r = first; r < G.n; r += stride)
+    if (ip[r + 1] - ip[r] != (int64_t)G.rlen[r] + (G.tptr[r + 1] - G.tptr[r])) build_error(st, kErrLength, r);
+  for (int64_t k = first; k < nsrc; k += stride) {
+    const int64_t s = src[k];
+    if (s < -n_recv || s >= entries) build_error(st, kErrSource, k);
+  }
+}
+
+// the entries of every row of a layout, sliced part and tail together (their scan: the row pointers of the CSR arrays
+// the layout was made from)
+__global__ __launch_bounds__(kBlock) void shv_row_lengths(LayoutView L, int64_t *__restrict__ len) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < L.n; r += stride)
+    len[r] = (int64_t)L.rlen[r] + (L.tptr[r + 1] - L.tptr[r]);
+}
+
+// The value of entry k of the CSR arrays a layout was made from (va: the handle's values, ip: its row pointers from
+// first_row on).  G_loc: the handle's entry ip[0] + k.  GH_loc: the conjugate of the handle's entry ip[0] + src[k], or of
+// recv[-1 - src[k]] for a negative source -- the select and the conjugation happen on the way into the slot.
+template <typename T> struct OwnValues {
+  const T *va;
+  const int64_t *ip;
+  __device__ __forceinline__ T operator()(int64_t k) const { return va[ip[0] + k]; }
+};
+template <typename T> struct SourcedValues {
+  const T *va;
+  const int64_t *ip;
+  const T *recv;
+  const int64_t *src;
+  __device__ __forceinline__ T operator()(int64_t k) const {
+    const int64_t s = src[k];
+    return dev_conj(s >= 0 ? va[ip[0] + s] : recv[-1 - s]);
+  }
+};
+
+// fsap_fill for the values alone: the slots position-major within the slice, then the tails of the slice's rows by the
+// whole wave; columns, padding slots and the structure are not touched.  rp: the row pointers of the CSR order (those of
+// the handle from first_row on for G_loc, the scan of shv_row_lengths for GH_loc); entry k of row r is rp[r] - rp[0] + k.
+template <typename T, typename V, typename F>
+__global__ __launch_bounds__(kBlock) void shv_fill(LayoutView L, const int64_t *__restrict__ rp, F value, V *__restrict__ val,
+                                                   V *__restrict__ tval) {
+  const int lane = threadIdx.x & 63;
+  const int64_t waves = (int64_t)gridDim.x * kWaves, e0 = rp[0];
+  for (int64_t s = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6); s < L.slices; s += waves) {
+    const int64_t r = s * 64 + lane, rows = rows_of(L.n, s), base = L.off[s];
+    const bool live = r < L.n;
+    const int64_t my = live ? L.rlen[r] : 0, k0 = live ? rp[r] - e0 : 0;
+    for (int64_t p = 0; p < my; ++p) down(value(k0 + p), &val[base + p * rows + lane]);
+    const int64_t t0 = live ? L.tptr[r] : 0, tc = live ? L.tptr[r + 1] - t0 : 0;
+    unsigned long long todo = __ballot(tc > 0);
+    while (todo) {
+      const int t = __ffsll(todo) - 1;
+      todo &= todo - 1;
+      const int64_t from = lane_value(k0 + my, t), dst = lane_value(t0, t), cnt = lane_value(tc, t);
+      for (int64_t e = lane; e < cnt; e += 64) down(value(from + e), &tval[dst + e]);
+    }
+  }
+}
+
+// the grid of a refill's kernels: at most kRefillBlocksPerCu workgroups per CU, as refill_layout
+unsigned refill_grid(int64_t items, int64_t per) { return blocks_for(items, per, (int64_t)ctx().num_cu * kRefillBlocksPerCu); }
+
+}  // namespace
+}  // namespace rlh
+
+extern "C" int rlh_shardvalues_pack(rlh_fsai_t h, int64_t first_row, int64_t count, const int64_t *d_pos, void *d_out) {
+  constexpr const char *kEntry = "rlh_shardvalues_pack";
+  if (int rc = require_ready()) return rc;
+  RLH_REQUIRE(h != nullptr, "%s: null handle", kEntry);
+  RLH_REQUIRE(count >= 0, "%s: negative size", kEntry);
+  RLH_REQUIRE(first_row >= 0 && first_row <= h->n, "%s: first row %lld of a handle of %lld rows", kEntry, (long long)first_row,
+              (long long)h->n);
+  if (count == 0) return 0;
+  RLH_REQUIRE(d_pos && d_out, "%s: null pointer", kEntry);
+  const int64_t room_p = bytes_from(d_pos), room_o = bytes_from(d_out);
+  const int64_t es = h->dtype == RLH_S ? 4 : h->dtype == RLH_Z ? 16 : 8;
+  RLH_REQUIRE((room_p < 0 || room_p >= 8 * count) && (room_o < 0 || room_o >= es * count), "%s: an array holds fewer than %lld entries",
+              kEntry, (long long)count);
+  if (h->n == 0 || !h->spd) {                          // no entries: every position lies outside
+    RLH_HIP(hipMemsetAsync(d_out, 0, (size_t)(es * count), ctx().stream));
+    return 0;
+  }
+  const SpdArrays g = spd_arrays(h->spd, 0);
+  return with_types(h->dtype, 0, [&](auto t, auto, auto) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(shv_pack<T>, dim3(refill_grid(count, kBlock)), dim3(kBlock), 0, ctx().stream, count, h->n - first_row,
+                       g.indptr + first_row, d_pos, (const T *)g.val, (T *)d_out);
+    RLH_HIP(hipGetLastError());
+    return 0;
+  });
+}
+
+extern "C" int rlh_shardvalues_refill(rlh_fsshard_t p, rlh_fsai_t h, int64_t first_row, const int64_t *d_src, int64_t n_recv,
+                                      const void *d_recv) {
+  constexpr const char *kEntry = "rlh_shardvalues_refill";
+  if (int rc = require_ready()) return rc;
+  RLH_REQUIRE(p != nullptr, "%s: null plan", kEntry);
+  RLH_REQUIRE(h != nullptr, "%s: null handle", kEntry);
+  RLH_REQUIRE(p->dtype == h->dtype, "%s: the plan's dtype (%d) is not the handle's (%d)", kEntry, p->dtype, h->dtype);
+  RLH_REQUIRE(n_recv >= 0, "%s: negative size", kEntry);
+  RLH_REQUIRE(first_row >= 0 && h->n - first_row == p->n_own, "%s: the plan has %lld own rows, the handle %lld from row %lld on", kEntry,
+              (long long)p->n_own, (long long)(h->n - first_row), (long long)first_row);
+  if (p->n_own == 0) {                                 // nothing to fill: a valid refill
+    p->refill_seconds = 0;
+    ++p->refills;
+    return 0;
+  }
+  RLH_REQUIRE(h->spd != nullptr, "%s: the handle holds no matrix", kEntry);
+  RLH_REQUIRE(d_src || p->gh.nnz == 0, "%s: null source list", kEntry);
+  RLH_REQUIRE(d_recv || n_recv == 0, "%s: null block of received values", kEntry);
+  const int64_t es = h->dtype == RLH_S ? 4 : h->dtype == RLH_Z ? 16 : 8;
+  const int64_t room_s = bytes_from(d_src), room_r = bytes_from(d_recv);
+  RLH_REQUIRE(room_s < 0 || room_s >= 8 * p->gh.nnz, "%s: the source list holds fewer than the %lld entries of G^H", kEntry,
+              (long long)p->gh.nnz);
+  RLH_REQUIRE(room_r < 0 || room_r >= es * n_recv, "%s: the block of received values holds fewer than %lld", kEntry, (long long)n_recv);
+  const SpdArrays g = spd_arrays(h->spd, 0);
+  const int64_t *ip = g.indptr + first_row;            // rows first_row .. n of the handle's G: the plan's G_loc
+  hipStream_t st = ctx().stream;
+  const int64_t n = p->n_own;
+  StreamTimer timer;
+  if (int rc = timer.start()) return rc;
+  DevBuf<ApplyStatus> status;
+  DevBuf<int64_t> len, bsum, hp;
+  if (int rc = status.alloc(1)) return rc;
+  if (int rc = len.alloc(n)) return rc;
+  if (int rc = bsum.alloc((n + kScanTile - 1) / kScanTile + 1)) return rc;
+  if (int rc = hp.alloc(n + 1)) return rc;
+  // ---- every check before any write to the plan; the one synchronisation for the status
+  ApplyStatus hs{};
+  hs.err = kNoError;
+  RLH_HIP(hipMemcpyAsync(status, &hs, sizeof hs, hipMemcpyHostToDevice, st));
+  const int64_t most = n > p->gh.nnz ? n : p->gh.nnz;
+  hipLaunchKernelGGL(shv_check, dim3(refill_grid(most, kBlock)), dim3(kBlock), 0, st, p->g.view(), ip, p->gh.nnz, d_src, n_recv,
+                     status.get());
+  RLH_HIP(hipGetLastError());
+  RLH_HIP(hipMemcpyAsync(&hs, status, sizeof hs, hipMemcpyDeviceToHost, st));
+  RLH_HIP(hipStreamSynchronize(st));
+  RLH_REQUIRE((int64_t)hs.nnz == p->g.nnz, "%s: the plan holds %lld entries of G, the handle %lld from row %lld on", kEntry,
+              (long long)p->g.nnz, (long long)hs.nnz, (long long)first_row);
+  if (hs.err != kNoError) {
+    const long long pos = (long long)(hs.err & kPosMask);
+    if ((int)(hs.err >> 56) == kErrLength)
+      set_error("%s: row %lld of G has another length in the plan than in the handle", kEntry, pos);
+    else
+      set_error("%s: entry %lld of G^H has its source outside [-%lld, %lld)", kEntry, pos, (long long)n_recv, (long long)hs.nnz);
+    return 1;
+  }
+  // ---- the row pointers of GH_loc, then the values of both layouts
+  hipLaunchKernelGGL(shv_row_lengths, dim3(refill_grid(n, kBlock)), dim3(kBlock), 0, st, p->gh.view(), len.get());
+  RLH_HIP(hipGetLastError());
+  if (int rc = exclusive_scan(n, len, bsum, hp)) return rc;
+  if (int rc = with_types(p->dtype, p->work, [&](auto t, auto v, auto) {
+        using T = decltype(t);
+        using V = decltype(v);
+        const T *va = (const T *)g.val;
+        const dim3 grid(refill_grid(p->g.slices, kWaves));
+        hipLaunchKernelGGL((shv_fill<T, V, OwnValues<T>>), grid, dim3(kBlock), 0, st, p->g.view(), ip, OwnValues<T>{va, ip}, (V *)p->g.val.get(),
+                           (V *)p->g.tval.get());
+        hipLaunchKernelGGL((shv_fill<T, V, SourcedValues<T>>), grid, dim3(kBlock), 0, st, p->gh.view(), (const int64_t *)hp.get(),
+                           SourcedValues<T>{va, ip, (const T *)d_recv, d_src}, (V *)p->gh.val.get(), (V *)p->gh.tval.get());
+        RLH_HIP(hipGetLastError());
+        return 0;
+      }))
+    return rc;
+  if (int rc = timer.stop()) return rc;                // the handle's arrays, the caller's and the scratch are not referenced after the return
+  p->refill_seconds = timer.seconds();
+  ++p->refills;
+  return 0;
+}
+
+extern "C" int rlh_shardvalues_info(rlh_fsshard_t p, int64_t *updates, double *seconds) {
+  RLH_REQUIRE(p != nullptr, "rlh_shardvalues_info: null plan");
+  if (updates) *updates = p->refills;
+  if (seconds) *seconds = p->refill_seconds;
+  return 0;
+}

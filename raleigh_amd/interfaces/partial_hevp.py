@@ -57,7 +57,9 @@ def partial_hevp(A, B=None, T=None, buckling=False, sigma=0, which=6, tol=1e-4, 
     (`vectors` and ``operator=ShardedSparseMatrix(...)``) the approximate inverse is `ShardedApproximateInverse`
     (algebra/hip/dist.py), built with the operator's partition: every rank holds its rows of G and its columns of G^H,
     and an application exchanges the rows of x it reads from lower ranks and the rows of G x it reads from higher
-    ones; beyond ``levels=1, steps=0`` its pattern depends on the partition.
+    ones; beyond ``levels=1, steps=0`` its pattern depends on the partition.  Built with ``updatable=True`` it keeps
+    its builder, and ``T.update_values(matrix)`` / ``T.update_local_rows(rows)`` (collective) give it the values of a
+    new matrix on the kept pattern as `ApproximateInverse.update_values` does on one GPU.
 
     Returns (lmd, x, status): eigenvalues ascending, eigenvectors as columns, status as
     in the reference (0 success, 1 iteration limit, 2 no search directions, 3/4 some

@@ -17,6 +17,14 @@ else is "no winner".  Nothing here is a threshold, and nothing here says anythin
 
     python tools/approx_inverse_shard_bench.py [--out profiles/r18_approx_inverse_sharded.txt] [--m 16] [--calls 20]
                                                [--repeats 5] [--lap 64] [--no-resources]
+
+--update runs another leg INSTEAD: construction against update_values on re-valued copies of the matrix taking turns in
+one run (construct on A_0, update to A_1, construct on A_1, update to A_2, ...: `revalued` below is the recipe of
+tests/_fsai_values_cases.py), work='native', on lap3d and the config-3 surrogate at levels 1, 2, 3 and levels=1 with
+steps=4, step_size=4; host wall seconds with the stream drained at both ends, fastest .. slowest of --repeats after a
+warm-up round, the comparison being the construction of the same run; construction with updatable=False next to them.
+
+    python tools/approx_inverse_shard_bench.py --update [--out profiles/r25_approx_inverse_shard_update.txt] [--repeats 5]
 """
 import argparse
 import ctypes
@@ -37,15 +45,77 @@ def resource_lines():
     return out + ['   ' + ln for ln in (r.stdout.strip().splitlines() or ['(no compiler here: %s)' % r.stderr.strip()[-200:]])]
 
 
+def revalued(A, seed):
+    """tests/_fsai_values_cases.py's recipe: every stored off-diagonal entry of the upper triangle times a factor uniform in
+    [0.5, 1), every diagonal entry times one in [1, 2), the lower triangle mirrored; the structure is unchanged and a
+    diagonally dominant matrix stays so."""
+    import scipy.sparse as sp
+    n = A.shape[0]
+    rng = np.random.default_rng(seed)
+    u = sp.triu(A, format='coo')
+    factor = np.where(u.row == u.col, rng.uniform(1.0, 2.0, u.nnz), rng.uniform(0.5, 1.0, u.nnz)).astype(A.real.dtype)
+    up = sp.csr_matrix((u.data * factor, (u.row, u.col)), shape=(n, n))
+    B = sp.csr_matrix(up + sp.triu(up, k=1).conj().T).astype(A.dtype)
+    B.sort_indices()
+    return B
+
+
+def update_leg(args, say, span, verdict, comm):
+    import scipy.sparse as sp
+    from raleigh_amd import _lib
+    from raleigh_amd.algebra.hip.dist import ShardedApproximateInverse
+    from raleigh_amd.synthetic import lap3d_rows, fe_surrogate
+    L = _lib.lib()
+    side = args.lap
+    lap = lambda: lap3d_rows(side, side, side, 1.0, 1.01, 1.02, 0, side ** 3)
+    configs = [('levels=%d' % lv, dict(levels=lv)) for lv in (1, 2, 3)] + [('levels=1, steps=4, step_size=4', dict(steps=4, step_size=4))]
+
+    def timed(f):
+        _lib.check(L.rlh_sync())
+        t0 = time.perf_counter()
+        out = f()
+        _lib.check(L.rlh_sync())
+        return time.perf_counter() - t0, out
+    for title, make in (('lap3d %d^3' % side, lap), ('config-3 FE surrogate', fe_surrogate)):
+        A = sp.csr_matrix(make().astype(np.float64))
+        A.sort_indices()
+        n = A.shape[0]
+        copies = [revalued(A, 200 + k) for k in range(args.repeats + 2)]
+        say('== %s: n = %d, nnz = %d (%.1f per row)' % (title, n, A.nnz, A.nnz / n))
+        for name, kw in configs:
+            build, plain, update, device = [], [], [], []
+            for k in range(args.repeats + 1):                  # (round 0 is the warm-up)
+                tb, T = timed(lambda: ShardedApproximateInverse(copies[k], comm, work='native', updatable=True, **kw))
+                tp, P = timed(lambda: ShardedApproximateInverse(copies[k], comm, work='native', **kw))
+                tu, _ = timed(lambda: T.update_values(copies[k + 1]))
+                sec = ctypes.c_double()
+                _lib.check(L.rlh_shardvalues_info(T._plan, None, ctypes.byref(sec)))
+                if k:
+                    build.append(tb), plain.append(tp), update.append(tu), device.append(sec.value * 1e3)
+                nnz, extra = T.nnz, T.device_bytes() - P.device_bytes()
+                del T, P
+            say('   %-32s nnz(G) = %d (%.1f per row); updatable=True holds %.1f MB more' % (name, nnz, nnz / n, extra / 1e6))
+            say('      construction updatable=True   %s s' % span(build))
+            say('      construction updatable=False  %s s' % span(plain))
+            say('      update_values                 %s s (the refill of the plan: %s ms on the stream)' % (span(update), span(device, '%.3f')))
+            say('      ' + verdict('update_values', 'construction (updatable=True)', update, build))
+            say('      ' + verdict('construction updatable=True', 'construction updatable=False', build, plain))
+            say('      fastest against fastest: construction / update = %.1f' % (min(build) / min(update)))
+        say()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'r18_approx_inverse_sharded.txt'))
+    ap.add_argument('--update', action='store_true', help='the construction-against-update leg instead of the application and the solves')
+    ap.add_argument('--out', default=None)
     ap.add_argument('--m', type=int, default=16)
     ap.add_argument('--calls', type=int, default=20)
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--lap', type=int, default=64)
     ap.add_argument('--no-resources', action='store_true', help='skip the compiler\'s resource lines (needs hipcc)')
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, 'profiles', 'r25_approx_inverse_shard_update.txt' if args.update else 'r18_approx_inverse_sharded.txt')
     import torch
     import torch.distributed as dist
     import scipy.sparse as sp
@@ -81,6 +151,20 @@ def main():
             return '%s loses to %s (fastest %.4g > slowest %.4g)' % (a, b, min(ta), max(tb))
         return 'no winner between %s and %s (the ranges overlap)' % (a, b)
 
+    if args.update:
+        say('# ShardedApproximateInverse(updatable=True): construction against update_values, forced collectives at ONE rank (two virtual')
+        say('# ranks: the entries across the cut are packed, sent to self and received), float64, work=native')
+        say('# %s, host wall seconds with the stream drained at both ends, %d repeats after a warm-up round, fastest .. slowest;'
+            % (torch.cuda.get_device_name(0), args.repeats))
+        say('# re-valued copies of the matrix take turns; written by tools/approx_inverse_shard_bench.py --update')
+        say('# forced at one rank: nothing here is a measurement across GPUs')
+        say()
+        update_leg(args, say, span, verdict, comm)
+        _lib.check(L.rlh_sync())
+        torch.cuda.synchronize()
+        dist.destroy_process_group()
+        out_file.close()
+        return
     say('# ShardedApproximateInverse with forced collectives at ONE rank (two virtual ranks, sends to self), float64, m = %d' % m)
     say('# %s, %d calls per timing, %d repeats after a warm-up, fastest .. slowest; written by tools/approx_inverse_shard_bench.py'
         % (torch.cuda.get_device_name(0), args.calls, args.repeats))
